@@ -9,8 +9,10 @@ BASELINE.json (1.2 M Gaussians, 1200x680):
 `value` = frames / s over all ranks (weak scaling: every rank tracks and renders its own view; see
 `config.parallelism` in the JSON line and DESIGN.md section 5 for what is exchanged).
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with `roofline` for the
-dominant kernel and `cpu_baseline` (oracle on the host cores, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly `--steps` frames (`ms_per_step`,
+`value`) and prints the headline fields; `--full` adds the further timed blocks, `roofline` for the dominant kernel,
+`cpu_baseline` (oracle on the host cores, bounded sample) and the other legs.  `--dump-outputs DIR` writes what the
+last timed frame computed (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -62,8 +64,17 @@ def parse():
                     help="untimed frames of the real workload before the warm-up: a FIXED count (every rank issues the same "
                          "collectives), >= 1.5 s of GPU work - a fresh box needs that long to reach its steady clocks (the "
                          "driver's first block of round 3 ran 25 %% slower than its later ones after 0.1 s of pre-warm)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps frames, each bracketed as the contract says: "
-                                                           "`value` is their MEDIAN (the first block is reported beside it)")
+    ap.add_argument("--repeats", type=int, default=5, help="with --full: timed blocks of --steps frames, each bracketed as the "
+                                                           "contract says; their median is reported in `repeats` (`value` is "
+                                                           "the first block)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline block, run everything else the line can report: further timed blocks (--repeats), "
+                         "the unit taken apart, the scaling legs, the kernel profile / roofline, the surface, schedule, "
+                         "sequence, TUM-ICP, drop-in and configs[4] legs, the CPU baseline.  Without it a run sets up, warms "
+                         "up, times --steps frames and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/64, "
+                         "about 16 MB; see dump_outputs)")
     ap.add_argument("--surface-map", action="store_true", help="headline leg on the single-layer surface map instead of the "
                                                                "SURVEY 8d volume generator")
     ap.add_argument("--no-schedule", action="store_true", help="skip the reference-schedule leg (6 frames: 6 tracks + "
@@ -228,8 +239,8 @@ def main():
 
     def frame():
         pipe.track(track_stage)
-        map_step()
-        return pipe.result()
+        loss = map_step()
+        return pipe.result(), loss
 
     def barrier():
         if world > 1:
@@ -269,7 +280,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         th = time.perf_counter()
-        frame()
+        last = frame()
         host_ms.append(1e3 * (time.perf_counter() - th))
         frame_t0.append(th)
     barrier()
@@ -278,9 +289,47 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        opt.flush()                                           # every rank: a pending row exchange is collective
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last, opt, N)
 
-    # further timed blocks (same K): run-to-run spread on this box.  `value` stays the contract's first block.
-    block_ms = [1e3 * dt / args.steps]
+    # the headline: exactly --steps frames, barrier-bracketed, max over ranks
+    ms_per_step = 1e3 * dt / args.steps
+    frames_per_step = 1 if mode == "tileband" else world
+    fps = frames_per_step * 1e3 / ms_per_step
+    par = {"single": "1 GPU",
+           "sparse": f"dp{world}: replicated map and Adam state, one view per rank, RCCL all-gather of the gradient rows that "
+                     "exist (fixed capacity, counts in band, no host sync), identical Adam step on every replica",
+           "sharded": f"dp{world}: one view per rank, dense RCCL reduce-scatter of the gradients, Adam on the rank's row "
+                      "shard (optimizer state sharded), all-gather of the updated rows",
+           "tileband": f"tp{world}: ONE view split into tile bands, loss normalisers all-reduced, sparse gradient-row "
+                       "exchange, identical Adam step on every replica"}[mode]
+    workload = ("`value` counts UNITS, not SLAM frames (the SLAM frame rate by the reference's definition is "
+                "`slam_frames_per_sec`, from the `slam_sequence` leg of --full).  One UNIT per step = 1 ICP track (3 levels x 5 GN "
+                "iters, 1200x680, on a second HIP stream) + 1 map-optimisation iteration (raster fwd + masked L1 colour / gated "
+                f"depth loss + attach regulariser + raster bwd + fused Adam) over {N} "
+                + ("opaque wall discs (single-layer surface map)" if args.surface_map else
+                   "random Gaussians (SURVEY.md 8d generator, seed 2024)") +
+                ", all tiles.  `value` counts these units; the reference's Replica schedule runs 50 iterations "
+                "every 6th frame (~8.3 per frame): see frames_per_sec_replica_schedule")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({
+                "metric": "hot_path_units_per_sec", "value": round(fps, 3), "unit": "units/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+                "higher_is_better": True, "scaling": "strong" if mode == "tileband" else "weak", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic",
+                "config": {"workload": workload, "gaussians": N, "image": [cam.H, cam.W], "mode": mode, "parallelism": par},
+                "cold_first_frame_ms": round(cold_ms, 2), "prewarm_frames": args.prewarm,
+                "mapper_reserved_cus": args.reserve_cus, "rccl_ranks": rccl_ranks, "full": False}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # further timed blocks (same K): the run-to-run spread.  `value` stays the first block.
+    block_ms = [ms_per_step]
     for _ in range(max(0, args.repeats - 1)):
         barrier()
         tb = time.perf_counter()
@@ -517,21 +566,11 @@ def main():
         if not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only
             cpu = cpu_baseline(g, cam, d0, d1, dev)
 
-        par = {"single": "1 GPU",
-               "sparse": f"dp{world}: replicated map and Adam state, one view per rank, RCCL all-gather of the gradient rows that "
-                         "exist (fixed capacity, counts in band, no host sync), identical Adam step on every replica",
-               "sharded": f"dp{world}: one view per rank, dense RCCL reduce-scatter of the gradients, Adam on the rank's row "
-                          "shard (optimizer state sharded), all-gather of the updated rows",
-               "tileband": f"tp{world}: ONE view split into tile bands, loss normalisers all-reduced, sparse gradient-row "
-                           "exchange, identical Adam step on every replica"}[mode]
-        frames_per_step = 1 if mode == "tileband" else world
-        # `value`: the MEDIAN of the `--repeats` timed blocks, each of which is the contract's measurement (exactly K steps between
-        # barrier + synchronize, max over ranks).  Rounds 4-6 reported the first block; on some leases ONE host frame in ~1 500
-        # takes 8.5-8.7 ms (the same length every time, with or without a short GIL switch interval, with no garbage collection
-        # inside it - `host_frames_over_2ms`; on other leases 12 000 frames pass without one), and when it lands in a 20-step
-        # block of 8.3 ms it halves that block.  The first block stays in the line (`first_block_ms_per_step`).
-        med_ms = sorted(block_ms)[len(block_ms) // 2]
-        fps = frames_per_step * 1e3 / med_ms
+        # `value` / `ms_per_step`: the first block, exactly --steps frames between barrier + synchronize, max over ranks - the
+        # same as a plain run.  Round 6 reported the MEDIAN of the `--repeats` blocks instead: on some machines ONE host frame
+        # in ~1 500 takes 8.5-8.7 ms (the same length every time, with or without a short GIL switch interval, with no garbage
+        # collection inside it - `host_frames_over_2ms`; on other machines 12 000 frames pass without one), and when it lands
+        # in a 20-step block of 8.3 ms it halves that block.  The median stays in the line (`repeats.median_ms_per_step`).
         sched = None
         if world == 1 and not args.no_schedule and not args.no_surface:
             sched = reference_schedule_leg(cam, N, dev)
@@ -546,18 +585,11 @@ def main():
         spread = (bs[-1] - bs[0]) / bs[len(bs) // 2]
         result = {
             "metric": "hot_path_units_per_sec", "value": round(fps, 3), "unit": "units/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(med_ms, 3),
-            "first_block_ms_per_step": round(1e3 * dt / args.steps, 3),
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "first_block_ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "strong" if mode == "tileband" else "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "`value` counts UNITS, not SLAM frames (the SLAM frame rate by the reference's definition is "
-                                   "`slam_frames_per_sec`, from the `slam_sequence` leg).  One UNIT per step = 1 ICP track (3 levels x 5 GN iters, 1200x680, on a second HIP stream) "
-                                   "+ 1 map-optimisation iteration (raster fwd + masked L1 colour / gated depth loss + attach "
-                                   f"regulariser + raster bwd + fused Adam) over {N} "
-                                   + ("opaque wall discs (single-layer surface map)" if args.surface_map else
-                                      "random Gaussians (SURVEY.md 8d generator, seed 2024)") +
-                                   ", all tiles.  `value` counts these units; the reference's Replica schedule runs 50 iterations "
-                                   "every 6th frame (~8.3 per frame): see frames_per_sec_replica_schedule",
+            "config": {"workload": workload,
                        "gaussians": N, "gaussians_with_gradient": rows_touched, "image": [cam.H, cam.W],
                        "instances": R, "instances_consumed": consumed,
                        "pixel_pairs_evaluated": pairs,
@@ -587,7 +619,7 @@ def main():
                         "host_frames_over_2ms": slow_frames,
                         "slowest_host_frame_ms_per_block": [round(max(host_ms[i:i + args.steps]), 3)
                                                             for i in range(0, len(host_ms), args.steps)]},
-            "rccl_ranks": rccl_ranks,
+            "rccl_ranks": rccl_ranks, "full": True,
             "slam_frames_per_sec": None if seq is None else seq["fps"],
             "slam_sequence": seq,
             "icp_track_ms_tum_480x640_noisy": tum,
@@ -607,6 +639,38 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_ROWS = 65536
+
+
+def dump_outputs(out_dir, last, opt, N):
+    """--dump-outputs: what the last timed frame handed its caller, as float32 .npy files (about 16 MB at the default size):
+      icp_result       float32[20] of icp_track: the pose (16, row-major) + [valid_ratio, p2p_loss, n_singular, aborted]
+      map_loss         the map step's loss (0-dim)
+      map_losses       float32[4]: total, colour, depth, ssim (one-call step only; the autograd step of --mode sharded
+                       returns the total alone)
+      map_{xyz,shs,raw8}_sample: the updated map's rows [:, 3 / 48 / 8] for a FIXED sample of 65 536 rows (seeded; every
+      row when the map is smaller); map_sample_rows (float64) holds their indices
+    The inputs are seeded, so runs with the same arguments start from identical data.  Two runs of one build agree to
+    ~1e-5 relative here; the step's rendered maps are left out: after thousands of steps with float-atomic gradient sums
+    ~1 % of their pixels flip a discontinuous decision (depth gate, stop rule) from run to run."""
+    import numpy as np
+    icp_out, loss = last
+    rows = (np.arange(N) if N <= DUMP_SAMPLE_ROWS
+            else np.sort(np.random.RandomState(0).choice(N, DUMP_SAMPLE_ROWS, replace=False)))
+    idx = torch.from_numpy(rows).to(opt.state["xyz"]["p"].device)
+    arrays = {"icp_result": icp_out, "map_loss": loss}
+    if opt.last_render is not None:
+        arrays["map_losses"] = opt.last_losses
+    for nm in ("xyz", "shs", "raw8"):
+        arrays[f"map_{nm}_sample"] = opt.state[nm]["p"][:N].index_select(0, idx)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    host["map_sample_rows"] = rows.astype(np.float64)
+    assert sum(a.nbytes for a in host.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def reference_schedule_leg(cam, N, dev, cycles=3, iters=50, every=6, window=5, n_new=40800):

@@ -19,9 +19,13 @@ def test_default_flags_are_the_contracts(monkeypatch):
     assert a.sequence_frames >= 300 and not a.no_sequence and not a.no_config5 and not a.no_dropin and a.only is None
     assert not a.no_cpu_baseline and not a.no_schedule and not a.no_surface and not a.surface_map
     assert a.prewarm >= 3000 and a.repeats == 5
+    assert not a.full and a.dump_outputs is None          # a plain run: the headline only, nothing written
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "50", "--warmup", "5"])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 50, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
 
 
 def test_committed_pmc_numbers_and_bench_line_belong_to_the_same_kernel_sources():

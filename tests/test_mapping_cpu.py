@@ -334,20 +334,12 @@ def test_update_poses_and_the_small_accessors():
                                         ("scannetpp_base.yaml", "scannetpp_args")])
 def test_argument_sets_are_the_references_config_files(leaf, build):
     """replica_args() / tum_args() against configs/base.yaml overlaid with the dataset's base file (the `parent:` chain the
-    reference's loader follows), read from /root/reference where it lies: every value the two have in common is equal, and
-    every name Mapping / Tracker / Renderer / IcpTracker read from `args` is in the argument set.  (Build container only.)"""
-    import yaml
-    cfg_dir = "/root/reference/configs"
-    if not os.path.isdir(cfg_dir):
-        pytest.skip("reference tree not present")
-
-    def load(path):
-        d = yaml.safe_load(open(path))
-        parent = d.pop("parent", None)
-        base = load(os.path.join("/root/reference", parent)) if parent not in (None, "None", "") else {}
-        base.update(d)
-        return base
-    ref = load(os.path.join(cfg_dir, leaf))
+    reference's loader follows): every value the two have in common is equal, and
+    every name Mapping / Tracker / Renderer / IcpTracker read from `args` is in the argument set.  The reference's files,
+    merged along that chain, are tests/golden/reference_configs.json (oracle/gen_config_golden.py)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_configs.json")) as f:
+        ref = json.load(f)[leaf]
     mine = vars(getattr(mp, build)())
     common = sorted(set(ref) & set(mine))
     assert len(common) >= 45, common

@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
 if [ "${SKIP_TESTS:-0}" != "1" ]; then timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -6 > $O/pytest_gpu.txt; cat $O/pytest_gpu.txt; fi
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -2 $O/smoke.txt; python - <<'PY'
 import json
 d=json.load(open('/root/repo/gpurun_out/final/bench.json'))

@@ -11,9 +11,9 @@ cd $R
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -6 > $O/pytest_gpu.txt
 fi
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_bench -o bench -- python $R/bench.py --no-cpu-baseline --no-schedule --no-surface --prewarm 400 > $O/ks_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_bench -o bench -- python $R/bench.py --full --no-cpu-baseline --no-schedule --no-surface --prewarm 400 > $O/ks_bench.log 2>&1
 python $R/tools/unit_trace.py $(find $O/ks_bench -name "*kernel_trace.csv" | head -1) 150 200 > $O/unit_trace.txt 2>&1
 for w in headline surface; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_$w -o k -- python $R/tools/prof_raster.py $w 50 > $O/ks_$w.log 2>&1

@@ -16,7 +16,7 @@ for w in headline surface; do python $R/tools/pmc_summary.py $O/sq/pmc_sq_$w.csv
 cp $O/traffic_headline.json $R/profiles/traffic_latest.json; cp $O/valu.json $R/profiles/valu_latest.json
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*.db" -delete
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 d=json.load(open('/root/repo/gpurun_out/pmcf/bench.json'))
