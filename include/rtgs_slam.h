@@ -13,6 +13,8 @@
  *   frame preprocessing      tracker.py:97-159 -> SLAM/utils.py:65-139 (vertex / normal / confidence maps),
  *                            SLAM/utils.py:550-589 (bilateral filter), SLAM/utils.py:141-183 (sample_pixels' mask)
  *   rtgs_gather_rows3        the normal-map gather of Renderer.render, SLAM/render.py:130-133
+ *   rtgs_eval_*              SLAM/eval.py's picture metrics (utils/loss_utils.py psnr / l1_loss, pytorch_msssim.ms_ssim)
+ *                            and the nearest-neighbour reduction of eval_pcd (scipy cKDTree queries: rtgs_knn3_query_built)
  */
 #ifndef RTGS_SLAM_H
 #define RTGS_SLAM_H
@@ -198,6 +200,45 @@ int rtgs_transform_map(const float* map3, int64_t n, const float* transform16, f
  * g[:, p] (accumulates; caller zeroes). */
 int rtgs_gather_rows3(const float* rows, const int32_t* index, int32_t n, float* out, void* stream);
 int rtgs_scatter_rows3(const float* g, const int32_t* index, int32_t n, float* grad_rows, void* stream);
+
+/* ---- evaluation (SLAM/eval.py: eval_picture :38-147, eval_pcd :149-223) -------------------------------------------
+ * Bitwise reproducible run to run: per-workgroup partials in scratch, reduced in a fixed order in float64; no float atomics.
+ *
+ * rtgs_eval_picture: render / gt_color [3,H,W], depth [1,H,W], gt_depth [H,W] (metres), depth_index [1,H,W] int32 (-1 = no
+ * Gaussian).  Writes out[RTGS_EVAL_PICTURE_OUT] float64 on the device:
+ *   psnr       mean over R, G, B of 20 log10(1 / sqrt(mse_c)), mse_c = mean over the H W pixels (mse_c = 0 -> +inf);
+ *   color_l1   mean |gt - render| over the 3 H W values;
+ *   depth      gt depth outside the OPEN interval (min_depth, max_depth) counts as 0; a pixel is valid iff depth_index != -1
+ *              and gt != 0; valid_ratio = valid / (H W), depth_l1 = mean |depth - gt| over the valid pixels (NaN if none);
+ *   ms_ssim    pytorch_msssim.ms_ssim(data_range 1) when with_ms_ssim != 0, else NaN: 11-tap Gaussian (sigma 1.5), VALID,
+ *              C1 = 0.01^2, C2 = 0.03^2, 5 levels, weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), relu(mean cs) on levels
+ *              0-3 and relu(mean ssim) on level 4, product of powers per channel, mean over channels; 2 x 2 average pooling
+ *              between levels with a leading zero on odd axes and divisor 4.  Needs min(H, W) > RTGS_EVAL_MS_SSIM_MIN_SIDE
+ *              (-1 otherwise).  Per-level means of cs / ssim per channel are in the vector too.
+ * scratch: rtgs_eval_picture_scratch_bytes(H, W) bytes.
+ *
+ * rtgs_eval_nn_stats: column 0 (the nearest neighbour) of dist2 [N,3] float32 as rtgs_knn3_query_built leaves it; k <=
+ * RTGS_EVAL_MAX_THRESHOLDS thresholds (device float64).  out[0] = sum of sqrt(d2) in float64, out[1 + j] = number of points
+ * with sqrt(d2) < thresholds[j].  scratch: rtgs_eval_nn_stats_scratch_bytes(N, k) bytes. */
+#define RTGS_EVAL_MS_SSIM_MIN_SIDE 160
+#define RTGS_EVAL_MAX_THRESHOLDS 16
+#define RTGS_EVAL_OUT_PSNR 0
+#define RTGS_EVAL_OUT_COLOR_L1 1
+#define RTGS_EVAL_OUT_DEPTH_L1 2
+#define RTGS_EVAL_OUT_VALID_RATIO 3
+#define RTGS_EVAL_OUT_MS_SSIM 4
+#define RTGS_EVAL_OUT_VALID_COUNT 5
+#define RTGS_EVAL_OUT_MSE 6                 /* 3 values, R G B */
+#define RTGS_EVAL_OUT_CS 9                  /* 15 values, [level][channel] */
+#define RTGS_EVAL_OUT_SSIM 24               /* 15 values, [level][channel] */
+#define RTGS_EVAL_PICTURE_OUT 39              /* every slot is written */
+size_t rtgs_eval_picture_scratch_bytes(int32_t H, int32_t W);
+int rtgs_eval_picture(const float* render, const float* gt_color, const float* depth, const float* gt_depth,
+                      const int32_t* depth_index, int32_t H, int32_t W, float min_depth, float max_depth, int32_t with_ms_ssim,
+                      void* scratch, double* out, void* stream);
+size_t rtgs_eval_nn_stats_scratch_bytes(int32_t N, int32_t k);
+int rtgs_eval_nn_stats(const float* dist2, int32_t N, const double* thresholds, int32_t k, void* scratch, double* out,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,11 @@ _SIGNATURES = {
     "rtgs_transform_map": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "rtgs_gather_rows3": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "rtgs_scatter_rows3": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    # evaluation
+    "rtgs_eval_picture_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtgs_eval_picture": (C.c_int, [_P] * 5 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _P, _P, _P]),
+    "rtgs_eval_nn_stats_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtgs_eval_nn_stats": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,0 +1,210 @@
+"""Map-quality evaluation of the reference (SLAM/eval.py, metric.py) on the HIP kernels of include/rtgs_slam.h, "evaluation":
+
+    eval_picture       SLAM/eval.py:38-147    PSNR (mean of the per-channel PSNR, utils/loss_utils.py:23-25), MS-SSIM
+                                              (pytorch_msssim.ms_ssim, data_range 1), colour L1, depth L1, valid-pixel ratio;
+                                              LPIPS is not computed (no pretrained AlexNet weights): None
+    eval_pcd           SLAM/eval.py:149-223   accuracy / completion (cm), precision / recall (%) and F1 per threshold, from
+                                              the exact 3-NN search (rtgs_knn3_build_ref / _query_built, column 0) and one
+                                              reduction kernel per direction
+    eval_frame         SLAM/eval.py:225-270   render the map at a frame (under no_grad), then the two above
+    evaluate_sequence  metric.py:137-219      every frame of a finished run with the evaluation renderer, the reconstruction
+                                              once, per-frame rows and the mean row
+
+Each metric call reads its float64 result vector from the device once; that read is its only synchronisation.  The results
+are bitwise reproducible run to run (fixed-order reductions, no float atomics).  There is no CPU path."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from types import SimpleNamespace
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .io_formats import metrics_mean_row
+
+# layout of rtgs_eval_picture's result vector (include/rtgs_slam.h)
+OUT_PSNR, OUT_COLOR_L1, OUT_DEPTH_L1, OUT_VALID_RATIO, OUT_MS_SSIM, OUT_VALID_COUNT = 0, 1, 2, 3, 4, 5
+OUT_MSE, OUT_CS, OUT_SSIM = 6, 9, 24            # [3], [5 levels][3 channels], [5][3]
+PICTURE_OUT = 39
+MS_SSIM_MIN_SIDE = 160                          # pytorch_msssim asserts the smaller side is > 160
+MAX_THRESHOLDS = 16
+
+
+def _dev(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("rtg_slam_amd.evaluation: tensors must live on a HIP device; this build has no CPU path.")
+    return ts[0].device
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def picture_metrics(render: torch.Tensor, gt_color: torch.Tensor, depth: torch.Tensor, gt_depth: torch.Tensor,
+                    depth_index: torch.Tensor, min_depth: float, max_depth: float, with_ms_ssim: bool = True) -> torch.Tensor:
+    """rtgs_eval_picture -> its float64 result vector [PICTURE_OUT], left on the device (no synchronisation).  render /
+    gt_color [3,H,W]; depth, gt_depth, depth_index: H*W values each ([1,H,W], [H,W] or [H,W,1])."""
+    H, W = int(render.shape[-2]), int(render.shape[-1])
+    if with_ms_ssim and min(H, W) <= MS_SSIM_MIN_SIDE:
+        raise ValueError(f"rtg_slam_amd.evaluation: MS-SSIM needs the smaller image side > {MS_SSIM_MIN_SIDE}, got {H}x{W}")
+    for name, t, n in (("render", render, 3 * H * W), ("gt_color", gt_color, 3 * H * W), ("depth", depth, H * W),
+                       ("gt_depth", gt_depth, H * W), ("depth_index", depth_index, H * W)):
+        if t.numel() != n:
+            raise ValueError(f"rtg_slam_amd.evaluation: {name} has {t.numel()} values, expected {n} for a {H}x{W} image")
+    dev = _dev(render, gt_color, depth, gt_depth, depth_index)
+    lib = _lib.load()
+    r, g = render.detach().float().contiguous(), gt_color.detach().float().contiguous()
+    d, gd = depth.detach().float().contiguous(), gt_depth.detach().float().contiguous()
+    idx = depth_index.detach().to(torch.int32).contiguous()
+    scratch = torch.empty(lib.rtgs_eval_picture_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
+    out = torch.empty(PICTURE_OUT, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_eval_picture(_p(r), _p(g), _p(d), _p(gd), _p(idx), H, W, float(min_depth), float(max_depth),
+                                   int(bool(with_ms_ssim)), _p(scratch), _p(out), _stream(dev))
+    _lib.check(rc, "rtgs_eval_picture")
+    return out
+
+
+def eval_picture(render_output: Dict[str, torch.Tensor], gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: float,
+                 max_depth: float, with_ms_ssim: bool = True) -> Dict:
+    """SLAM/eval.py:38-147 on a `Renderer.render` result: gt_color [3,H,W] in 0..1, gt_depth in metres (the reference's
+    255 * original_depth).  Keys as the reference's `losses`, plus color_l1 (its l1_loss of the colour, logged there)."""
+    v = picture_metrics(render_output["render"], gt_color, render_output["depth"], gt_depth, render_output["depth_index_map"],
+                        min_depth, max_depth, with_ms_ssim).cpu().tolist()
+    return {
+        "valid_pixel_ratio": v[OUT_VALID_RATIO],
+        "depth_loss": v[OUT_DEPTH_L1],
+        "normal_loss": 0,                                             # eval.py:135: torch.tensor(0)
+        "psnr": v[OUT_PSNR],
+        "ssim": v[OUT_MS_SSIM] if with_ms_ssim else None,
+        "lpips": None,                                                # needs pretrained AlexNet weights: not computed
+        "color_l1": v[OUT_COLOR_L1],
+    }
+
+
+def nn_stats(dist2: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
+    """rtgs_eval_nn_stats over column 0 of dist2 [N,3] -> float64 [1 + k] on the device: sum of the distances, then the
+    number of distances below each threshold (float64 [k] on the device)."""
+    dev = _dev(dist2, thresholds)
+    lib = _lib.load()
+    d = dist2.detach().float().contiguous()
+    N, k = int(d.shape[0]), int(thresholds.numel())
+    if d.dim() != 2 or d.shape[1] != 3 or N == 0 or k > MAX_THRESHOLDS:
+        raise ValueError(f"rtg_slam_amd.evaluation: dist2 must be [N >= 1, 3] and k <= {MAX_THRESHOLDS}")
+    thr = thresholds.to(torch.float64).contiguous()
+    scratch = torch.empty(lib.rtgs_eval_nn_stats_scratch_bytes(N, k), dtype=torch.uint8, device=dev)
+    out = torch.empty(1 + k, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_eval_nn_stats(_p(d), N, _p(thr), k, _p(scratch), _p(out), _stream(dev))
+    _lib.check(rc, "rtgs_eval_nn_stats")
+    return out
+
+
+def subsample(points: torch.Tensor, sample_nums: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """Rows drawn without replacement down to sample_nums (eval.py:164-165's np.random.choice), or all of them."""
+    P = int(points.shape[0])
+    if P <= sample_nums:
+        return points
+    pick = torch.randperm(P, generator=generator)[:int(sample_nums)]
+    return points[pick.to(points.device)]
+
+
+def eval_pcd(rec_points, gt_points, dist_thres: Sequence[float] = (0.03,), transform=None, sample_nums: int = 1_000_000,
+             generator: Optional[torch.Generator] = None) -> Dict[str, float]:
+    """SLAM/eval.py:149-223 on point sets: rec_points [P,3] (the map's Gaussian centres) on the device, gt_points [M,3]
+    (sampled from the GT mesh: io_formats.sample_mesh_surface) as a tensor or array.  `transform` (4x4) moves the
+    reconstruction first; it is then subsampled without replacement to sample_nums.  accuracy = mean distance of the
+    reconstruction to GT, completion = of GT to the reconstruction, both in cm; P / R = percentage below each threshold;
+    F1 = 2PR / (P + R), NaN when P + R = 0."""
+    from . import slam_ops as so
+    dev = _dev(rec_points)
+    rec = rec_points.detach().float().reshape(-1, 3)
+    gt = torch.as_tensor(gt_points).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    if rec.shape[0] == 0 or gt.shape[0] == 0:
+        raise ValueError("rtg_slam_amd.evaluation: eval_pcd needs non-empty point sets")
+    thres = [float(t) for t in dist_thres]
+    if len(thres) > MAX_THRESHOLDS:
+        raise ValueError(f"rtg_slam_amd.evaluation: at most {MAX_THRESHOLDS} thresholds")
+    rec = subsample(rec, sample_nums, generator)
+    if transform is not None:
+        rec = so.transform_map(rec.contiguous(), torch.as_tensor(np.asarray(transform, dtype=np.float32)))
+    rec = rec.contiguous()
+    Nr, Ng = int(rec.shape[0]), int(gt.shape[0])
+    thr = torch.tensor(thres, dtype=torch.float64, device=dev)
+    d_acc, _ = so.knn_query_built(so.knn_build_ref(gt), Ng, rec)        # reconstruction -> GT: accuracy, precision
+    d_comp, _ = so.knn_query_built(so.knn_build_ref(rec), Nr, gt)       # GT -> reconstruction: completion, recall
+    v = torch.cat([nn_stats(d_acc, thr), nn_stats(d_comp, thr)]).cpu().tolist()
+    k = len(thres)
+    acc, comp = v[:1 + k], v[1 + k:]
+    res = {"accuracy": acc[0] / Nr * 100.0, "completion": comp[0] / Ng * 100.0}
+    Ps = {f"P (< {t})": acc[1 + j] / Nr * 100.0 for j, t in enumerate(thres)}
+    Rs = {f"R (< {t})": comp[1 + j] / Ng * 100.0 for j, t in enumerate(thres)}
+    Fs = {}
+    for t in thres:
+        P, R = Ps[f"P (< {t})"], Rs[f"R (< {t})"]
+        Fs[f"F1 (< {t})"] = 2 * P * R / (P + R) if P + R > 0 else math.nan
+    res.update(Ps)
+    res.update(Rs)
+    res.update(Fs)
+    return res
+
+
+def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: Optional[float] = None,
+               max_depth: Optional[float] = None, renderer=None, run_picture: bool = True, run_pcd: bool = False,
+               gt_points=None, dist_thres: Sequence[float] = (0.03,), sample_nums: int = 1_000_000, transform=None,
+               generator: Optional[torch.Generator] = None, with_ms_ssim: bool = True) -> Dict:
+    """SLAM/eval.py:225-270: the map (mapper.global_params) rendered at `frame` under no_grad, then eval_picture; eval_pcd
+    on the map's Gaussian centres when run_pcd and gt_points are given.  renderer=None renders with the mapper's own
+    renderer, as slam.py does, through Mapping._render: a full render of the same frame, pose and map made just before
+    (get_render_output) is reused, not redone."""
+    a = mapper.args
+    min_depth = a.min_depth if min_depth is None else min_depth
+    max_depth = a.max_depth if max_depth is None else max_depth
+    losses: Dict = {}
+    with torch.no_grad():
+        if run_picture:
+            out = mapper._render(frame, "all") if renderer is None else renderer.render(frame, mapper.global_params)
+            losses.update(eval_picture(out, gt_color, gt_depth, min_depth, max_depth, with_ms_ssim))
+        if run_pcd and gt_points is not None:
+            losses.update(eval_pcd(mapper.opt.gaussian_data("all")["xyz"], gt_points, dist_thres, transform, sample_nums,
+                                   generator))
+    return losses
+
+
+def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_points=None, dist_thres: Sequence[float] = (0.03,),
+                      transform=None, sample_nums: int = 1_000_000, generator: Optional[torch.Generator] = None,
+                      with_ms_ssim: bool = True) -> Dict:
+    """metric.py:137-219 over a finished map.  `stream` yields (depth [H,W] metres, colour [3,H,W], GT c2w) as run_sequence's
+    does; frame i is rendered at poses[i] (the estimated trajectory, e.g. tracker.pose_es) or, without poses, at its GT pose,
+    by a Renderer whose opaque threshold is args.renderer_opaque_threshold_eval (metric.py:138).  With gt_points, the
+    reconstruction metrics of the map's Gaussian centres join the last frame's row, as metric.py runs them there.
+    Returns {"rows": one dict per frame (with "frame" and "iter"), "mean": the mean row of metric.py:205-211}."""
+    from .mapping import Frame
+    from .render import Renderer
+    args = mapper.args if args is None else args
+    eval_args = SimpleNamespace(**vars(args))
+    eval_args.renderer_opaque_threshold = float(getattr(args, "renderer_opaque_threshold_eval", 0.5))
+    renderer = Renderer(eval_args)
+    rows: List[Dict] = []
+    for i, (depth, color, gt_c2w) in enumerate(stream):
+        frame = Frame(cam, gt_c2w, mapper.device, uid=i)
+        if poses is not None:
+            frame.updatePose(np.asarray(poses[i], dtype=np.float64))         # metric.py:175-176
+        row = eval_frame(mapper, frame, color, depth, args.min_depth, args.max_depth, renderer=renderer,
+                         with_ms_ssim=with_ms_ssim)
+        row["frame"] = i
+        row["iter"] = int(getattr(mapper, "iter", 0))
+        rows.append(row)
+    if gt_points is not None and rows:
+        with torch.no_grad():
+            rows[-1].update(eval_pcd(mapper.opt.gaussian_data("all")["xyz"], gt_points, dist_thres, transform, sample_nums,
+                                     generator))
+    return {"rows": rows, "mean": metrics_mean_row(rows)}

@@ -7,15 +7,20 @@
     SLAM/gaussian_pointcloud.py:407-466 (writer), :118-193 (reader), SLAM/utils.py:321-392 (merge);
   * trajectories     `save_traj/pose_es.npy`, `pose_gt.npy` - float [n,4,4] camera-to-world: tracker.py:352-362;
   * `performance.json` - {"tracking", "mapping": mean seconds per frame, "fps": 1 / mapping, "gpu_memory": MB}:
-    utils/monitor.py:22-50.
+    utils/monitor.py:22-50;
+  * ground-truth meshes (PLY, ascii or binary little-endian; triangles and quads) and the surface sampling eval_pcd
+    applies to them (trimesh.load / trimesh.sample.sample_surface, SLAM/eval.py:155-170), and the per-frame metrics
+    table `statis_frame_*_iter_*.csv` with its mean row (metric.py:203-219, written there by pandas).
 
 The packed [N,59] layout of rtg_slam_amd.map_optim (xyz | f_dc | f_rest coefficient-major | opacity | scaling |
 rotation) converts to and from the file's columns here."""
 from __future__ import annotations
 
+import csv
 import json
+import math
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -179,3 +184,210 @@ class Recorder:
         os.makedirs(directory, exist_ok=True)
         with open(os.path.join(directory, "performance.json"), "w") as f:
             json.dump(self._value, f)
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _ply_header(f, path):
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []                    # elements: [name, count, [(prop, type) | (prop, (count_type, item_type))]]
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError(f"{path}: truncated header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "end_header":
+            break
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], (_PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]])))
+            else:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii, binary_little_endian)")
+    return fmt, elements
+
+
+def _ply_binary_element(buf, pos, count, props):
+    """One element's rows from a binary little-endian body -> ({prop: array or list of arrays}, new position)."""
+    lists = [i for i, (_, t) in enumerate(props) if isinstance(t, tuple)]
+    if not lists:
+        dt = np.dtype([(n, "<" + t) for n, t in props])
+        rows = np.frombuffer(buf, dtype=dt, count=count, offset=pos)
+        return {n: rows[n] for n, _ in props}, pos + count * dt.itemsize
+    if count == 0:
+        return {n: np.zeros(0) for n, _ in props}, pos
+    # fast path: every list of the element has the length its first row has (all triangles, or all quads)
+    lens, p = [], pos
+    for n, t in props:
+        if isinstance(t, tuple):
+            k = int(np.frombuffer(buf, dtype="<" + t[0], count=1, offset=p)[0])
+            lens.append(k)
+            p += np.dtype(t[0]).itemsize + k * np.dtype(t[1]).itemsize
+        else:
+            p += np.dtype(t).itemsize
+    fields, li = [], 0
+    for n, t in props:
+        if isinstance(t, tuple):
+            fields += [(n + "#n", "<" + t[0]), (n, "<" + t[1], (lens[li],))]
+            li += 1
+        else:
+            fields.append((n, "<" + t))
+    dt = np.dtype(fields)
+    if pos + count * dt.itemsize <= len(buf):
+        rows = np.frombuffer(buf, dtype=dt, count=count, offset=pos)
+        li = 0
+        ok = True
+        for n, t in props:
+            if isinstance(t, tuple):
+                ok = ok and bool((rows[n + "#n"] == lens[li]).all())
+                li += 1
+        if ok:
+            return {n: rows[n] for n, _ in props}, pos + count * dt.itemsize
+    # mixed list lengths: row by row
+    out = {n: [] for n, _ in props}
+    for _ in range(count):
+        for n, t in props:
+            if isinstance(t, tuple):
+                k = int(np.frombuffer(buf, dtype="<" + t[0], count=1, offset=pos)[0])
+                pos += np.dtype(t[0]).itemsize
+                out[n].append(np.frombuffer(buf, dtype="<" + t[1], count=k, offset=pos))
+                pos += k * np.dtype(t[1]).itemsize
+            else:
+                out[n].append(np.frombuffer(buf, dtype="<" + t, count=1, offset=pos)[0])
+                pos += np.dtype(t).itemsize
+    return out, pos
+
+
+def _ply_ascii_element(tokens, pos, count, props):
+    if not any(isinstance(t, tuple) for _, t in props):
+        m = len(props)
+        block = np.asarray(tokens[pos:pos + count * m], dtype=np.float64).reshape(count, m)
+        return {n: block[:, i] for i, (n, _) in enumerate(props)}, pos + count * m
+    out = {n: [] for n, _ in props}
+    for _ in range(count):
+        for n, t in props:
+            if isinstance(t, tuple):
+                k = int(tokens[pos])
+                out[n].append(np.asarray(tokens[pos + 1:pos + 1 + k], dtype=np.int64))
+                pos += 1 + k
+            else:
+                out[n].append(float(tokens[pos]))
+                pos += 1
+    return out, pos
+
+
+def _triangulate(polys) -> np.ndarray:
+    """Face index lists -> [F,3] int64 triangles; a polygon (a, b, c, d, ...) becomes the fan (a,b,c), (a,c,d), ..."""
+    if isinstance(polys, np.ndarray) and polys.ndim == 2:
+        k = polys.shape[1]
+        if k < 3:
+            raise ValueError("PLY face with fewer than 3 vertices")
+        fan = [np.stack([polys[:, 0], polys[:, j], polys[:, j + 1]], axis=1) for j in range(1, k - 1)]
+        return np.stack(fan, axis=1).reshape(-1, 3).astype(np.int64)
+    tris = []
+    for p in polys:
+        p = np.asarray(p, dtype=np.int64)
+        if p.shape[0] < 3:
+            raise ValueError("PLY face with fewer than 3 vertices")
+        tris += [(p[0], p[j], p[j + 1]) for j in range(1, p.shape[0] - 1)]
+    return np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+
+
+def load_mesh_ply(path: str):
+    """A triangle mesh from a PLY file, ascii or binary little-endian (what trimesh.load reads for eval_pcd's GT mesh,
+    SLAM/eval.py:155): -> (vertices float64 [V,3], faces int64 [F,3]).  Faces are lists of 3 or more vertex indices;
+    quads (and larger polygons) are split into triangles (a,b,c), (a,c,d).  Other elements are skipped."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        body = f.read()
+    verts, faces = None, np.zeros((0, 3), np.int64)
+    if fmt == "ascii":
+        tokens, pos = body.decode("ascii").split(), 0
+        read = lambda count, props, pos: _ply_ascii_element(tokens, pos, count, props)
+    else:
+        pos = 0
+        read = lambda count, props, pos: _ply_binary_element(body, pos, count, props)
+    for name, count, props in elements:
+        cols, pos = read(count, props, pos)
+        if name == "vertex":
+            verts = np.stack([np.asarray(cols[k], dtype=np.float64) for k in ("x", "y", "z")], axis=1)
+        elif name == "face":
+            key = next((n for n, t in props if isinstance(t, tuple) and n in ("vertex_indices", "vertex_index")), None)
+            if key is None:
+                raise ValueError(f"{path}: face element without vertex_indices")
+            faces = _triangulate(cols[key])
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    return verts, faces
+
+
+def sample_mesh_surface(vertices, faces, n: int, seed: int = 0):
+    """n points uniformly on the surface (trimesh.sample.sample_surface, which eval_pcd applies to the GT mesh): a face with
+    probability proportional to its area, then a uniform point of it (barycentric u, v in the unit square, folded into the
+    triangle).  -> (points float64 [n,3], face index int64 [n])."""
+    v = np.asarray(vertices, dtype=np.float64)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    area = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+    if f.shape[0] == 0 or not area.sum() > 0:
+        raise ValueError("sample_mesh_surface: the mesh has no area")
+    rng = np.random.default_rng(seed)
+    cum = np.cumsum(area)
+    face = np.minimum(np.searchsorted(cum, rng.random(n) * cum[-1], side="right"), f.shape[0] - 1).astype(np.int64)
+    uv = rng.random((n, 2))
+    flip = uv.sum(axis=1) > 1.0
+    uv[flip] = 1.0 - uv[flip]
+    pts = a[face] + uv[:, :1] * (b[face] - a[face]) + uv[:, 1:] * (c[face] - a[face])
+    return pts, face
+
+
+def _is_number(x) -> bool:
+    return isinstance(x, (int, float, np.integer, np.floating)) and not (isinstance(x, (float, np.floating)) and math.isnan(x))
+
+
+def metrics_mean_row(rows: Sequence[Dict]) -> Dict:
+    """metric.py:205-209's mean row: per column (in order of first appearance) the mean of its numeric values, NaN and
+    missing cells skipped as pandas does; a column without numbers stays None; `frame` = "mean"."""
+    cols: List[str] = []
+    for r in rows:
+        cols += [k for k in r if k not in cols]
+    mean = {}
+    for k in cols:
+        vals = [float(r[k]) for r in rows if k in r and _is_number(r[k])]
+        mean[k] = sum(vals) / len(vals) if vals else None
+    mean["frame"] = "mean"
+    return mean
+
+
+def save_metrics_csv(path: str, rows: Sequence[Dict]) -> None:
+    """metric.py:203-219 without pandas: one line per frame, then the mean row; the first column is the row index, as
+    DataFrame.to_csv writes it.  NaN and None are empty cells."""
+    rows = list(rows)
+    table = rows + [metrics_mean_row(rows)]
+    cols: List[str] = []
+    for r in table:
+        cols += [k for k in r if k not in cols]
+
+    def cell(x):
+        if x is None or (isinstance(x, (float, np.floating)) and math.isnan(x)):
+            return ""
+        if isinstance(x, (float, np.floating)):
+            return repr(float(x))
+        return str(x)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow([""] + cols)
+        for i, r in enumerate(table):
+            w.writerow([str(i)] + [cell(r.get(k)) for k in cols])

@@ -66,6 +66,8 @@ def replica_args(**over) -> SimpleNamespace:
         # render params (:64-70)
         renderer_opaque_threshold=0.6, renderer_normal_threshold=60.0, renderer_depth_threshold=1.0, color_sigma=3.0,
         global_opt_top_ratio=0.4,
+        # evaluation (base.yaml:20, 122; metric.py:138 renders with renderer_opaque_threshold_eval)
+        save_step=2000, renderer_opaque_threshold_eval=0.5,
         # optimize params (:73-91; replica_base.yaml:16-24, 38-40)
         gaussian_update_iter=50, gaussian_update_frame=6, final_global_iter=20, color_weight=0.8, depth_weight=1.0,
         ssim_weight=0.2, normal_weight=0.0, position_lr=0.001, feature_lr=0.0005, opacity_lr=0.0, scaling_lr=0.004,

@@ -87,13 +87,21 @@ def ate_rmse(pose_es, pose_gt, align: bool = False) -> float:
 
 
 def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] = None, lr_scale: float = 1.0,
-                 capacity: Optional[int] = None, on_frame: Optional[Callable] = None, final_global: bool = False):
+                 capacity: Optional[int] = None, on_frame: Optional[Callable] = None, final_global: bool = False,
+                 eval_every: Optional[int] = None):
     """slam.py:56-95 over `stream` = iterable of (depth [H,W] metres, colour [3,H,W] in 0..1, ground-truth c2w 4x4) on the
     device.  Returns (mapper, tracker, report): report["fps"] is the reference's definition, 1 / mean(mapping seconds per
-    frame) (utils/monitor.py:22-24), next to the frame rate of the whole loop (tracking + mapping, sequential)."""
+    frame) (utils/monitor.py:22-24), next to the frame rate of the whole loop (tracking + mapping, sequential).
+
+    eval_every (the reference's save_step, slam.py:98-110, 130-138): evaluate the map (rtg_slam_amd.evaluation.eval_frame)
+    at mapper.time 0 and whenever (time + 1) % eval_every == 0, after the frame's mapping clock stops and on the full render
+    get_render_output just made; with final_global, once more after the final global optimisation on the last keyframe and
+    its raw colour / depth.  The rows are report["eval"].  None (default): no evaluation, the report as without it."""
+    from . import evaluation
     mapper = mapper if mapper is not None else Mapping(args, device, capacity=capacity, lr_scale=lr_scale)
     tracker = Tracker(args, device)
     t_track, t_map, per_frame = 0.0, 0.0, []
+    evals, last_kf = [], None
     n = 0
     torch.cuda.synchronize(device)
     t_all = time.perf_counter()
@@ -114,6 +122,13 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         t_track += t1 - t0
         t_map += t2 - t1
         per_frame.append((t1 - t0, t2 - t1, mapper.opt.N, mapper.opt.n_frozen))
+        if eval_every:
+            if mapper.keyframe_list and mapper.keyframe_list[-1] is frame:     # keymap_list keeps the preprocessed depth only
+                last_kf = (frame, frame_id, depth.clone(), color.clone())
+            if mapper.time == 0 or (mapper.time + 1) % int(eval_every) == 0:
+                row = evaluation.eval_frame(mapper, frame, color, depth)
+                row.update(frame=mapper.time, final=False)
+                evals.append(row)
         if on_frame is not None:
             on_frame(frame_id, frame, frame_map, mapper, tracker)
         mapper.time += 1
@@ -121,6 +136,11 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
     if final_global and n > 0:
         mapper.global_optimization(select_keyframe_num=-1, is_end=True)
         torch.cuda.synchronize(device)
+        if eval_every and last_kf is not None:
+            kf, kf_id, kf_depth, kf_color = last_kf
+            row = evaluation.eval_frame(mapper, kf, kf_color, kf_depth)
+            row.update(frame=kf_id, final=True)
+            evals.append(row)
     wall = time.perf_counter() - t_all
     es, gt = tracker.pose_es, tracker.pose_gt
     report = {
@@ -137,4 +157,6 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         "per_frame": per_frame,
         "stage_profile_ms_per_frame": None if mapper.prof is None else {k: round(1e3 * v / max(n, 1), 3) for k, v in mapper.prof.items()},
     }
+    if eval_every:
+        report["eval"] = evals
     return mapper, tracker, report
