@@ -83,6 +83,14 @@ void rtgs_raster_set_bwd_stamps(void* dev);
 /* The same for blend_fwd (tools/fwd_stamps.py): `dev` = device uint64[tiles x 4 waves x 8]: wall clock at entry / exit, cycles until
  * the tile range is there | until the first batch is staged | inside the walk loops | in the kernel, walk steps, batches. */
 void rtgs_raster_set_fwd_stamps(void* dev);
+/* The same for the tracker's residual launches (tools/icp_stamps.py): `dev` = device uint64[RTGS_ICP_STAMP_LAUNCHES x
+ * RTGS_ICP_STAMP_WGS workgroups x 4 waves x 8] or NULL.  Residual launch k after the call (rtgs_icp_track, rtgs_icp_step) takes
+ * slot k % RTGS_ICP_STAMP_LAUNCHES and runs the stamped twin of the kernel.  Per wave: wall clock (100 MHz) at entry and exit,
+ * shader cycles of the source loads | gathers | projection, gates and sums | partial publish + ticket | last arriver's
+ * partial reads + float64 sum | its solve.  PROCESS-WIDE; each call restarts at slot 0. */
+#define RTGS_ICP_STAMP_LAUNCHES 16
+#define RTGS_ICP_STAMP_WGS 256
+void rtgs_icp_set_stamps(void* dev);
 
 #ifdef __cplusplus
 }

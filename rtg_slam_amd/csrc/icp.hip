@@ -5,6 +5,7 @@
 // device.  Compiled with -ffp-contract=off so the float32 op sequence of the gating
 // arithmetic (projection, nearest-neighbour association, thresholds) follows the reference's.
 #include "../../include/rtgs_icp.h"
+#include "../../include/rtgs_debug.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -13,11 +14,12 @@ namespace rtgs_icp {
 
 // Residual workgroups per launch, at most.  One per CU measured best at 1200x680, alone and beside the mapper (track alone /
 // unit, us: 64: 457 / 556, 128: 317 / 445, 192: 281 / 437, 256: 263 / 420, 384: 270 / 427, 512: 283 / 431): fewer tickets and
-// partial rows for the last arriver, and - the kernel needs 151 VGPRs - fewer wave slots to find beside the mapper's.
+// partial rows for the last arriver, and - the kernel needs ~150 VGPRs - fewer wave slots to find beside the mapper's.
 #ifndef RTGS_ICP_MAX_BLOCKS
 #define RTGS_ICP_MAX_BLOCKS 256
 #endif
 constexpr int MAX_BLOCKS = RTGS_ICP_MAX_BLOCKS;
+static_assert(MAX_BLOCKS <= RTGS_ICP_STAMP_WGS, "stamp slots hold RTGS_ICP_STAMP_WGS workgroups");
 constexpr int NACC = 28;            // 21 upper-triangular JtJ + 6 Jtr + 1 valid count
 constexpr int PSTRIDE = 32;         // floats per block partial
 
@@ -267,16 +269,18 @@ __device__ __forceinline__ float wave_sum63(float v) {
   return v;
 }
 
-__device__ __forceinline__ void block_write_partials(float (&acc)[NACC], float* __restrict__ partials) {
+// The workgroup's sums of the first NCOL columns -> its partial row.
+template <int NCOL>
+__device__ __forceinline__ void block_write_partials(float (&acc)[NCOL], float* __restrict__ partials) {
   __shared__ float s_part[4 * PSTRIDE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < NACC; ++k) {
+  for (int k = 0; k < NCOL; ++k) {
     const float r = wave_sum63(acc[k]);
     if (lane == 63) s_part[wave * PSTRIDE + k] = r;
   }
   __syncthreads();
-  if (threadIdx.x < NACC) {
+  if (threadIdx.x < NCOL) {
     const int k = threadIdx.x;
     // write-through (sc1) store: visible to the electing workgroup without an L2 write-back fence
     __hip_atomic_store(&partials[(size_t)blockIdx.x * PSTRIDE + k],
@@ -364,8 +368,9 @@ __device__ __forceinline__ void sum_partials(const float* __restrict__ partials,
 
 // One Gauss-Newton update from the 28 sums, by ONE thread: lev_mar_H damping (icp.py:248-256), xi = -H^-1 J^T r
 // through a register-resident Cholesky (icp.py:328-334 inverts H on the CPU), pose <- exp(xi) @ pose (icp.py:271-310,
-// :259-268).  Returns false (pose untouched) when the damped H is not positive definite.
-__device__ __forceinline__ bool gn_update(const double (&S)[NACC], float damping, float* pose) {
+// :259-268).  Returns false (pose untouched) when the damped H is not positive definite.  `pin` is the pose before the
+// step (read by the caller ahead of time: no memory round trip inside the serial chain), `pose` receives the result.
+__device__ __forceinline__ bool gn_update(const double (&S)[NACC], float damping, const float (&pin)[16], float* pose) {
   double Hm[6][6], bvec[6];
 #pragma unroll
   for (int r = 0; r < 6; ++r)
@@ -457,7 +462,7 @@ __device__ __forceinline__ bool gn_update(const double (&S)[NACC], float damping
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) Pm[r][c] = (double)pose[r * 4 + c];
+    for (int c = 0; c < 4; ++c) Pm[r][c] = (double)pin[r * 4 + c];
   // pose <- exp(xi) @ pose (bottom row stays 0 0 0 1)
 #pragma unroll
   for (int r = 0; r < 3; ++r)
@@ -477,7 +482,7 @@ __device__ __forceinline__ bool gn_update(const double (&S)[NACC], float damping
 // float64 sums and the float32 solve the reference's own code reproduces its float32 answer to 2e-9).  What this
 // cannot reproduce is the blocked / vectorised order INSIDE the library calls (sgetri's triangular solves, the 8-lane
 // horizontal sum behind torch.sum): differences of one float32 rounding remain.  Measured: tests/test_icp_gpu.py.
-__device__ __forceinline__ bool gn_update_f32(const double (&S)[NACC], float damping, float* pose) {
+__device__ __forceinline__ bool gn_update_f32(const double (&S)[NACC], float damping, const float (&pin)[16], float* pose) {
   float A[6][6], b[6];
 #pragma unroll
   for (int r = 0; r < 6; ++r)
@@ -569,7 +574,7 @@ __device__ __forceinline__ bool gn_update_f32(const double (&S)[NACC], float dam
   float tv[3];
   for (int r = 0; r < 3; ++r) tv[r] = __fadd_rn(__fadd_rn(__fmul_rn(Jl[r][0], xi[3]), __fmul_rn(Jl[r][1], xi[4])), __fmul_rn(Jl[r][2], xi[5]));
   float Pm[4][4];
-  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Pm[r][c] = pose[r * 4 + c];
+  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Pm[r][c] = pin[r * 4 + c];
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 4; ++c) {
       float o = __fmul_rn(E[r][0], Pm[0][c]);
@@ -581,12 +586,8 @@ __device__ __forceinline__ bool gn_update_f32(const double (&S)[NACC], float dam
   return true;
 }
 
-// Executed by ONE whole workgroup (256 threads): the last one to arrive in the residual kernel.
-__device__ __forceinline__ void final_stage(const float* __restrict__ partials, int nblocks, const FinalArgs& fa) {
-  __shared__ double s_sum[32 * PSTRIDE];
-  __shared__ double s_tot[PSTRIDE];
-  sum_partials(partials, nblocks, s_sum, s_tot);
-  if (threadIdx.x != 0) return;
+// Thread 0 of the last arriver: the 28 totals in s_tot -> the launch's output (solve + pose update, equations, or loss).
+__device__ __forceinline__ void final_solve_from(const double* s_tot, const FinalArgs& fa, const float (&pin)[16]) {
   double S[NACC];
 #pragma unroll
   for (int c = 0; c < NACC; ++c) S[c] = s_tot[c];
@@ -610,7 +611,34 @@ __device__ __forceinline__ void final_stage(const float* __restrict__ partials, 
     for (int k = 0; k < 16; ++k) fa.pose[k] = (k % 5 == 0) ? 1.f : 0.f;
   }
   fa.stats[0] = (float)(S[27] * (double)fa.inv_pixels);            // valid_ratio (icp.py:46-47)
-  if (!(fa.f32_solve ? gn_update_f32(S, fa.damping, fa.pose) : gn_update(S, fa.damping, fa.pose))) fa.stats[2] += 1.f;
+  if (!(fa.f32_solve ? gn_update_f32(S, fa.damping, pin, fa.pose) : gn_update(S, fa.damping, pin, fa.pose))) fa.stats[2] += 1.f;
+}
+
+// Executed by ONE whole workgroup (256 threads): the last one to arrive in the residual kernel.  STAMP: cyc[0] / cyc[1] =
+// shader cycles of the partial-row reads + float64 sum / of the rest (solve and pose update), thread 0's view.
+template <bool STAMP>
+__device__ __forceinline__ void final_stage(const float* __restrict__ partials, int nblocks, const FinalArgs& fa,
+                                            unsigned long long (&cyc)[2]) {
+  __shared__ double s_sum[32 * PSTRIDE];
+  __shared__ double s_tot[PSTRIDE];
+  unsigned long long t0 = 0;
+  if constexpr (STAMP) t0 = __builtin_readcyclecounter();
+  // the pose this step starts from, loaded while the partial rows are summed (the identity for a track's first step)
+  float pin[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) pin[k] = (k % 5 == 0) ? 1.f : 0.f;
+  if (threadIdx.x == 0 && fa.mode == MODE_SOLVE && !(fa.first & 2)) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) pin[k] = fa.pose[k];
+  }
+  sum_partials(partials, nblocks, s_sum, s_tot);
+  if constexpr (STAMP) { const unsigned long long t = __builtin_readcyclecounter(); cyc[0] = t - t0; t0 = t; }
+  if (threadIdx.x != 0) return;
+  final_solve_from(s_tot, fa, pin);
+  if constexpr (STAMP) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    cyc[1] = __builtin_readcyclecounter() - t0;
+  }
 }
 
 // Publish this workgroup's partial row and elect the last arriver.  Hand-off form (cdna_hip_programming.md
@@ -639,48 +667,70 @@ struct LevelGeom {
   int W;
 };
 
-// One source pixel: transform, project, nearest-neighbour association, the three gates, and the rank-1 update of the
-// 27 sums + valid count.  The float32 op sequence of the gating arithmetic follows the reference's (icp.py:52-104,
-// warp_features :132-148) so that associations and gate decisions match it bit for bit.
-__device__ __forceinline__ void accumulate_pixel(const LevelGeom& g, float v0, float v1, float v2, float n0, float n1,
-                                                 float n2, const float* __restrict__ vt, const float* __restrict__ nt,
-                                                 float (&acc)[NACC]) {
-  const float px = (g.R00 * v0 + g.R01 * v1 + g.R02 * v2) + g.t0;
-  const float py = (g.R10 * v0 + g.R11 * v1 + g.R12 * v2) + g.t1;
-  const float pz = (g.R20 * v0 + g.R21 * v1 + g.R22 * v2) + g.t2;
-  const float u = (px / pz) * g.fx + g.cx;
-  const float v = (py / pz) * g.fy + g.cy;
+// One source pixel, split at the gather so that a lane can issue the target loads of all of its pixels before it uses
+// any: project() transforms, projects and associates (icp.py:52-76, warp_features :132-148) and gives the element
+// index of the target pixel, or -1 (outside the view, or no source depth); finish() applies the target-depth, normal
+// and distance gates and adds the rank-1 update of the 27 sums + valid count.  The float32 op sequence of the gating
+// arithmetic follows the reference's so that associations and gate decisions match it bit for bit.
+struct Proj {
+  float px, py, pz;
+  int j;
+};
+struct Tgt {
+  float q0, q1, q2, m0, m1, m2;
+};
+
+__device__ __forceinline__ Proj project(const LevelGeom& g, float v0, float v1, float v2) {
+  Proj P;
+  P.px = (g.R00 * v0 + g.R01 * v1 + g.R02 * v2) + g.t0;
+  P.py = (g.R10 * v0 + g.R11 * v1 + g.R12 * v2) + g.t1;
+  P.pz = (g.R20 * v0 + g.R21 * v1 + g.R22 * v2) + g.t2;
+  P.j = -1;
+  const float u = (P.px / P.pz) * g.fx + g.cx;
+  const float v = (P.py / P.pz) * g.fy + g.cy;
   const bool inview = (u > 0.f) && (u < g.Wm1) && (v > 0.f) && (v < g.Hm1);
-  if (!inview || !(v2 > 0.f)) return;
-  // grid_sample(nearest, border, align_corners=True) of warp_features (icp.py:132-148)
-  const float un = u / g.hw - 1.f, vn = v / g.hh - 1.f;
-  float ix = ((un + 1.f) / 2.f) * g.Wm1, iy = ((vn + 1.f) / 2.f) * g.Hm1;
-  ix = fminf(g.Wm1, fmaxf(ix, 0.f));
-  iy = fminf(g.Hm1, fmaxf(iy, 0.f));
-  const int xi = (int)nearbyintf(ix), yi = (int)nearbyintf(iy);
-  const size_t j = ((size_t)yi * g.W + xi) * 3;
-  const float q0 = vt[j], q1 = vt[j + 1], q2 = vt[j + 2];
-  if (!(q2 > 0.f)) return;
-  const float m0 = nt[j], m1 = nt[j + 1], m2 = nt[j + 2];
+  if (inview && (v2 > 0.f)) {
+    // grid_sample(nearest, border, align_corners=True) of warp_features (icp.py:132-148)
+    const float un = u / g.hw - 1.f, vn = v / g.hh - 1.f;
+    float ix = ((un + 1.f) / 2.f) * g.Wm1, iy = ((vn + 1.f) / 2.f) * g.Hm1;
+    ix = fminf(g.Wm1, fmaxf(ix, 0.f));
+    iy = fminf(g.Hm1, fmaxf(iy, 0.f));
+    P.j = ((int)nearbyintf(iy) * g.W + (int)nearbyintf(ix)) * 3;
+  }
+  return P;
+}
+
+// Target vertex AND target normal in one round trip; the target-depth test comes after the data.  No branch around the
+// loads (a pixel without a target reads pixel 0 and finish() drops it): a branch per pixel makes the compiler wait for
+// each pixel's loads before the next pixel's are issued.
+__device__ __forceinline__ Tgt gather(const Proj& P, const float* __restrict__ vt, const float* __restrict__ nt) {
+  const int j = P.j < 0 ? 0 : P.j;
+  return Tgt{vt[j], vt[j + 1], vt[j + 2], nt[j], nt[j + 1], nt[j + 2]};
+}
+
+__device__ __forceinline__ void finish(const LevelGeom& g, const Proj& P, float n0, float n1, float n2, const Tgt& T,
+                                       float (&acc)[NACC]) {
+  if (P.j < 0 || !(T.q2 > 0.f)) return;
   const float rn0 = g.R00 * n0 + g.R01 * n1 + g.R02 * n2;
   const float rn1 = g.R10 * n0 + g.R11 * n1 + g.R12 * n2;
   const float rn2 = g.R20 * n0 + g.R21 * n1 + g.R22 * n2;
-  if (!(rn0 * m0 + rn1 * m1 + rn2 * m2 > g.cos_thr)) return;
-  const float d0 = px - q0, d1 = py - q1, d2 = pz - q2;
+  if (!(rn0 * T.m0 + rn1 * T.m1 + rn2 * T.m2 > g.cos_thr)) return;
+  const float d0 = P.px - T.q0, d1 = P.py - T.q1, d2 = P.pz - T.q2;
   if (sqrtf(d0 * d0 + d1 * d1 + d2 * d2) > g.dist_thr) return;
-  const float r = m0 * d0 + m1 * d1 + m2 * d2;
+  const float r = T.m0 * d0 + T.m1 * d1 + T.m2 * d2;
   float J[6];
-  J[0] = py * m2 - pz * m1;        // -(m^T [p]x) = p x m
-  J[1] = pz * m0 - px * m2;
-  J[2] = px * m1 - py * m0;
-  J[3] = m0; J[4] = m1; J[5] = m2;
+  J[0] = P.py * T.m2 - P.pz * T.m1;        // -(m^T [p]x) = p x m
+  J[1] = P.pz * T.m0 - P.px * T.m2;
+  J[2] = P.px * T.m1 - P.py * T.m0;
+  J[3] = T.m0; J[4] = T.m1; J[5] = T.m2;
+  // the sums are not gating arithmetic: one fused multiply-add per term (-ffp-contract=off would split them)
   int k = 0;
 #pragma unroll
   for (int a = 0; a < 6; ++a)
 #pragma unroll
-    for (int b = a; b < 6; ++b) acc[k++] += J[a] * J[b];
+    for (int b = a; b < 6; ++b) { acc[k] = __builtin_fmaf(J[a], J[b], acc[k]); ++k; }
 #pragma unroll
-  for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+  for (int a = 0; a < 6; ++a) acc[21 + a] = __builtin_fmaf(J[a], r, acc[21 + a]);
   acc[27] += 1.f;
 }
 
@@ -699,70 +749,165 @@ __device__ __forceinline__ LevelGeom make_geom(const float* pose, const float* _
   return g;
 }
 
-// The source maps are [n,3] float32: a lane takes FOUR consecutive pixels = 48 contiguous bytes per map = three 16-B
-// loads (the 12-B pixel stride rules out one vector load per pixel); the remaining n % 4 pixels go to one lane each.
+// STAMP (measurement only, rtgs_icp_set_stamps, tools/icp_stamps.py): every wave of a stamped launch leaves eight 64-bit
+// words - wall clock (100 MHz) at entry and exit, then shader cycles of: source loads (issue -> data) | gathers (issue ->
+// data) | projection, gates and rank-1 updates | publish of the partial row + ticket | last arriver only: partial-row
+// reads + float64 sum | the Gauss-Newton solve.  Each lap drains the wave's loads (s_waitcnt vmcnt(0)) before it reads
+// the clock; loads the compiler issues after a drain land in the next phase.
+struct Stamp {
+  unsigned long long t, src, gat, acc;
+};
+template <bool STAMP>
+__device__ __forceinline__ void stamp_lap(Stamp& s, unsigned long long& into, bool drain) {
+  if constexpr (STAMP) {
+    if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long t = __builtin_readcyclecounter();
+    into += t - s.t;
+    s.t = t;
+  }
+}
+
+// The source maps are [n,3] float32: a lane takes FOUR consecutive pixels (a quad) = 48 contiguous bytes per map = three
+// 16-B loads (the 12-B pixel stride rules out one vector load per pixel); the remaining n % 4 pixels go to one lane each.
+// Per quad: the six source loads, then the 4 x 6 target loads in one go - two dependent memory round trips per quad
+// instead of three per pixel.  (Two or four quads per pass with every source load first measured slower - 241 / 245 us
+// per 1200x680 track against 237, with 182 / 256 VGPRs - when the gathers still had a branch per pixel.)
+template <bool STAMP>
 __device__ __forceinline__ void accumulate_range(const LevelGeom& g, const float* __restrict__ vs,
                                                  const float* __restrict__ ns, const float* __restrict__ vt,
                                                  const float* __restrict__ nt, int n, int first, int stride,
-                                                 float (&acc)[NACC]) {
+                                                 float (&acc)[NACC], Stamp& st) {
   const int n4 = n >> 2;
   const float4* vs4 = reinterpret_cast<const float4*>(vs);
   const float4* ns4 = reinterpret_cast<const float4*>(ns);
   for (int q = first; q < n4; q += stride) {
     const float4 a0 = vs4[3 * q], a1 = vs4[3 * q + 1], a2 = vs4[3 * q + 2];
     const float4 b0 = ns4[3 * q], b1 = ns4[3 * q + 1], b2 = ns4[3 * q + 2];
-    accumulate_pixel(g, a0.x, a0.y, a0.z, b0.x, b0.y, b0.z, vt, nt, acc);
-    accumulate_pixel(g, a0.w, a1.x, a1.y, b0.w, b1.x, b1.y, vt, nt, acc);
-    accumulate_pixel(g, a1.z, a1.w, a2.x, b1.z, b1.w, b2.x, vt, nt, acc);
-    accumulate_pixel(g, a2.y, a2.z, a2.w, b2.y, b2.z, b2.w, vt, nt, acc);
+    stamp_lap<STAMP>(st, st.src, true);
+    const Proj P0 = project(g, a0.x, a0.y, a0.z);
+    const Proj P1 = project(g, a0.w, a1.x, a1.y);
+    const Proj P2 = project(g, a1.z, a1.w, a2.x);
+    const Proj P3 = project(g, a2.y, a2.z, a2.w);
+    const Tgt T0 = gather(P0, vt, nt), T1 = gather(P1, vt, nt), T2 = gather(P2, vt, nt), T3 = gather(P3, vt, nt);
+    stamp_lap<STAMP>(st, st.acc, false);
+    stamp_lap<STAMP>(st, st.gat, true);
+    finish(g, P0, b0.x, b0.y, b0.z, T0, acc);
+    finish(g, P1, b0.w, b1.x, b1.y, T1, acc);
+    finish(g, P2, b1.z, b1.w, b2.x, T2, acc);
+    finish(g, P3, b2.y, b2.z, b2.w, T3, acc);
+    stamp_lap<STAMP>(st, st.acc, false);
   }
   const int idx = 4 * n4 + first;
-  if (idx < n)
-    accumulate_pixel(g, vs[(size_t)idx * 3], vs[(size_t)idx * 3 + 1], vs[(size_t)idx * 3 + 2], ns[(size_t)idx * 3],
-                     ns[(size_t)idx * 3 + 1], ns[(size_t)idx * 3 + 2], vt, nt, acc);
+  if (idx < n) {
+    const float* v = vs + (size_t)idx * 3;
+    const float* m = ns + (size_t)idx * 3;
+    const float n0 = m[0], n1 = m[1], n2 = m[2];
+    const Proj P = project(g, v[0], v[1], v[2]);
+    finish(g, P, n0, n1, n2, gather(P, vt, nt), acc);
+  }
 }
 
 // K points at the FULL-resolution intrinsics; `ds` is the level's downscale (icp.py:431-433).
-__global__ void __launch_bounds__(256) icp_reduce_kernel(
+template <bool STAMP>
+__device__ __forceinline__ void icp_reduce_body(
     const float* __restrict__ vs, const float* __restrict__ ns, const float* __restrict__ vt,
     const float* __restrict__ nt, int H, int W, const float* __restrict__ K, float ds,
     const float* __restrict__ pose, float dist_thr, float cos_thr, float* __restrict__ partials,
-    uint32_t* __restrict__ ticket, FinalArgs fa) {
+    uint32_t* __restrict__ ticket, const FinalArgs& fa, unsigned long long* __restrict__ stamps) {
   wave_priority_high();
+  unsigned long long wall0 = 0;
+  Stamp st{0, 0, 0, 0};
+  if constexpr (STAMP) { wall0 = wall_clock64(); st.t = __builtin_readcyclecounter(); }
   const LevelGeom g = make_geom((fa.first & 2) ? c_identity : pose, K, ds, H, W, dist_thr, cos_thr);
   float acc[NACC];
 #pragma unroll
   for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-  accumulate_range(g, vs, ns, vt, nt, H * W, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, acc);
-  block_write_partials(acc, partials);
-  if (arrive_and_elect_last(ticket)) final_stage(partials, (int)gridDim.x, fa);
+  accumulate_range<STAMP>(g, vs, ns, vt, nt, H * W, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, acc, st);
+  block_write_partials<NACC>(acc, partials);
+  const bool last = arrive_and_elect_last(ticket);
+  unsigned long long pub = 0, fin[2] = {0, 0};
+  stamp_lap<STAMP>(st, pub, false);
+  if (last) final_stage<STAMP>(partials, (int)gridDim.x, fa, fin);
+  if constexpr (STAMP) {
+    if ((threadIdx.x & 63) == 0) {
+      unsigned long long* o = stamps + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+      o[0] = wall0; o[1] = wall_clock64(); o[2] = st.src; o[3] = st.gat; o[4] = st.acc; o[5] = pub;
+      o[6] = fin[0]; o[7] = fin[1];
+    }
+  }
 }
 
+#define RTGS_ICP_REDUCE_ARGS                                                                                              \
+  const float *__restrict__ vs, const float *__restrict__ ns, const float *__restrict__ vt,                               \
+      const float *__restrict__ nt, int H, int W, const float *__restrict__ K, float ds, const float *__restrict__ pose,  \
+      float dist_thr, float cos_thr, float *__restrict__ partials, uint32_t *__restrict__ ticket, FinalArgs fa,          \
+      unsigned long long *__restrict__ stamps
+#define RTGS_ICP_REDUCE_PASS vs, ns, vt, nt, H, W, K, ds, pose, dist_thr, cos_thr, partials, ticket, fa, stamps
+__global__ void __launch_bounds__(256) icp_reduce_kernel(RTGS_ICP_REDUCE_ARGS) {
+  icp_reduce_body<false>(RTGS_ICP_REDUCE_PASS);
+}
+// the same, leaving per-wave time stamps (tools/icp_stamps.py)
+__global__ void __launch_bounds__(256) icp_reduce_stamped_kernel(RTGS_ICP_REDUCE_ARGS) {
+  icp_reduce_body<true>(RTGS_ICP_REDUCE_PASS);
+}
+#undef RTGS_ICP_REDUCE_ARGS
+#undef RTGS_ICP_REDUCE_PASS
+
 // ---- point2plane_loss (icp.py:7-13) at one level: sum(((R v1 + t - v0) . n0)^2) ---------------
+// Quads as in accumulate_range: a lane issues the nine 16-B loads (source vertex, target vertex, target normal) of each of
+// its (up to) two quads of a pass before the first use - one memory round trip per pass, two passes per lane at 1200x680
+// (one pixel per lane and nine scalar loads per pixel before: 13.0 -> 11.0 us).
+constexpr int P2P_QUADS = 2;
+__device__ __forceinline__ float p2p_term(const float* Rt, float v0, float v1, float v2, float q0, float q1, float q2,
+                                          float m0, float m1, float m2) {
+  const float px = (v0 * Rt[0] + v1 * Rt[1] + v2 * Rt[2]) + Rt[3];
+  const float py = (v0 * Rt[4] + v1 * Rt[5] + v2 * Rt[6]) + Rt[7];
+  const float pz = (v0 * Rt[8] + v1 * Rt[9] + v2 * Rt[10]) + Rt[11];
+  const float l = (px - q0) * m0 + (py - q1) * m1 + (pz - q2) * m2;
+  return l * l;
+}
+
 __global__ void __launch_bounds__(256) icp_p2p_kernel(const float* __restrict__ vs, const float* __restrict__ vt,
                                                       const float* __restrict__ nt, int n,
                                                       const float* __restrict__ pose, float* __restrict__ partials,
                                                       uint32_t* __restrict__ ticket, FinalArgs fa) {
   wave_priority_high();
-  const float R00 = pose[0], R01 = pose[1], R02 = pose[2], t0 = pose[3];
-  const float R10 = pose[4], R11 = pose[5], R12 = pose[6], t1 = pose[7];
-  const float R20 = pose[8], R21 = pose[9], R22 = pose[10], t2 = pose[11];
-  float acc[NACC];
+  float Rt[12];
 #pragma unroll
-  for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-    const size_t j = (size_t)idx * 3;
-    const float v0 = vs[j], v1 = vs[j + 1], v2 = vs[j + 2];
-    const float px = (v0 * R00 + v1 * R01 + v2 * R02) + t0;
-    const float py = (v0 * R10 + v1 * R11 + v2 * R12) + t1;
-    const float pz = (v0 * R20 + v1 * R21 + v2 * R22) + t2;
-    const float l = (px - vt[j]) * nt[j] + (py - vt[j + 1]) * nt[j + 1] + (pz - vt[j + 2]) * nt[j + 2];
-    acc[0] += l * l;
+  for (int k = 0; k < 12; ++k) Rt[k] = pose[k];
+  float acc[1] = {0.f};
+  const int n4 = n >> 2, first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+  const float4* vs4 = reinterpret_cast<const float4*>(vs);
+  const float4* vt4 = reinterpret_cast<const float4*>(vt);
+  const float4* nt4 = reinterpret_cast<const float4*>(nt);
+  for (int base = first; base < n4; base += P2P_QUADS * stride) {
+    float4 a[P2P_QUADS][3], c[P2P_QUADS][3], m[P2P_QUADS][3];
+#pragma unroll
+    for (int i = 0; i < P2P_QUADS; ++i) {
+      const int q = base + i * stride;
+      if (q < n4) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { a[i][k] = vs4[3 * q + k]; c[i][k] = vt4[3 * q + k]; m[i][k] = nt4[3 * q + k]; }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < P2P_QUADS; ++i) {
+      if (base + i * stride >= n4) break;
+      acc[0] += p2p_term(Rt, a[i][0].x, a[i][0].y, a[i][0].z, c[i][0].x, c[i][0].y, c[i][0].z, m[i][0].x, m[i][0].y, m[i][0].z);
+      acc[0] += p2p_term(Rt, a[i][0].w, a[i][1].x, a[i][1].y, c[i][0].w, c[i][1].x, c[i][1].y, m[i][0].w, m[i][1].x, m[i][1].y);
+      acc[0] += p2p_term(Rt, a[i][1].z, a[i][1].w, a[i][2].x, c[i][1].z, c[i][1].w, c[i][2].x, m[i][1].z, m[i][1].w, m[i][2].x);
+      acc[0] += p2p_term(Rt, a[i][2].y, a[i][2].z, a[i][2].w, c[i][2].y, c[i][2].z, c[i][2].w, m[i][2].y, m[i][2].z, m[i][2].w);
+    }
   }
-  block_write_partials(acc, partials);
-  if (arrive_and_elect_last(ticket)) final_stage(partials, (int)gridDim.x, fa);
+  const int idx = 4 * n4 + first;
+  if (idx < n) {
+    const size_t j = (size_t)idx * 3;
+    acc[0] += p2p_term(Rt, vs[j], vs[j + 1], vs[j + 2], vt[j], vt[j + 1], vt[j + 2], nt[j], nt[j + 1], nt[j + 2]);
+  }
+  block_write_partials<1>(acc, partials);      // only column 0: the last arriver reads nothing else in MODE_P2P
+  unsigned long long fin[2];
+  if (arrive_and_elect_last(ticket)) final_stage<false>(partials, (int)gridDim.x, fa, fin);
 }
-
 // ---- the whole track as ONE persistent kernel ---------------------------------------------------
 // IcpTracker.predict_pose's level loop (icp.py:428-447: 3 levels x 5 Gauss-Newton iterations, then the p2p loss) used
 // to be 16 dependent launches, each with a whole-grid fan-in to a last-arriver workgroup and a fan-out through the next
@@ -851,7 +996,8 @@ __global__ void __launch_bounds__(256) icp_track_kernel(TrackArgs a) {
       const LevelGeom g = make_geom(s_pose, a.K, L.ds, L.H, L.W, a.dist_thr, a.cos_thr);
 #pragma unroll
       for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-      accumulate_range(g, L.vs, L.ns, L.vt, L.nt, n, bid * 256 + (int)threadIdx.x, G * 256, acc);
+      Stamp no_stamp{0, 0, 0, 0};
+      accumulate_range<false>(g, L.vs, L.ns, L.vt, L.nt, n, bid * 256 + (int)threadIdx.x, G * 256, acc, no_stamp);
       double* totals = a.sums + (size_t)epoch * 8 * PSTRIDE;
       if (stamp) a.dbg[5 * epoch + 1] = wall_clock64();
       block_add_totals(acc, totals + ((uint32_t)bid & 7u) * PSTRIDE);
@@ -866,7 +1012,10 @@ __global__ void __launch_bounds__(256) icp_track_kernel(TrackArgs a) {
 #pragma unroll
         for (int c = 0; c < NACC; ++c) S[c] = s_tot[c];
         s_stat[0] = (float)(S[27] * (double)inv);                // valid_ratio of this iteration (icp.py:46-47)
-        if (!gn_update(S, a.damping, s_pose)) s_stat[2] += 1.f;
+        float pin[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) pin[k] = s_pose[k];
+        if (!gn_update(S, a.damping, pin, s_pose)) s_stat[2] += 1.f;
         if (stamp) a.dbg[5 * epoch - 1] = wall_clock64();
       }
       __syncthreads();
@@ -931,6 +1080,24 @@ __global__ void __launch_bounds__(256) icp_fill_kernel(float* __restrict__ rd, c
 static int grid_for(int n) {
   int g = (n + 255) / 256;
   return g > MAX_BLOCKS ? MAX_BLOCKS : (g < 1 ? 1 : g);
+}
+
+static unsigned long long* g_stamps = nullptr;     // rtgs_icp_set_stamps (include/rtgs_debug.h)
+static int g_stamp_launch = 0;
+
+// One residual launch over H x W pixels: a lane takes four pixels, one workgroup per 1024 pixels up to MAX_BLOCKS - at the
+// coarse levels that is 50 / 200 workgroups, and as many tickets and partial rows for the last arriver to collect.
+static void launch_reduce(const float* vs, const float* ns, const float* vt, const float* nt, int H, int W, const float* K,
+                          float ds, const float* pose, float dist_thr, float cos_thr, float* partials, uint32_t* ticket,
+                          const FinalArgs& fa, hipStream_t st) {
+  const int g = grid_for((H * W + 3) / 4);
+  unsigned long long* stamps = nullptr;
+  if (g_stamps) stamps = g_stamps + (size_t)(g_stamp_launch++ % RTGS_ICP_STAMP_LAUNCHES) * RTGS_ICP_STAMP_WGS * 4 * 8;
+#define RTGS_ICP_LAUNCH(KERNEL)                                                                                        \
+  hipLaunchKernelGGL(KERNEL, dim3(g), dim3(256), 0, st, vs, ns, vt, nt, H, W, K, ds, pose, dist_thr, cos_thr, partials, \
+                     ticket, fa, stamps)
+  if (stamps) RTGS_ICP_LAUNCH(icp_reduce_stamped_kernel); else RTGS_ICP_LAUNCH(icp_reduce_kernel);
+#undef RTGS_ICP_LAUNCH
 }
 
 }  // namespace rtgs_icp
@@ -1011,11 +1178,9 @@ int rtgs_icp_step(const float* vs, const float* ns, const float* vt, const float
     return -1;
   hipStream_t st = (hipStream_t)stream;
   Scratch* sc = (Scratch*)scratch;
-  const int g = grid_for(H * W);
   ICP_TRY(hipMemsetAsync(&sc->ticket, 0, sizeof(uint32_t), st));
   FinalArgs fa{(int)MODE_EQUATIONS, 0.f, 0.f, nullptr, nullptr, JtJ_out, Jtr_out, nvalid_out};
-  hipLaunchKernelGGL(icp_reduce_kernel, dim3(g), dim3(256), 0, st, vs, ns, vt, nt, H, W, K, 1.0f, pose, dist_thr,
-                     cos_thr, sc->partials, &sc->ticket, fa);
+  launch_reduce(vs, ns, vt, nt, H, W, K, 1.0f, pose, dist_thr, cos_thr, sc->partials, &sc->ticket, fa, st);
   ICP_TRY(hipGetLastError());
   return 0;
 }
@@ -1103,18 +1268,13 @@ int rtgs_icp_track(const rtgs_icp_level* lv, int32_t n_levels, const float* K, f
   bool launched_any = false;
   for (int l = first_launched; l < n_levels; ++l) {
     const rtgs_icp_level& L = lv[l];
-    // a lane takes FOUR pixels (accumulate_range): one workgroup per 1024 pixels - at the coarse levels that is 50 / 200
-    // workgroups instead of 200 / 512 with three lanes in four idle, and as many fewer tickets and partial rows for the
-    // last arriver to collect
-    const int g = grid_for((L.H * L.W + 3) / 4);
     const float inv = 1.f / ((float)L.H * (float)L.W);
     FinalArgs fa{(int)MODE_SOLVE, damping, inv, pose, stats, nullptr, nullptr, nullptr, 0, (flags & RTGS_ICP_FLAG_F32_SOLVE) ? 1 : 0};
     for (int it = 0; it < L.iters; ++it) {   // ONE launch per Gauss-Newton iteration: residuals + solve + pose update
       fa.first = (plain && !launched_any) ? (1 | (from_identity ? 2 : 0)) : 0;
       launched_any = true;
-      hipLaunchKernelGGL(icp_reduce_kernel, dim3(g), dim3(256), 0, st, L.vertex_src, L.normal_src, L.vertex_tgt,
-                         L.normal_tgt, L.H, L.W, K, L.downscale, (const float*)pose, dist_thr, cos_thr, sc->partials,
-                         &sc->ticket, fa);
+      launch_reduce(L.vertex_src, L.normal_src, L.vertex_tgt, L.normal_tgt, L.H, L.W, K, L.downscale, pose, dist_thr,
+                    cos_thr, sc->partials, &sc->ticket, fa, st);
     }
   }
   if (plain && !launched_any) {                    // no iteration anywhere: nobody cleared / initialised anything
@@ -1126,12 +1286,17 @@ int rtgs_icp_track(const rtgs_icp_level* lv, int32_t n_levels, const float* K, f
   }
   const rtgs_icp_level& F = lv[n_levels - 1];
   const int n = F.H * F.W;
-  const int g = grid_for(n);
+  const int g = grid_for((n + 3) / 4);
   FinalArgs fp{(int)MODE_P2P, 0.f, 1.f / (float)n, pose, stats, nullptr, nullptr, nullptr, 0, 0};
   hipLaunchKernelGGL(icp_p2p_kernel, dim3(g), dim3(256), 0, st, F.vertex_src, F.vertex_tgt, F.normal_tgt, n,
                      (const float*)pose, sc->partials, &sc->ticket, fp);
   ICP_TRY(hipGetLastError());
   return 0;
+}
+
+void rtgs_icp_set_stamps(void* dev) {
+  g_stamps = (unsigned long long*)dev;
+  g_stamp_launch = 0;
 }
 
 int rtgs_icp_fill_model_depth(float* rd, const float* fd, const float* rn, const float* fn, int32_t H, int32_t W,
