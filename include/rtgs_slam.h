@@ -15,6 +15,9 @@
  *   rtgs_gather_rows3        the normal-map gather of Renderer.render, SLAM/render.py:130-133
  *   rtgs_eval_*              SLAM/eval.py's picture metrics (utils/loss_utils.py psnr / l1_loss, pytorch_msssim.ms_ssim)
  *                            and the nearest-neighbour reduction of eval_pcd (scipy cKDTree queries: rtgs_knn3_query_built)
+ *   rtgs_ingest_rgbd         the pixel arithmetic between the dataset files and the tracker: readCameras' depth scaling
+ *                            (scene/dataset_readers.py:848-932), PILtoTorch (utils/general_utils.py:43-49) and map_preprocess's
+ *                            * 255 (SLAM/multiprocess/tracker.py:97-101)
  */
 #ifndef RTGS_SLAM_H
 #define RTGS_SLAM_H
@@ -239,6 +242,15 @@ int rtgs_eval_picture(const float* render, const float* gt_color, const float* d
 size_t rtgs_eval_nn_stats_scratch_bytes(int32_t N, int32_t k);
 int rtgs_eval_nn_stats(const float* dist2, int32_t N, const double* thresholds, int32_t k, void* scratch, double* out,
                        void* stream);
+
+/* ---- frame ingest (scene/dataset_readers.py:848-932 -> utils/general_utils.py:43-49 -> tracker.py:97-101) ----------
+ * One launch per frame: raw u16 depth [Hd,Wd] and u8 colour [Hd,Wd,channels] (channels 3 or 4; a 4th channel is dropped)
+ * -> depth_out [H,W] float32 and color_out [3,H,W] float32, H = Hd - 2 crop, W = Wd - 2 crop (the [c:-c, c:-c] crop of
+ * readCameras).  Per pixel, each step one correctly rounded float32 operation, bit-identical to the reference's chain:
+ *   depth_out = ((f32(raw) / depth_scale) / 255) * 255;   color_out[k] = f32(colour[k]) / 255.
+ * Returns -1 on a bad shape, channel count, crop or scale (depth_scale must be > 0). */
+int rtgs_ingest_rgbd(const uint16_t* depth_raw, const uint8_t* color_raw, int32_t Hd, int32_t Wd, int32_t channels, int32_t crop,
+                     float depth_scale, float* depth_out, float* color_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,249 @@
+"""Command-line entry points, the reference's two scripts on recorded datasets:
+
+    python -m rtg_slam_amd slam   --config configs/replica/office0.yaml     (slam.py)
+    python -m rtg_slam_amd metric --config configs/replica/office0.yaml     (metric.py)
+
+`slam` writes, under the config's save_path: config.yaml (the merged config), save_model/frame_XXXX/iter_XXXX*.ply (at frame 0,
+every save_step frames and after the final global optimisation), save_traj/pose_es.npy, pose_gt.npy and ate.txt (the ATE in
+cm of every prefix of the trajectory), performance.json, eval_metric/slam_eval.csv (the in-loop evaluation rows) and
+run_report.json (run_sequence's report plus the I/O statistics of the frame source).  `metric` evaluates a saved model over
+the same frames and writes statis_frame_F_iter_I.csv.
+
+What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
+end (use_orb_backend: the trajectory is tracked with ICP only), pcd_densify (needs open3d) and rendered pictures."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import shutil
+import sys
+import time
+
+import numpy as np
+
+
+def log(msg: str) -> None:
+    print(f"[rtg_slam_amd] {msg}", flush=True)
+
+
+def horn_ate_cm(pose_estimate, pose_gt) -> float:
+    """SLAM/utils.py:455-503 eval_ate: align `pose_estimate`'s positions (model) onto `pose_gt`'s (data) with Horn's
+    closed form, then the RMSE of the residuals, in cm.  Inputs [n,3] positions."""
+    model = np.asarray(pose_estimate, dtype=np.float64).T
+    data = np.asarray(pose_gt, dtype=np.float64).T
+    mz = model - model.mean(1, keepdims=True)
+    dz = data - data.mean(1, keepdims=True)
+    Wm = mz @ dz.T
+    U, _, Vh = np.linalg.svd(Wm.T)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vh) < 0:
+        S[2, 2] = -1
+    rot = U @ S @ Vh
+    trans = data.mean(1, keepdims=True) - rot @ model.mean(1, keepdims=True)
+    err = rot @ model + trans - data
+    e = np.sqrt((err * err).sum(0))
+    return float(np.sqrt(np.dot(e, e) / len(e)) * 100)
+
+
+def prefix_ates(pose_es, pose_gt):
+    """tracker.py:297-302, 374-380: the ATE of every prefix 1..n.  The reference passes the GT trajectory as the estimate
+    (eval_ate(pose_gt, pose_es)), i.e. the GT positions are aligned onto the estimated ones; kept."""
+    es = np.stack([np.asarray(p)[:3, 3] for p in pose_es])
+    gt = np.stack([np.asarray(p)[:3, 3] for p in pose_gt])
+    return [horn_ate_cm(gt[:i], es[:i]) for i in range(1, len(gt) + 1)]
+
+
+def _save_model(mapper, save_path: str, frame: int) -> str:
+    d = os.path.join(save_path, "save_model", f"frame_{frame:04d}")
+    os.makedirs(d, exist_ok=True)
+    path = os.path.join(d, f"iter_{int(mapper.iter):04d}")
+    mapper.save_model(path)
+    return path
+
+
+def _dump_config(args, path: str) -> None:
+    import yaml
+    d = {}
+    for k, v in vars(args).items():
+        d[k] = list(v) if isinstance(v, tuple) else v
+    with open(path, "w") as f:
+        yaml.safe_dump(d, f, sort_keys=False)
+
+
+def cmd_slam(opts) -> int:
+    import torch
+    from . import config, datasets, io_formats as iof
+    from .mapping import Mapping
+    from .slam import run_sequence
+    args = config.load_config(opts.config)
+    if opts.frames is not None:
+        args.frame_num = int(opts.frames)
+    save_path = args.save_path
+    if os.path.isdir(save_path) and os.listdir(save_path):
+        if not opts.overwrite:
+            log(f"save_path {save_path} is not empty; pass --overwrite to replace it")
+            return 2
+        shutil.rmtree(save_path)
+    for sub in ("save_model", "save_traj", "eval_metric"):
+        os.makedirs(os.path.join(save_path, sub), exist_ok=True)
+    if getattr(args, "use_orb_backend", False):
+        log("use_orb_backend: the ORB-SLAM2 back end is not available; tracking with ICP only")
+    if "device_list" in vars(args):
+        log(f"device_list {args.device_list} ignored; running on {opts.device}")
+    device = torch.device(opts.device)
+    torch.cuda.set_device(device)
+    _dump_config(args, os.path.join(save_path, "config.yaml"))
+    info = datasets.load_dataset(args)
+    source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
+    cam = info.camera()
+    log(f"{info.type} {info.source_path}: {len(info)} frames {info.width}x{info.height}, {source.io_workers} io workers")
+    mapper = Mapping(args, device)
+    save_step = int(getattr(args, "save_step", 2000))
+    loop = {"t0": None, "t_last": None}
+
+    def on_frame(frame_id, frame, frame_map, mapper_, tracker):
+        t = mapper_.time
+        if t == 0 or (t + 1) % save_step == 0:
+            _save_model(mapper_, save_path, t)
+        loop["t_last"] = time.perf_counter()
+
+    torch.cuda.synchronize(device)
+    loop["t0"] = time.perf_counter()
+    mapper, tracker, report = run_sequence(cam, source, args, device, mapper=mapper, on_frame=on_frame, final_global=True,
+                                           eval_every=save_step)
+    n = report["frames"]
+    if n == 0:
+        log("no frames")
+        return 1
+    _save_model(mapper, save_path, mapper.time)
+    iof.save_trajectories(save_path, tracker.pose_es, tracker.pose_gt)
+    ates = prefix_ates(tracker.pose_es, tracker.pose_gt)
+    with open(os.path.join(save_path, "save_traj", "ate.txt"), "w") as f:
+        f.write("".join(f"{a!r}\n" for a in ates))
+    rec = iof.Recorder(device.index or 0)
+    for t_track, t_map, _, _ in report["per_frame"]:
+        rec.update_mean("tracking", t_track, 1)
+        rec.update_mean("mapping", t_map, 1)
+    if getattr(args, "record_mem", False):
+        rec.watch_gpu()
+    rec.cal_fps()
+    rec.save(save_path)
+    iof.save_metrics_csv(os.path.join(save_path, "eval_metric", "slam_eval.csv"), report.get("eval", []))
+    st = source.stats()
+    loop_s = loop["t_last"] - loop["t0"]
+    report.update(io_wait_s_mean=st["io_wait_s_mean"], io_wait_s=st["io_wait_s"], decode_ms_per_frame=st["decode_ms_per_frame"],
+                  io_workers=st["io_workers"], prefetch=st["prefetch"], h2d_bytes_per_frame=st["h2d_bytes_per_frame"],
+                  wall_fps_including_io=n / loop_s if loop_s > 0 else None, ate_cm=ates[-1])
+    with open(os.path.join(save_path, "run_report.json"), "w") as f:
+        json.dump(report, f, indent=1, default=float)
+    if getattr(args, "pcd_densify", False):
+        log("pcd_densify skipped (needs open3d)")
+    log(f"{n} frames: fps {report['fps']:.2f} (1 / mapping), wall fps with I/O {report['wall_fps_including_io']:.2f}, "
+        f"io wait {1e3 * st['io_wait_s_mean']:.3f} ms/frame, ATE {ates[-1]:.3f} cm -> {save_path}")
+    return 0
+
+
+def filter_models(frame_path: str, eval_merge: bool, load_iter):
+    """metric.py:37-66: the model files of a frame directory to evaluate (the stable cloud by default, the merged one with
+    eval_merge; the highest iteration unless load_iter names some)."""
+    exclude, include = ("stable", "merge") if eval_merge else ("merge", "stable")
+    total = [i for i in os.listdir(frame_path) if "sibr" not in i and exclude not in i]
+    if not total:
+        raise FileNotFoundError(f"rtg_slam_amd: no model file to evaluate in {frame_path} (eval_merge={eval_merge}; an empty "
+                                "cloud is not written)")
+    select = []
+    if len(load_iter) > 0:
+        for it in load_iter:
+            model_iter = [i for i in total if "%04d" % it in i]
+            merged = [i for i in model_iter if include in i]
+            select.extend(merged if merged else model_iter)
+    else:
+        max_iter = sorted([i[5:9] for i in total], reverse=True)[0]
+        total = [i for i in total if max_iter in i]
+        merged = [i for i in total if include in i]
+        select.extend(merged if merged else total)
+    return select
+
+
+def load_map(args, device, ply_path: str):
+    """A saved model file as a Mapping: load_model_ply -> model_to_packed -> append_rows, confidence kept, capacity = rows."""
+    import torch
+    from . import io_formats as iof
+    from .mapping import Mapping
+    m = iof.load_model_ply(ply_path, int(args.max_sh_degree))
+    packed = iof.model_to_packed(m)
+    n = int(packed.shape[0])
+    if n == 0:
+        raise ValueError(f"rtg_slam_amd: {ply_path} holds no Gaussians")
+    mapper = Mapping(args, device, capacity=n)
+    mapper.opt.append_rows(torch.from_numpy(packed).to(device),
+                           aux={"confidence": torch.from_numpy(m["confidence"]).to(device)})
+    return mapper
+
+
+def cmd_metric(opts) -> int:
+    import torch
+    from . import config, datasets, evaluation, io_formats as iof
+    args = config.load_config(opts.config)
+    device = torch.device(opts.device)
+    torch.cuda.set_device(device)
+    model_base = os.path.join(args.save_path, "save_model")
+    frames = sorted(i for i in os.listdir(model_base) if os.path.isdir(os.path.join(model_base, i)))
+    if opts.load_frame < 0:
+        check_frame = frames[-1]
+    else:
+        check_frame = [i for i in frames if "%04d" % opts.load_frame in i][0]
+    last = int(check_frame.split("_")[-1])
+    max_cams = last if opts.eval_frames < 0 else min(opts.eval_frames, last)
+    frame_path = os.path.join(model_base, check_frame)
+    select = filter_models(frame_path, opts.eval_merge, opts.load_iter)
+    model = select[0]
+    test_iter = model[5:9]
+    log(f"evaluating {os.path.join(frame_path, model)} over {max_cams} frames")
+    mapper = load_map(args, device, os.path.join(frame_path, model))
+    mapper.time = int(check_frame.split("_")[1])
+    mapper.iter = int(test_iter)
+    poses = None
+    if not args.use_gt_pose:
+        poses = np.load(os.path.join(args.save_path, "save_traj", "pose_es.npy")).reshape(-1, 4, 4)[int(args.frame_start):]
+    args.frame_num = max_cams
+    info = datasets.load_dataset(args)
+    source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
+    gt_points, transform = None, None
+    if info.mesh_path and os.path.isfile(info.mesh_path):
+        v, f = iof.load_mesh_ply(info.mesh_path)
+        gt_points, _ = iof.sample_mesh_surface(v, f, 1_000_000)
+        transform = datasets.read_pose_t0(args)
+    res = evaluation.evaluate_sequence(mapper, info.camera(), source, poses=poses, args=args, gt_points=gt_points,
+                                       dist_thres=[0.03], transform=transform, sample_nums=1_000_000)
+    out = os.path.join(args.save_path, f"statis_frame_{mapper.time}_iter_{test_iter}.csv")
+    iof.save_metrics_csv(out, res["rows"])
+    m = res["mean"]
+    log(f"{len(res['rows'])} frames: psnr {m.get('psnr')}, ssim {m.get('ssim')}, depth L1 {m.get('depth_loss')} -> {out}")
+    return 0
+
+
+def main(argv=None) -> int:
+    p = argparse.ArgumentParser(prog="python -m rtg_slam_amd", description=__doc__.split("\n\n")[0])
+    sub = p.add_subparsers(dest="cmd", required=True)
+    s = sub.add_parser("slam", help="run SLAM on a dataset (slam.py)")
+    s.add_argument("--config", required=True)
+    s.add_argument("--frames", type=int, default=None, help="overrides frame_num")
+    s.add_argument("--device", default="cuda:0")
+    s.add_argument("--io-workers", type=int, default=None)
+    s.add_argument("--overwrite", action="store_true", help="replace a non-empty save_path")
+    m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
+    m.add_argument("--config", required=True)
+    m.add_argument("--load-frame", type=int, default=-1)
+    m.add_argument("--load-iter", type=int, nargs="+", default=[])
+    m.add_argument("--eval-frames", type=int, default=-1)
+    m.add_argument("--eval-merge", action="store_true")
+    m.add_argument("--device", default="cuda:0")
+    m.add_argument("--io-workers", type=int, default=None)
+    opts = p.parse_args(argv)
+    return cmd_slam(opts) if opts.cmd == "slam" else cmd_metric(opts)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -226,6 +226,8 @@ _SIGNATURES = {
     "rtgs_eval_picture": (C.c_int, [_P] * 5 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _P, _P, _P]),
     "rtgs_eval_nn_stats_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtgs_eval_nn_stats": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    # frame ingest
+    "rtgs_ingest_rgbd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
