@@ -18,6 +18,8 @@
  *   rtgs_ingest_rgbd         the pixel arithmetic between the dataset files and the tracker: readCameras' depth scaling
  *                            (scene/dataset_readers.py:848-932), PILtoTorch (utils/general_utils.py:43-49) and map_preprocess's
  *                            * 255 (SLAM/multiprocess/tracker.py:97-101)
+ *   rtgs_densify_discs       GaussianPointCloud.densify (SLAM/gaussian_pointcloud.py:53-116), the points slam.py:146-150
+ *                            writes to save_model/pcd_densify.ply when the config sets pcd_densify
  */
 #ifndef RTGS_SLAM_H
 #define RTGS_SLAM_H
@@ -251,6 +253,20 @@ int rtgs_eval_nn_stats(const float* dist2, int32_t N, const double* thresholds, 
  * Returns -1 on a bad shape, channel count, crop or scale (depth_scale must be > 0). */
 int rtgs_ingest_rgbd(const uint16_t* depth_raw, const uint8_t* color_raw, int32_t Hd, int32_t Wd, int32_t channels, int32_t crop,
                      float depth_scale, float* depth_out, float* color_out, void* stream);
+
+/* ---- densification (SLAM/gaussian_pointcloud.py:53-116, with get_normal / get_plane :539-571) -----------------------
+ * Rows [row_begin, row_end) of the stable cloud: xyz [*,3], the activated scales [*,3] (exp of the raw scaling) and the
+ * normalised rotations [*,4] (r, x, y, z; build_rotation normalises them once more, as the reference does).  cos_theta /
+ * sin_theta [circle_num]: cos and sin of the reference's theta, computed by the caller.  K = sigma * levels * circle_num
+ * points per Gaussian, point k = s (levels circle_num) + l circle_num + c of row r written to
+ * out[((r - row_begin) K + k) 6 + 0..5] = x y z nx ny nz as float64 (the record of the PLY file): Gaussian-major, 64-bit
+ * offsets.  The float32 chain is in csrc/densify.hip; scale ties sort to the lower axis index.  out must be 16-B aligned.
+ * Returns 0 without a launch when row_end == row_begin; -1 on a bad range, count or pointer, or
+ * K > RTGS_DENSIFY_MAX_POINTS_PER_GAUSSIAN. */
+#define RTGS_DENSIFY_MAX_POINTS_PER_GAUSSIAN 2048
+int rtgs_densify_discs(const float* xyz, const float* scales, const float* rotations, int64_t row_begin, int64_t row_end,
+                       const float* cos_theta, const float* sin_theta, int32_t sigma, int32_t levels, int32_t circle_num,
+                       double* out, void* stream);
 
 #ifdef __cplusplus
 }

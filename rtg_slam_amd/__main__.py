@@ -6,11 +6,14 @@
 `slam` writes, under the config's save_path: config.yaml (the merged config), save_model/frame_XXXX/iter_XXXX*.ply (at frame 0,
 every save_step frames and after the final global optimisation), save_traj/pose_es.npy, pose_gt.npy and ate.txt (the ATE in
 cm of every prefix of the trajectory), performance.json, eval_metric/slam_eval.csv (the in-loop evaluation rows) and
-run_report.json (run_sequence's report plus the I/O statistics of the frame source).  `metric` evaluates a saved model over
-the same frames and writes statis_frame_F_iter_I.csv.
+run_report.json (run_sequence's report plus the I/O statistics of the frame source).  With --pcd-densify and a config that
+sets pcd_densify, it then writes save_model/pcd_densify.ply: 150 points on concentric ellipses around every stable Gaussian
+(Mapping.save_densified, slam.py:146-150), theta drawn from a generator seeded with the config's seed.  `metric` evaluates a
+saved model over the same frames and writes statis_frame_F_iter_I.csv; when the config sets pcd_densify and
+save_model/pcd_densify.ply exists, the reconstruction metrics are computed on that file's points (metric.py:156-163).
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
-end (use_orb_backend: the trajectory is tracked with ICP only), pcd_densify (needs open3d) and rendered pictures."""
+end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
 from __future__ import annotations
 
 import argparse
@@ -137,11 +140,34 @@ def cmd_slam(opts) -> int:
                   wall_fps_including_io=n / loop_s if loop_s > 0 else None, ate_cm=ates[-1])
     with open(os.path.join(save_path, "run_report.json"), "w") as f:
         json.dump(report, f, indent=1, default=float)
-    if getattr(args, "pcd_densify", False):
-        log("pcd_densify skipped (needs open3d)")
     log(f"{n} frames: fps {report['fps']:.2f} (1 / mapping), wall fps with I/O {report['wall_fps_including_io']:.2f}, "
         f"io wait {1e3 * st['io_wait_s_mean']:.3f} ms/frame, ATE {ates[-1]:.3f} cm -> {save_path}")
+    if getattr(args, "pcd_densify", False):
+        if opts.pcd_densify:
+            path = os.path.join(save_path, "save_model", DENSIFY_PLY)
+            seed = getattr(args, "seed", None)
+            gen = torch.Generator().manual_seed(0 if seed is None else int(seed))
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            n_points = mapper.save_densified(path, 1, 30, 5, generator=gen)      # slam.py:147: densify(1, 30, 5)
+            log(f"pcd_densify: {n_points} points from {mapper.get_stable_num} stable Gaussians in "
+                f"{time.perf_counter() - t0:.3f} s -> {path if n_points else '(empty stable cloud: no file)'}")
+        else:
+            log("pcd_densify skipped (pass --pcd-densify to write save_model/pcd_densify.ply)")
     return 0
+
+
+DENSIFY_PLY = "pcd_densify.ply"
+
+
+def geometry_ply(args, model_base: str, select_ply: str) -> str:
+    """metric.py:156-163: the file the reconstruction metrics are computed on - save_model/pcd_densify.ply when the config
+    sets pcd_densify and the file exists, the selected model file otherwise."""
+    if getattr(args, "pcd_densify", False):
+        path = os.path.join(model_base, DENSIFY_PLY)
+        if os.path.exists(path):
+            return path
+    return select_ply
 
 
 def filter_models(frame_path: str, eval_merge: bool, load_iter):
@@ -201,7 +227,10 @@ def cmd_metric(opts) -> int:
     model = select[0]
     test_iter = model[5:9]
     log(f"evaluating {os.path.join(frame_path, model)} over {max_cams} frames")
-    mapper = load_map(args, device, os.path.join(frame_path, model))
+    select_ply = os.path.join(frame_path, model)
+    pcd_path = geometry_ply(args, model_base, select_ply)
+    log(f"geometry eval ply: {pcd_path}")
+    mapper = load_map(args, device, select_ply)
     mapper.time = int(check_frame.split("_")[1])
     mapper.iter = int(test_iter)
     poses = None
@@ -210,13 +239,18 @@ def cmd_metric(opts) -> int:
     args.frame_num = max_cams
     info = datasets.load_dataset(args)
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
-    gt_points, transform = None, None
+    gt_points, transform, rec_points = None, None, None
     if info.mesh_path and os.path.isfile(info.mesh_path):
         v, f = iof.load_mesh_ply(info.mesh_path)
         gt_points, _ = iof.sample_mesh_surface(v, f, 1_000_000)
         transform = datasets.read_pose_t0(args)
+        if pcd_path != select_ply:
+            xyz, _ = iof.load_point_cloud_ply(pcd_path)
+            if xyz.shape[0] == 0:
+                raise ValueError(f"rtg_slam_amd: {pcd_path} holds no points")
+            rec_points = torch.from_numpy(xyz).to(device=device, dtype=torch.float32)
     res = evaluation.evaluate_sequence(mapper, info.camera(), source, poses=poses, args=args, gt_points=gt_points,
-                                       dist_thres=[0.03], transform=transform, sample_nums=1_000_000)
+                                       dist_thres=[0.03], transform=transform, sample_nums=1_000_000, rec_points=rec_points)
     out = os.path.join(args.save_path, f"statis_frame_{mapper.time}_iter_{test_iter}.csv")
     iof.save_metrics_csv(out, res["rows"])
     m = res["mean"]
@@ -224,7 +258,7 @@ def cmd_metric(opts) -> int:
     return 0
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m rtg_slam_amd", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="cmd", required=True)
     s = sub.add_parser("slam", help="run SLAM on a dataset (slam.py)")
@@ -233,6 +267,8 @@ def main(argv=None) -> int:
     s.add_argument("--device", default="cuda:0")
     s.add_argument("--io-workers", type=int, default=None)
     s.add_argument("--overwrite", action="store_true", help="replace a non-empty save_path")
+    s.add_argument("--pcd-densify", action="store_true",
+                   help="when the config sets pcd_densify, write save_model/pcd_densify.ply after the run (slam.py:146-150)")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)
@@ -241,7 +277,11 @@ def main(argv=None) -> int:
     m.add_argument("--eval-merge", action="store_true")
     m.add_argument("--device", default="cuda:0")
     m.add_argument("--io-workers", type=int, default=None)
-    opts = p.parse_args(argv)
+    return p
+
+
+def main(argv=None) -> int:
+    opts = build_parser().parse_args(argv)
     return cmd_slam(opts) if opts.cmd == "slam" else cmd_metric(opts)
 
 

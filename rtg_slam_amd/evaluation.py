@@ -181,11 +181,12 @@ def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, mi
 
 def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_points=None, dist_thres: Sequence[float] = (0.03,),
                       transform=None, sample_nums: int = 1_000_000, generator: Optional[torch.Generator] = None,
-                      with_ms_ssim: bool = True) -> Dict:
+                      with_ms_ssim: bool = True, rec_points: Optional[torch.Tensor] = None) -> Dict:
     """metric.py:137-219 over a finished map.  `stream` yields (depth [H,W] metres, colour [3,H,W], GT c2w) as run_sequence's
     does; frame i is rendered at poses[i] (the estimated trajectory, e.g. tracker.pose_es) or, without poses, at its GT pose,
     by a Renderer whose opaque threshold is args.renderer_opaque_threshold_eval (metric.py:138).  With gt_points, the
-    reconstruction metrics of the map's Gaussian centres join the last frame's row, as metric.py runs them there.
+    reconstruction metrics join the last frame's row, as metric.py runs them there: of rec_points [P,3] on the device (the
+    points of pcd_densify.ply, metric.py:156-163) when given, else of the map's Gaussian centres.
     Returns {"rows": one dict per frame (with "frame" and "iter"), "mean": the mean row of metric.py:205-211}."""
     from .mapping import Frame
     from .render import Renderer
@@ -205,6 +206,6 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
         rows.append(row)
     if gt_points is not None and rows:
         with torch.no_grad():
-            rows[-1].update(eval_pcd(mapper.opt.gaussian_data("all")["xyz"], gt_points, dist_thres, transform, sample_nums,
-                                     generator))
+            rec = mapper.opt.gaussian_data("all")["xyz"] if rec_points is None else rec_points
+            rows[-1].update(eval_pcd(rec, gt_points, dist_thres, transform, sample_nums, generator))
     return {"rows": rows, "mean": metrics_mean_row(rows)}

@@ -8,6 +8,9 @@
   * trajectories     `save_traj/pose_es.npy`, `pose_gt.npy` - float [n,4,4] camera-to-world: tracker.py:352-362;
   * `performance.json` - {"tracking", "mapping": mean seconds per frame, "fps": 1 / mapping, "gpu_memory": MB}:
     utils/monitor.py:22-50;
+  * densified point clouds  `save_model/pcd_densify.ply` - binary little-endian PLY, one `vertex` element of float64
+    `x y z nx ny nz`, the layout of Open3D's write_point_cloud (slam.py:146-150); read back as o3d.io.read_point_cloud
+    reads it for eval_pcd (SLAM/eval.py:160), and model files likewise;
   * ground-truth meshes (PLY, ascii or binary little-endian; triangles and quads) and the surface sampling eval_pcd
     applies to them (trimesh.load / trimesh.sample.sample_surface, SLAM/eval.py:155-170), and the per-frame metrics
     table `statis_frame_*_iter_*.csv` with its mean row (metric.py:203-219, written there by pandas).
@@ -19,6 +22,7 @@ from __future__ import annotations
 import csv
 import json
 import math
+import mmap
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -350,6 +354,98 @@ def sample_mesh_surface(vertices, faces, n: int, seed: int = 0):
     uv[flip] = 1.0 - uv[flip]
     pts = a[face] + uv[:, :1] * (b[face] - a[face]) + uv[:, 1:] * (c[face] - a[face])
     return pts, face
+
+
+POINT_CLOUD_COLUMNS = ("x", "y", "z", "nx", "ny", "nz")
+
+
+def point_cloud_header(n: int) -> bytes:
+    """The header Open3D's write_point_cloud gives a binary cloud with normals and no colours (as far as it is known
+    without Open3D: not compared byte for byte against a file Open3D wrote)."""
+    lines = ["ply", "format binary_little_endian 1.0", "comment Created by Open3D", f"element vertex {int(n)}"]
+    lines += [f"property double {c}" for c in POINT_CLOUD_COLUMNS] + ["end_header"]
+    return ("\n".join(lines) + "\n").encode("ascii")
+
+
+class PointCloudPlyWriter:
+    """Streams `n` float64 records (x y z nx ny nz) into a point-cloud PLY in pieces: the header first, then write(rows)
+    with [m,6] float64 arrays (or anything exposing that buffer) until n rows are in.  close() checks the count."""
+
+    def __init__(self, path: str, n: int):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.path, self.n, self.written = path, int(n), 0
+        self._f = open(path, "wb")
+        self._f.write(point_cloud_header(self.n))
+
+    def write(self, rows) -> None:
+        a = np.asarray(rows)
+        if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError("PointCloudPlyWriter.write: rows must be float64 [m, 6]")
+        if self.written + a.shape[0] > self.n:
+            raise ValueError(f"PointCloudPlyWriter.write: more than the {self.n} rows of the header")
+        self._f.write(memoryview(np.ascontiguousarray(a)).cast("B"))
+        self.written += a.shape[0]
+
+    def close(self) -> None:
+        if self._f is None:
+            return
+        self._f.close()
+        self._f = None
+        if self.written != self.n:
+            raise ValueError(f"{self.path}: {self.written} rows written, the header says {self.n}")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self._f is not None:
+            self._f.close()
+            self._f = None
+
+
+def save_point_cloud_ply(path: str, xyz, normals) -> int:
+    """o3d.io.write_point_cloud of a cloud with normals: float64 records x y z nx ny nz.  An empty cloud writes no file (Open3D
+    refuses to write one, we believe).  -> the number of points."""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    nrm = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    if xyz.shape != nrm.shape:
+        raise ValueError("save_point_cloud_ply: xyz and normals differ in shape")
+    if xyz.shape[0] == 0:
+        return 0
+    with PointCloudPlyWriter(path, xyz.shape[0]) as w:
+        w.write(np.concatenate([xyz, nrm], axis=1))
+    return xyz.shape[0]
+
+
+def load_point_cloud_ply(path: str):
+    """o3d.io.read_point_cloud as eval_pcd uses it (SLAM/eval.py:160): the `vertex` element's x y z and, when all three are
+    present, nx ny nz, as float or double in any property order, ascii or binary little-endian; other properties and elements
+    are skipped.  A binary body is memory-mapped, not read into memory first.  -> (xyz float64 [N,3], normals float64 [N,3]
+    or None).  Reads pcd_densify.ply and model files alike."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        pos = f.tell()
+        if fmt == "ascii":
+            tokens, pos = f.read().decode("ascii").split(), 0
+            read = lambda count, props, pos: _ply_ascii_element(tokens, pos, count, props)
+        else:
+            buf = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            read = lambda count, props, pos: _ply_binary_element(buf, pos, count, props)
+    for name, count, props in elements:
+        cols, pos = read(count, props, pos)
+        if name != "vertex":
+            continue
+        names = [n for n, _ in props]
+        if not all(c in names for c in ("x", "y", "z")):
+            raise ValueError(f"{path}: vertex element without x, y, z")
+        xyz = np.stack([np.asarray(cols[c], dtype=np.float64) for c in ("x", "y", "z")], axis=1)
+        nrm = None
+        if all(c in names for c in ("nx", "ny", "nz")):
+            nrm = np.stack([np.asarray(cols[c], dtype=np.float64) for c in ("nx", "ny", "nz")], axis=1)
+        return xyz, nrm                         # the copies above release the mapping
+    raise ValueError(f"{path}: no vertex element")
 
 
 def _is_number(x) -> bool:

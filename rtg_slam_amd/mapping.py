@@ -980,6 +980,42 @@ class Mapping:
                 iof.merge_ply(path + tag + ".ply", path + "_stable" + tag + ".ply", path + "_merge" + tag + ".ply",
                               include_confidence=with_conf)
 
+    def save_densified(self, path: str, sigma: int = 1, circle_num: int = 30, levels: int = 5,
+                       generator: Optional[torch.Generator] = None, chunk_points: int = 1 << 21) -> int:
+        """slam.py:146-150 with pcd_densify: stable_pointcloud.densify(sigma, circle_num, levels) (gaussian_pointcloud.py:53-116)
+        written as o3d.io.write_point_cloud writes it (io_formats.PointCloudPlyWriter).  theta comes from
+        slam_ops.densify_theta(circle_num, generator); the points from the rtgs_densify_discs kernel over the stable rows, in
+        chunks of about chunk_points points, each copied to pinned memory while the previous one is written, so that host
+        and device memory stay bounded whatever the map's size.  An empty stable cloud writes no file.  -> points written."""
+        from . import io_formats as iof, slam_ops as so
+        cos, sin = (t.to(self.device) for t in so.densify_theta(circle_num, generator))
+        K = int(sigma) * int(levels) * int(circle_num)
+        gd = self.opt.gaussian_data("stable")
+        P = int(gd["xyz"].shape[0])
+        if P == 0 or K == 0:
+            return 0
+        rows = max(1, int(chunk_points) // K)
+        cap = min(P, rows) * K
+        bufs = [(torch.empty(cap, 6, dtype=torch.float64, device=self.device),
+                 torch.empty(cap, 6, dtype=torch.float64, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
+        stream = torch.cuda.current_stream(self.device)
+        with iof.PointCloudPlyWriter(path, P * K) as w:
+            pending = None
+            for i, r0 in enumerate(range(0, P, rows)):
+                r1 = min(P, r0 + rows)
+                d, h, ev = bufs[i % 2]
+                n = (r1 - r0) * K
+                so.densify_discs(gd["xyz"], gd["scales"], gd["rotations"], cos, sin, sigma, levels, r0, r1, out=d)
+                h[:n].copy_(d[:n], non_blocking=True)
+                ev.record(stream)
+                if pending is not None:
+                    pending[0].synchronize()
+                    w.write(pending[1][:pending[2]].numpy())
+                pending = (ev, h, n)
+            pending[0].synchronize()
+            w.write(pending[1][:pending[2]].numpy())
+        return P * K
+
     def get_render_output(self, frame):
         out = self._render(frame, "all")
         self.model_map = {

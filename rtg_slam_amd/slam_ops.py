@@ -7,6 +7,7 @@ and signatures so that its callers bind unchanged:
     accumulate_gaussian_error (also cuda_utils._C.accumulate_gaussian_error) mapper.py:15, 541-565
     bilateralFilter_torch / frame_preprocess / sample_pixels               SLAM/utils.py:550-589, tracker.py:104-131,
                                                                            SLAM/utils.py:141-183
+    densify_theta / densify_discs                                          gaussian_pointcloud.py:53-116 (densify)
 torch supplies device memory and the current HIP stream; there is no CPU path."""
 from __future__ import annotations
 
@@ -472,3 +473,45 @@ def sample_pixels(vertex_map, normal_map, color_map, uniform_sample_num, select_
     pick = idx[:n_cand][torch.randperm(n_cand, device=dev, generator=generator)[:n]].long()
     return (vertex_map.reshape(-1, 3)[pick].view(n, 3), normal_map.reshape(-1, 3)[pick].view(n, 3),
             color_map.reshape(-1, 3)[pick].view(n, 3))
+
+
+def densify_theta(circle_num: int, generator: Optional[torch.Generator] = None):
+    """The angles of GaussianPointCloud.densify (gaussian_pointcloud.py:65): theta = torch.rand(1, C) * pi * 2 in float32 on
+    the CPU, drawn from `generator` (the reference draws from the global RNG).  -> (cos theta, sin theta), float32 [C] on the
+    CPU, as torch computes them there; densify_discs takes these tables and does not recompute them."""
+    theta = torch.rand(1, int(circle_num), generator=generator) * torch.pi * 2
+    return torch.cos(theta)[0], torch.sin(theta)[0]
+
+
+def densify_discs(xyz: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                  sigma: int = 1, levels: int = 5, row_begin: int = 0, row_end: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GaussianPointCloud.densify's points (gaussian_pointcloud.py:53-116) of rows [row_begin, row_end) of xyz [P,3], the
+    activated scales [P,3] and the normalised rotations [P,4] (gaussian_data("stable")): K = sigma * levels * len(cos) points
+    per Gaussian on concentric ellipses, Gaussian-major.  -> float64 [(row_end - row_begin) K, 6] on the device, each row
+    x y z nx ny nz (the record of pcd_densify.ply); written into `out` (its first rows) when given."""
+    lib, dev = _lib.load(), _dev(xyz)
+    P = int(xyz.shape[0])
+    r0, r1 = int(row_begin), P if row_end is None else int(row_end)
+    if not (0 <= r0 <= r1 <= P) or scales.shape[0] != P or rotations.shape[0] != P:
+        raise ValueError("rtg_slam_amd.slam_ops.densify_discs: bad row range or row counts")
+    C_ = int(cos.numel())
+    if int(sin.numel()) != C_:
+        raise ValueError("rtg_slam_amd.slam_ops.densify_discs: cos and sin tables differ in length")
+    K = int(sigma) * int(levels) * C_
+    n = (r1 - r0) * K
+    if out is None:
+        out = torch.empty(n, 6, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n * 6 or out.device != dev:
+        raise ValueError("rtg_slam_amd.slam_ops.densify_discs: out must be a contiguous float64 tensor of >= n * 6 values")
+    out = out.view(-1)[:n * 6].view(n, 6)
+    x = xyz.float().contiguous()
+    s = scales.float().contiguous()
+    q = rotations.float().contiguous()
+    c = cos.to(device=dev, dtype=torch.float32).contiguous()
+    sn = sin.to(device=dev, dtype=torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_densify_discs(_p(x), _p(s), _p(q), r0, r1, _p(c), _p(sn), int(sigma), int(levels), C_, _p(out),
+                                    _stream(dev))
+    _lib.check(rc, "rtgs_densify_discs")
+    return out
