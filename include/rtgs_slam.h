@@ -18,6 +18,8 @@
  *   rtgs_ingest_rgbd         the pixel arithmetic between the dataset files and the tracker: readCameras' depth scaling
  *                            (scene/dataset_readers.py:848-932), PILtoTorch (utils/general_utils.py:43-49) and map_preprocess's
  *                            * 255 (SLAM/multiprocess/tracker.py:97-101)
+ *   rtgs_ingest_rgbd_resized the same with loadCam's resize in between (utils/camera_utils.py:22-74: PIL BILINEAR on the u8
+ *                            colour, PIL NEAREST on the float depth), for resolution_scales other than 1
  *   rtgs_densify_discs       GaussianPointCloud.densify (SLAM/gaussian_pointcloud.py:53-116), the points slam.py:146-150
  *                            writes to save_model/pcd_densify.ply when the config sets pcd_densify
  */
@@ -253,6 +255,29 @@ int rtgs_eval_nn_stats(const float* dist2, int32_t N, const double* thresholds, 
  * Returns -1 on a bad shape, channel count, crop or scale (depth_scale must be > 0). */
 int rtgs_ingest_rgbd(const uint16_t* depth_raw, const uint8_t* color_raw, int32_t Hd, int32_t Wd, int32_t channels, int32_t crop,
                      float depth_scale, float* depth_out, float* color_out, void* stream);
+
+/* The same frame resized to Ho x Wo after the crop, as loadCam (utils/camera_utils.py:22-74) resizes it with PIL, in the same
+ * single launch and bit-identical to that chain:
+ *   colour  Image.resize((Wo, Ho), BILINEAR) on the cropped u8 image, then / 255.  Pillow's 8-bit resampler in integers: a
+ *           horizontal pass, then a vertical pass on the rounded u8 result of the first; per pass
+ *           out = clip_0..255((2^21 + sum_j coeff[j] * src[start + j]) >> 22).  A 4-channel image is resampled as
+ *           Image.resize resamples RGBA: premultiplied by alpha before, divided by the resampled alpha after.
+ *   depth   Image.resize((Wo, Ho), NEAREST) on f32(raw) / depth_scale: the pick of one source pixel, then / 255 * 255.
+ * `tables` (device, int32, tables_len values) holds what depends on (cropped size, output size) only, computed on the host in
+ * float64 as Pillow computes it (rtg_slam_amd.datasets.resample_tables / nearest_indices), in this order:
+ *   x_start[Wo] x_len[Wo] x_near[Wo] y_start[Ho] y_len[Ho] y_near[Ho] x_coeff[Wo * x_ksize] y_coeff[Ho * y_ksize]
+ * with start / len the source window of an output column or row (within the CROPPED image), coeff its 22-bit fixed-point
+ * weights (zero beyond len), near the source index of the nearest pick, x_ksize / y_ksize the longest window.  Any ratio,
+ * enlarging included; an output size equal to the cropped size works but rtgs_ingest_rgbd is the path for it.  The
+ * horizontally resampled rows a tile's vertical windows cover are staged in LDS (no intermediate image in global memory);
+ * the tile height shrinks from 16 rows to 1 as the reduction factor grows (and to 2 for outputs of few tiles).  Returns -1
+ * on what rtgs_ingest_rgbd rejects, on a non-positive output size or window length, on a tables_len that is not
+ * 3 Wo + 3 Ho + Wo x_ksize + Ho y_ksize, and when the window of a single output row does not fit 64 KiB of LDS (y_ksize
+ * above ~250); windows are never truncated.
+ * Indices read from `tables` are clamped to the buffers they address. */
+int rtgs_ingest_rgbd_resized(const uint16_t* depth_raw, const uint8_t* color_raw, int32_t Hd, int32_t Wd, int32_t channels,
+                             int32_t crop, float depth_scale, int32_t Ho, int32_t Wo, const int32_t* tables, int64_t tables_len,
+                             int32_t x_ksize, int32_t y_ksize, float* depth_out, float* color_out, void* stream);
 
 /* ---- densification (SLAM/gaussian_pointcloud.py:53-116, with get_normal / get_plane :539-571) -----------------------
  * Rows [row_begin, row_end) of the stable cloud: xyz [*,3], the activated scales [*,3] (exp of the raw scaling) and the

@@ -6,7 +6,9 @@
 `slam` writes, under the config's save_path: config.yaml (the merged config), save_model/frame_XXXX/iter_XXXX*.ply (at frame 0,
 every save_step frames and after the final global optimisation), save_traj/pose_es.npy, pose_gt.npy and ate.txt (the ATE in
 cm of every prefix of the trajectory), performance.json, eval_metric/slam_eval.csv (the in-loop evaluation rows) and
-run_report.json (run_sequence's report plus the I/O statistics of the frame source).  With --pcd-densify and a config that
+run_report.json (run_sequence's report plus the I/O statistics of the frame source and the frame size).  With
+`resolution_scales: [S]` in the config, or --resolution-scale S (which overrides it and is written into config.yaml), both
+commands run on frames resized to 1/S of the decoded size as the reference's loadCam resizes them, on the device.  With --pcd-densify and a config that
 sets pcd_densify, it then writes save_model/pcd_densify.ply: 150 points on concentric ellipses around every stable Gaussian
 (Mapping.save_densified, slam.py:146-150), theta drawn from a generator seeded with the config's seed.  `metric` evaluates a
 saved model over the same frames and writes statis_frame_F_iter_I.csv; when the config sets pcd_densify and
@@ -74,12 +76,21 @@ def _dump_config(args, path: str) -> None:
         yaml.safe_dump(d, f, sort_keys=False)
 
 
+def _apply_resolution_scale(args, opts) -> None:
+    """--resolution-scale S overrides the config's resolution_scales[0] (loadCam's resolution_scale)."""
+    if opts.resolution_scale is not None:
+        scales = list(getattr(args, "resolution_scales", None) or [1.0])
+        scales[0] = float(opts.resolution_scale)
+        args.resolution_scales = scales
+
+
 def cmd_slam(opts) -> int:
     import torch
     from . import config, datasets, io_formats as iof
     from .mapping import Mapping
     from .slam import run_sequence
     args = config.load_config(opts.config)
+    _apply_resolution_scale(args, opts)
     if opts.frames is not None:
         args.frame_num = int(opts.frames)
     save_path = args.save_path
@@ -100,7 +111,10 @@ def cmd_slam(opts) -> int:
     info = datasets.load_dataset(args)
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
     cam = info.camera()
-    log(f"{info.type} {info.source_path}: {len(info)} frames {info.width}x{info.height}, {source.io_workers} io workers")
+    size = f"{info.width}x{info.height}"
+    if info.resized:
+        size += f" (resized on the device from {info.crop_width}x{info.crop_height}, resolution scale {info.resolution_scale:g})"
+    log(f"{info.type} {info.source_path}: {len(info)} frames {size}, {source.io_workers} io workers")
     mapper = Mapping(args, device)
     save_step = int(getattr(args, "save_step", 2000))
     loop = {"t0": None, "t_last": None}
@@ -137,7 +151,8 @@ def cmd_slam(opts) -> int:
     loop_s = loop["t_last"] - loop["t0"]
     report.update(io_wait_s_mean=st["io_wait_s_mean"], io_wait_s=st["io_wait_s"], decode_ms_per_frame=st["decode_ms_per_frame"],
                   io_workers=st["io_workers"], prefetch=st["prefetch"], h2d_bytes_per_frame=st["h2d_bytes_per_frame"],
-                  wall_fps_including_io=n / loop_s if loop_s > 0 else None, ate_cm=ates[-1])
+                  wall_fps_including_io=n / loop_s if loop_s > 0 else None, ate_cm=ates[-1], width=st["width"],
+                  height=st["height"], resolution_scale=st["resolution_scale"])
     with open(os.path.join(save_path, "run_report.json"), "w") as f:
         json.dump(report, f, indent=1, default=float)
     log(f"{n} frames: fps {report['fps']:.2f} (1 / mapping), wall fps with I/O {report['wall_fps_including_io']:.2f}, "
@@ -212,6 +227,7 @@ def cmd_metric(opts) -> int:
     import torch
     from . import config, datasets, evaluation, io_formats as iof
     args = config.load_config(opts.config)
+    _apply_resolution_scale(args, opts)
     device = torch.device(opts.device)
     torch.cuda.set_device(device)
     model_base = os.path.join(args.save_path, "save_model")
@@ -239,6 +255,7 @@ def cmd_metric(opts) -> int:
     args.frame_num = max_cams
     info = datasets.load_dataset(args)
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
+    log(f"evaluating at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
     gt_points, transform, rec_points = None, None, None
     if info.mesh_path and os.path.isfile(info.mesh_path):
         v, f = iof.load_mesh_ply(info.mesh_path)
@@ -267,6 +284,8 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--device", default="cuda:0")
     s.add_argument("--io-workers", type=int, default=None)
     s.add_argument("--overwrite", action="store_true", help="replace a non-empty save_path")
+    s.add_argument("--resolution-scale", type=float, default=None,
+                   help="overrides resolution_scales[0]: the frames are resized to 1/S of their size on the device (loadCam)")
     s.add_argument("--pcd-densify", action="store_true",
                    help="when the config sets pcd_densify, write save_model/pcd_densify.ply after the run (slam.py:146-150)")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
@@ -277,6 +296,8 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("--eval-merge", action="store_true")
     m.add_argument("--device", default="cuda:0")
     m.add_argument("--io-workers", type=int, default=None)
+    m.add_argument("--resolution-scale", type=float, default=None,
+                   help="overrides resolution_scales[0]; evaluate at the scale the map was built at (metric.py:131,177)")
     return p
 
 

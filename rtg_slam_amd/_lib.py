@@ -228,6 +228,8 @@ _SIGNATURES = {
     "rtgs_eval_nn_stats": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     # frame ingest
     "rtgs_ingest_rgbd": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),
+    "rtgs_ingest_rgbd_resized": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                          _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
     # densification
     "rtgs_densify_discs": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
 }

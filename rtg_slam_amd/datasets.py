@@ -16,12 +16,19 @@ No image is decoded there except the first depth's header (the frame size).
 tensors on the device, as run_sequence consumes them.  Decoding (PIL + numpy) runs on a pool of worker threads; each
 decoded frame's raw bytes (u16 depth, u8 colour: 6 B per pixel for RGB) go through a ring of pinned host buffers to the
 device on a dedicated stream, where one `rtgs_ingest_rgbd` launch turns them into the float maps, bit-identical to the
-reference's chain (include/rtgs_slam.h, "frame ingest").  Frames come out in dataset order."""
+reference's chain (include/rtgs_slam.h, "frame ingest").  Frames come out in dataset order.
+
+With `resolution_scales: [S]`, S != 1, the frames are resized after the crop as utils/camera_utils.py:22-74 (loadCam) resizes
+them: the raw frame still travels to the device, where one `rtgs_ingest_rgbd_resized` launch reproduces PIL's BILINEAR
+(colour) and NEAREST (depth) resize bit for bit from tables computed here in float64 (resample_tables, nearest_indices);
+`DatasetInfo.width / height / camera()` then describe the resized frames (resize_info)."""
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import glob
 import json
+import math
 import os
 import threading
 import time
@@ -51,7 +58,7 @@ class DatasetInfo:
     frames: List[FrameRecord]
     fx: float
     fy: float
-    cx: float                             # after the crop: cx - crop_edge
+    cx: float                             # after the crop: cx - crop_edge (and after the resize, when there is one)
     cy: float
     depth_scale: float
     crop_edge: int
@@ -59,14 +66,29 @@ class DatasetInfo:
     raw_width: int
     mesh_path: Optional[str] = None
     extra: dict = field(default_factory=dict)
+    resolution_scale: float = 1.0         # loadCam's resolution_scale; fx, fy, cx, cy describe the frames AFTER the resize
+    out_width: Optional[int] = None       # the size loadCam resizes the cropped frames to; None: the cropped size
+    out_height: Optional[int] = None
 
     @property
-    def height(self) -> int:
+    def crop_height(self) -> int:
         return self.raw_height - 2 * self.crop_edge
 
     @property
-    def width(self) -> int:
+    def crop_width(self) -> int:
         return self.raw_width - 2 * self.crop_edge
+
+    @property
+    def height(self) -> int:
+        return self.crop_height if self.out_height is None else int(self.out_height)
+
+    @property
+    def width(self) -> int:
+        return self.crop_width if self.out_width is None else int(self.out_width)
+
+    @property
+    def resized(self) -> bool:
+        return (self.width, self.height) != (self.crop_width, self.crop_height)
 
     def camera(self):
         from .synth import CameraSpec
@@ -266,9 +288,38 @@ def loadcam_size(width: int, height: int, resolution, resolution_scale: float = 
     return (int(width / scale), int(height / scale))
 
 
+def resized_intrinsics(fx: float, fy: float, cx: float, cy: float, width: int, height: int, out_width: int, out_height: int,
+                       resolution_scale: float):
+    """The intrinsics the reference gives a width x height camera whose frames loadCam resizes to out_width x out_height:
+    the focal lengths go through the field of view of the cropped image (readCameras :908-909 focal2fov, scene/cameras.py
+    fov2focal at the new size), cx and cy are divided by resolution_scale (camera_utils.py:69-70)."""
+    fov_x = 2 * math.atan(width / (2 * fx))
+    fov_y = 2 * math.atan(height / (2 * fy))
+    return (out_width / (2 * math.tan(fov_x / 2)), out_height / (2 * math.tan(fov_y / 2)),
+            cx / resolution_scale, cy / resolution_scale)
+
+
+def resize_info(info: DatasetInfo, resolution_scale: float, resolution=1) -> DatasetInfo:
+    """`info` (at its cropped size) with loadCam's resize by `resolution_scale` applied: output size and intrinsics.
+    `resolution` must be one that by itself keeps the size; it only selects loadCam's rounding (round() for 1, int() for
+    -1 or the frame width).  Scale 1 returns `info` itself."""
+    s = float(resolution_scale)
+    if not s > 0 or info.resized:
+        raise ValueError(f"rtg_slam_amd.datasets: resolution scale {resolution_scale!r} (> 0 expected, on an unresized dataset)")
+    W, H = info.crop_width, info.crop_height
+    Wo, Ho = loadcam_size(W, H, resolution, s)
+    if Wo <= 0 or Ho <= 0:
+        raise ValueError(f"rtg_slam_amd.datasets: resolution scale {s} leaves nothing of the {W}x{H} frames")
+    if (Wo, Ho) == (W, H) and s == 1.0:
+        return info
+    fx, fy, cx, cy = resized_intrinsics(info.fx, info.fy, info.cx, info.cy, W, H, Wo, Ho, s)
+    return dataclasses.replace(info, fx=fx, fy=fy, cx=cx, cy=cy, resolution_scale=s, out_width=int(Wo), out_height=int(Ho))
+
+
 def load_dataset(args) -> DatasetInfo:
     """The reader of args.type over args.source_path with args.frame_start / frame_num / frame_step (scene/__init__.py:25-68).
-    Rejects eval: true, and any resolution / resolution_scales that would make loadCam resize the frames."""
+    args.resolution_scales[0] > 0 is loadCam's resolution_scale: the frames are resized on the device and the intrinsics
+    follow (resize_info).  Rejects eval: true, and any `resolution` that by itself would make loadCam resize the frames."""
     if bool(getattr(args, "eval", False)):
         raise ValueError("rtg_slam_amd.datasets: `eval: true` (train / test frame split) is not supported; no shipped config "
                          "sets it, and the reference's own eval path of the Ours reader is broken")
@@ -285,12 +336,16 @@ def load_dataset(args) -> DatasetInfo:
     else:
         raise ValueError(f"rtg_slam_amd.datasets: unknown dataset type {typ!r}")
     scales = list(getattr(args, "resolution_scales", [1.0]) or [1.0])
-    want = loadcam_size(info.width, info.height, getattr(args, "resolution", 1), scales[0])
+    resolution = getattr(args, "resolution", 1)
+    want = loadcam_size(info.width, info.height, resolution, 1.0)
     if tuple(want) != (info.width, info.height):
-        raise ValueError(f"rtg_slam_amd.datasets: resolution {getattr(args, 'resolution', 1)} / resolution_scales {scales} "
-                         f"would resize the {info.width}x{info.height} frames to {want[0]}x{want[1]}; only settings that "
-                         "keep the decoded size are supported")
-    return info
+        raise ValueError(f"rtg_slam_amd.datasets: resolution {resolution} would resize the {info.width}x{info.height} frames "
+                         f"to {want[0]}x{want[1]}, and the reference divides cx, cy by resolution_scale only, never by "
+                         "`resolution`: the resized camera would be wrong.  Use resolution_scales: [S] (or "
+                         "--resolution-scale S) to run at a reduced size")
+    if not float(scales[0]) > 0:
+        raise ValueError(f"rtg_slam_amd.datasets: resolution_scales {scales}: the first entry must be > 0")
+    return resize_info(info, float(scales[0]), resolution)
 
 
 def read_pose_t0(args) -> np.ndarray:
@@ -343,10 +398,138 @@ def reference_chain(depth_u16: np.ndarray, color_u8: np.ndarray, depth_scale: fl
     return d_t, c_t
 
 
+# ---------------------------------------------------------------------------------------------------------------- resize
+RESAMPLE_BITS = 22                        # Pillow's 8-bit resampler: coefficients in fixed point with 32 - 8 - 2 fractional bits
+
+
+def resample_tables(in_size: int, out_size: int):
+    """Pillow's BILINEAR coefficients for resampling one axis of in_size pixels to out_size (its precompute_coeffs and
+    normalize_coeffs_8bpc), in float64 as Pillow computes them in C doubles: -> (start int32 [out], length int32 [out],
+    coeff int32 [out, ksize]).  Output index i is sum(coeff[i, :length[i]] * src[start[i] : start[i] + length[i]]); the
+    triangle filter's support is widened by the reduction factor (1 when enlarging), the weights are normalised to sum 1,
+    then rounded to RESAMPLE_BITS fractional bits; coeff is zero beyond length."""
+    n_in, n_out = int(in_size), int(out_size)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"rtg_slam_amd.datasets: resample_tables({in_size}, {out_size}): sizes must be positive")
+    scale = n_in / n_out
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    ss = 1.0 / filterscale
+    start = (center - support + 0.5).astype(np.int64)              # C's (int): truncation
+    start[start < 0] = 0
+    stop = (center + support + 0.5).astype(np.int64)
+    stop[stop > n_in] = n_in
+    length = stop - start
+    k = np.zeros((n_out, ksize), dtype=np.float64)
+    ww = np.zeros(n_out, dtype=np.float64)
+    for x in range(ksize):                                         # ww accumulates in x order, as the C loop does
+        w = np.abs(((x + start).astype(np.float64) - center + 0.5) * ss)
+        w = np.where((w < 1.0) & (x < length), 1.0 - w, 0.0)
+        k[:, x] = w
+        ww = ww + w
+    nz = ww != 0.0
+    k[nz] = k[nz] / ww[nz, None]
+    coeff = (0.5 + k * float(1 << RESAMPLE_BITS)).astype(np.int64)  # the bilinear weights are never negative
+    coeff[np.arange(ksize)[None, :] >= length[:, None]] = 0
+    return start.astype(np.int32), length.astype(np.int32), np.ascontiguousarray(coeff.astype(np.int32))
+
+
+def nearest_indices(in_size: int, out_size: int) -> np.ndarray:
+    """The source index Pillow's NEAREST resize picks for every output index (its affine scaling walks the source coordinate
+    by repeated addition in a C double, starting half a step in): int32 [out]."""
+    n_in, n_out = int(in_size), int(out_size)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"rtg_slam_amd.datasets: nearest_indices({in_size}, {out_size}): sizes must be positive")
+    step = n_in / n_out
+    pos = np.empty(n_out, dtype=np.float64)
+    xo = step * 0.5
+    for i in range(n_out):
+        pos[i] = xo
+        xo += step
+    return np.clip(pos.astype(np.int64), 0, n_in - 1).astype(np.int32)
+
+
+def _resample_axis0(a: np.ndarray, tables) -> np.ndarray:
+    start, length, coeff = tables
+    acc = np.full((len(start),) + a.shape[1:], 1 << (RESAMPLE_BITS - 1), dtype=np.int64)
+    src = a.astype(np.int64)
+    for j in range(coeff.shape[1]):
+        idx = np.minimum(start.astype(np.int64) + j, a.shape[0] - 1)          # beyond `length` the coefficient is 0
+        acc += coeff[:, j].astype(np.int64).reshape((-1,) + (1,) * (a.ndim - 1)) * src[idx]
+    return np.clip(acc >> RESAMPLE_BITS, 0, 255).astype(np.uint8)
+
+
+def reference_resize(color_u8: np.ndarray, depth_f32, out_w: int, out_h: int):
+    """PIL's `resize((out_w, out_h), BILINEAR)` of a u8 [H,W,3|4] image and `resize((out_w, out_h), NEAREST)` of a [H,W] depth
+    image (either may be None), in numpy through resample_tables / nearest_indices: the arithmetic of
+    rtgs_ingest_rgbd_resized.  Colour: a horizontal pass, then a vertical pass on the rounded u8 result of the first; an
+    RGBA image is resampled with its colours premultiplied by alpha and divided by the resampled alpha afterwards, as
+    Image.resize does (modes RGBa / RGBA).  An image that already has the size is returned as it is."""
+    color = depth = None
+    if color_u8 is not None:
+        a = np.asarray(color_u8)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+            raise ValueError("rtg_slam_amd.datasets.reference_resize: colour u8 [H,W,3|4] expected")
+        if (a.shape[1], a.shape[0]) == (out_w, out_h):
+            color = a.copy()
+        else:
+            if a.shape[2] == 4:
+                t = a[..., :3].astype(np.int64) * a[..., 3:4].astype(np.int64) + 128
+                a = np.concatenate([(((t >> 8) + t) >> 8).astype(np.uint8), a[..., 3:4]], axis=2)
+            h = _resample_axis0(a.transpose(1, 0, 2), resample_tables(a.shape[1], out_w)).transpose(1, 0, 2)
+            color = _resample_axis0(h, resample_tables(a.shape[0], out_h))
+            if color.shape[2] == 4:
+                al = color[..., 3:4].astype(np.int64)
+                un = np.minimum(255 * color[..., :3].astype(np.int64) // np.maximum(al, 1), 255)
+                color[..., :3] = np.where((al == 0) | (al == 255), color[..., :3], un).astype(np.uint8)
+    if depth_f32 is not None:
+        d = np.asarray(depth_f32)
+        if d.ndim != 2:
+            raise ValueError("rtg_slam_amd.datasets.reference_resize: depth [H,W] expected")
+        depth = d.copy() if (d.shape[1], d.shape[0]) == (out_w, out_h) else \
+            d[nearest_indices(d.shape[0], out_h)[:, None], nearest_indices(d.shape[1], out_w)[None, :]]
+    return color, depth
+
+
 # ---------------------------------------------------------------------------------------------------------------- ingest
-def ingest(depth_raw: torch.Tensor, color_raw: torch.Tensor, depth_scale: float, crop: int = 0, stream=None):
+@dataclass
+class ResizeTables:
+    """What rtgs_ingest_rgbd_resized reads per (cropped size, output size): the packed int32 buffer of include/rtgs_slam.h
+    (x_start x_len x_near y_start y_len y_near x_coeff y_coeff), on the host (`packed`) and, after to(), on a device."""
+    in_size: tuple                        # (W, H) after the crop
+    out_size: tuple                       # (Wo, Ho)
+    x_ksize: int
+    y_ksize: int
+    packed: np.ndarray
+    device_buf: Optional[torch.Tensor] = None
+
+    def expected_len(self) -> int:
+        Wo, Ho = self.out_size
+        return 3 * Wo + 3 * Ho + Wo * self.x_ksize + Ho * self.y_ksize
+
+    def to(self, device) -> "ResizeTables":
+        return dataclasses.replace(self, device_buf=torch.from_numpy(self.packed).to(device))
+
+
+def resize_tables(in_size, out_size) -> ResizeTables:
+    """The tables of resample_tables / nearest_indices for resizing (W, H) frames to (Wo, Ho), packed for the kernel."""
+    (W, H), (Wo, Ho) = (int(v) for v in in_size), (int(v) for v in out_size)
+    xs, xl, xk = resample_tables(W, Wo)
+    ys, yl, yk = resample_tables(H, Ho)
+    packed = np.concatenate([xs, xl, nearest_indices(W, Wo), ys, yl, nearest_indices(H, Ho), xk.reshape(-1),
+                             yk.reshape(-1)]).astype(np.int32)
+    return ResizeTables((W, H), (Wo, Ho), int(xk.shape[1]), int(yk.shape[1]), np.ascontiguousarray(packed))
+
+
+def ingest(depth_raw: torch.Tensor, color_raw: torch.Tensor, depth_scale: float, crop: int = 0, stream=None, out_size=None,
+           tables: Optional[ResizeTables] = None):
     """rtgs_ingest_rgbd on the device: depth_raw u16 [Hd,Wd] (int16 / uint16 storage), color_raw u8 [Hd,Wd,3|4] ->
-    (depth [H,W,1] metres, colour [3,H,W]) float32, enqueued on `stream` (default: the current stream)."""
+    (depth [H,W,1] metres, colour [3,H,W]) float32, enqueued on `stream` (default: the current stream).  With an
+    `out_size` (Wo, Ho) other than the cropped size, rtgs_ingest_rgbd_resized: the frame resized after the crop as loadCam
+    does with PIL, -> (depth [Ho,Wo,1], colour [3,Ho,Wo]); `tables` (resize_tables(...).to(device), built for these very
+    sizes) spares computing and uploading them per call."""
     from . import _lib
     if not (depth_raw.is_cuda and color_raw.is_cuda):
         raise RuntimeError("rtg_slam_amd.datasets.ingest: tensors must live on a HIP device; this build has no CPU path.")
@@ -358,17 +541,45 @@ def ingest(depth_raw: torch.Tensor, color_raw: torch.Tensor, depth_scale: float,
     if crop < 0 or H <= 0 or W <= 0:
         raise ValueError(f"rtg_slam_amd.datasets.ingest: crop {crop} does not fit {Hd}x{Wd}")
     dev = depth_raw.device
+    resized = False
+    if out_size is not None:
+        Wo, Ho = int(out_size[0]), int(out_size[1])
+        if Wo <= 0 or Ho <= 0:
+            raise ValueError(f"rtg_slam_amd.datasets.ingest: out_size {tuple(out_size)} must be positive")
+        resized = (Wo, Ho) != (W, H)
+    if resized:
+        if tables is None:
+            tables = resize_tables((W, H), (Wo, Ho))
+        if tuple(tables.in_size) != (W, H) or tuple(tables.out_size) != (Wo, Ho):
+            raise ValueError(f"rtg_slam_amd.datasets.ingest: tables for {tables.in_size} -> {tables.out_size}, frame "
+                             f"{(W, H)} -> {(Wo, Ho)}")
+        if tables.device_buf is None or tables.device_buf.device != dev:
+            tables = tables.to(dev)
+        buf = tables.device_buf
+        if buf.dtype != torch.int32 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() != tables.expected_len():
+            raise ValueError(f"rtg_slam_amd.datasets.ingest: resize tables must be {tables.expected_len()} contiguous int32 "
+                             f"values, got {buf.dtype} {tuple(buf.shape)}")
+    else:
+        Wo, Ho = W, H
     st = torch.cuda.current_stream(dev) if stream is None else stream
     dr, cr = depth_raw.contiguous(), color_raw.contiguous()
     with torch.cuda.stream(st):
-        depth = torch.empty(H, W, 1, dtype=torch.float32, device=dev)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        depth = torch.empty(Ho, Wo, 1, dtype=torch.float32, device=dev)
+        color = torch.empty(3, Ho, Wo, dtype=torch.float32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        rc = lib.rtgs_ingest_rgbd(C.c_void_p(dr.data_ptr()), C.c_void_p(cr.data_ptr()), Hd, Wd, ch, int(crop),
-                                  float(depth_scale), C.c_void_p(depth.data_ptr()), C.c_void_p(color.data_ptr()),
-                                  C.c_void_p(st.cuda_stream))
-    _lib.check(rc, "rtgs_ingest_rgbd")
+        if resized:
+            rc = lib.rtgs_ingest_rgbd_resized(C.c_void_p(dr.data_ptr()), C.c_void_p(cr.data_ptr()), Hd, Wd, ch, int(crop),
+                                              float(depth_scale), Ho, Wo, C.c_void_p(buf.data_ptr()), int(buf.numel()),
+                                              int(tables.x_ksize), int(tables.y_ksize), C.c_void_p(depth.data_ptr()),
+                                              C.c_void_p(color.data_ptr()), C.c_void_p(st.cuda_stream))
+            if stream is not None:
+                buf.record_stream(st)
+        else:
+            rc = lib.rtgs_ingest_rgbd(C.c_void_p(dr.data_ptr()), C.c_void_p(cr.data_ptr()), Hd, Wd, ch, int(crop),
+                                      float(depth_scale), C.c_void_p(depth.data_ptr()), C.c_void_p(color.data_ptr()),
+                                      C.c_void_p(st.cuda_stream))
+    _lib.check(rc, "rtgs_ingest_rgbd_resized" if resized else "rtgs_ingest_rgbd")
     return depth, color
 
 
@@ -393,7 +604,9 @@ class _Slot:
 
 
 class FrameSource:
-    """Streams a `DatasetInfo`'s frames to `device` as (depth [H,W,1], colour [3,H,W], c2w float64 [4,4]).
+    """Streams a `DatasetInfo`'s frames to `device` as (depth [H,W,1], colour [3,H,W], c2w float64 [4,4]), H x W the
+    info's output size (the resize of a resized info happens in the ingest launch; the bytes copied per frame stay the raw
+    frame's).
 
     io_workers decode threads (default min(8, CPUs this process may use), at most 16); `prefetch` frames in flight at most
     (default io_workers + 2), one pinned staging slot each.  A worker decodes frame i, waits until the copy of the frame
@@ -401,7 +614,7 @@ class FrameSource:
     stream, the copy to the device, the ingest kernel and an event.  next() waits for frame i's worker (that wait is
     counted in `io_wait_s`), makes the consumer's current stream wait on the event, marks the tensors as used on that
     stream (record_stream) and hands frame i + prefetch to the pool.  prefetch = 1 with one worker runs the same code.
-    Statistics of the last pass: frames, io_wait_s, decode_s (summed over the workers), h2d_bytes."""
+    Statistics of the last pass: frames, io_wait_s, decode_s (summed over the workers), h2d_bytes; and the output size."""
 
     def __init__(self, info: DatasetInfo, device, io_workers: Optional[int] = None, prefetch: Optional[int] = None):
         self.info = info
@@ -418,6 +631,7 @@ class FrameSource:
         self._lock = threading.Lock()
         self._stream = None
         self._slots: List[_Slot] = []
+        self._tables: Optional[ResizeTables] = None
 
     def __len__(self) -> int:
         return len(self.info.frames)
@@ -427,6 +641,9 @@ class FrameSource:
             self._stream = torch.cuda.Stream(self.device)
             n_pix = self.info.raw_height * self.info.raw_width
             self._slots = [_Slot(n_pix, self.device) for _ in range(self.prefetch)]
+            if self.info.resized:                           # computed and uploaded once; every frame's launch reads them
+                self._tables = resize_tables((self.info.crop_width, self.info.crop_height),
+                                             (self.info.width, self.info.height)).to(self.device)
 
     def _work(self, i: int):
         info, rec = self.info, self.info.frames[i]
@@ -451,7 +668,7 @@ class FrameSource:
             slot.copied = copied
             d, c = ingest(slot.dev_depth.view(info.raw_height, info.raw_width),
                           slot.dev_color[:n_pix * ch].view(info.raw_height, info.raw_width, ch), info.depth_scale,
-                          info.crop_edge, self._stream)
+                          info.crop_edge, self._stream, out_size=(info.width, info.height), tables=self._tables)
             ready = torch.cuda.Event()
             ready.record(self._stream)
         with self._lock:
@@ -490,4 +707,5 @@ class FrameSource:
         n = max(self.frames, 1)
         return {"frames": self.frames, "io_workers": self.io_workers, "prefetch": self.prefetch,
                 "io_wait_s": self.io_wait_s, "io_wait_s_mean": self.io_wait_s / n,
-                "decode_ms_per_frame": 1e3 * self.decode_s / n, "h2d_bytes_per_frame": self.h2d_bytes / n}
+                "decode_ms_per_frame": 1e3 * self.decode_s / n, "h2d_bytes_per_frame": self.h2d_bytes / n,
+                "width": self.info.width, "height": self.info.height, "resolution_scale": self.info.resolution_scale}
