@@ -91,6 +91,10 @@ void rtgs_raster_set_fwd_stamps(void* dev);
 #define RTGS_ICP_STAMP_LAUNCHES 16
 #define RTGS_ICP_STAMP_WGS 256
 void rtgs_icp_set_stamps(void* dev);
+/* TSDF integration (rtgs_slam.h, "meshing"): on != 0 selects the dense form, one thread per voxel over the whole grid with no
+ * block test; 0 (default) the block-skipping form.  The planes are identical either way; the switch exists for A-B runs and
+ * tests.  RTGS_TSDF_DENSE=1 at load time.  PROCESS-WIDE. */
+void rtgs_tsdf_set_dense(int on);
 
 #ifdef __cplusplus
 }

@@ -293,6 +293,43 @@ int rtgs_densify_discs(const float* xyz, const float* scales, const float* rotat
                        const float* cos_theta, const float* sin_theta, int32_t sigma, int32_t levels, int32_t circle_num,
                        double* out, void* stream);
 
+/* ---- meshing: TSDF fusion and marching tetrahedra (no counterpart in the reference; csrc/tsdf.hip) ----------------------
+ * The volume is a dense axis-aligned grid: corner lo3_host (3 floats on the HOST), dims (nx, ny, nz), edge `voxel`, x fastest.
+ * Planes, all float32 on the device: tsdf [nz][ny][nx], weight [nz][ny][nx], rgb [3][nz][ny][nx]; a fresh volume holds
+ * tsdf = 1, weight = 0, rgb = 0.  Voxel (ix, iy, iz) has linear index (iz ny + iy) nx + ix.
+ *
+ * rtgs_tsdf_integrate fuses one frame: depth [H][W] in metres (<= 0 = hole), color [3][H][W], pinhole fx fy cx cy, and
+ * w2c12_host = the 3 rows of the world-to-camera rotation, then the translation (12 floats on the HOST).  Per voxel, in
+ * float32 and in this order:
+ *    p_w = lo + ((float)idx + 0.5f) voxel per axis;  p_c = R p_w + t, a row as ((r0 x + r1 y) + r2 z) + t;  skip if z_c <= 0;
+ *    u = fx x_c / z_c + cx, v likewise;  px = (int)floorf(u + 0.5f), py likewise;  skip outside the image;
+ *    d = depth[py][px], skip if d <= 0;  sdf = d - z_c, skip if sdf < -trunc;  s = fminf(1, sdf / trunc);
+ *    tsdf = (tsdf w + s) / (w + 1);  rgb[c] = (rgb[c] w + color[c][py][px]) / (w + 1);  w = fminf(w + 1, max_weight).
+ * By default blocks of 64 x 8 x 1 voxels that lie behind the camera, beyond the frame's largest depth + trunc or outside the
+ * frustum are skipped before any of their voxels is loaded; rtgs_tsdf_set_dense (rtgs_debug.h) selects the one-thread-per-
+ * voxel form.  Both forms write identical planes.  scratch: rtgs_tsdf_scratch_bytes(H, W) bytes on the device, 16-B aligned (the
+ * frame interleaved as r g b depth, and its largest depth).
+ *
+ * Extraction.  A cell (its lower-corner voxel) is meshed when all 8 corners have weight >= min_weight; a corner is inside
+ * when tsdf < 0.  The cell is split into the 6 tetrahedra around its main diagonal.  rtgs_tsdf_count writes the number of
+ * triangles of every cell to counts [nz ny nx] (0 for the last layer of every axis).  rtgs_tsdf_emit, given those counts, their
+ * EXCLUSIVE scan `offsets` and their sum n_tri, writes the triangles in the order (cell, tetrahedron, triangle): for corner
+ * k of triangle j, keys[3 j + k] = (linear index of the crossed edge's lower endpoint) 7 + (edge class: the direction bits
+ * x = 1, y = 2, z = 4 of the edge, minus 1), positions / colors [3 j + k][3] = the crossing interpolated from the lower
+ * endpoint a to the upper b, p = p_a + (p_b - p_a) (t_a / (t_a - t_b)).  Equal keys carry bit-identical positions and colours.
+ * Triangles are wound so that the normal points towards positive tsdf.  Returns -1 on a bad argument or a grid of more than
+ * RTGS_TSDF_MAX_VOXELS voxels. */
+#define RTGS_TSDF_MAX_VOXELS 2147483647LL
+size_t rtgs_tsdf_scratch_bytes(int32_t H, int32_t W);
+int rtgs_tsdf_integrate(float* tsdf, float* weight, float* rgb, int32_t nx, int32_t ny, int32_t nz, const float* lo3_host,
+                        float voxel, float trunc, float max_weight, const float* depth, const float* color, int32_t H, int32_t W,
+                        float fx, float fy, float cx, float cy, const float* w2c12_host, void* scratch, void* stream);
+int rtgs_tsdf_count(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
+                    int32_t* counts, void* stream);
+int rtgs_tsdf_emit(const float* tsdf, const float* weight, const float* rgb, int32_t nx, int32_t ny, int32_t nz,
+                   const float* lo3_host, float voxel, float min_weight, const int32_t* counts, const int64_t* offsets,
+                   int64_t n_tri, int64_t* keys, float* positions, float* colors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

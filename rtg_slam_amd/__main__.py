@@ -2,6 +2,7 @@
 
     python -m rtg_slam_amd slam   --config configs/replica/office0.yaml     (slam.py)
     python -m rtg_slam_amd metric --config configs/replica/office0.yaml     (metric.py)
+    python -m rtg_slam_amd mesh   --config configs/replica/office0.yaml     (no counterpart: a triangle mesh of the map)
 
 `slam` writes, under the config's save_path: config.yaml (the merged config), save_model/frame_XXXX/iter_XXXX*.ply (at frame 0,
 every save_step frames and after the final global optimisation), save_traj/pose_es.npy, pose_gt.npy and ate.txt (the ATE in
@@ -13,6 +14,9 @@ sets pcd_densify, it then writes save_model/pcd_densify.ply: 150 points on conce
 (Mapping.save_densified, slam.py:146-150), theta drawn from a generator seeded with the config's seed.  `metric` evaluates a
 saved model over the same frames and writes statis_frame_F_iter_I.csv; when the config sets pcd_densify and
 save_model/pcd_densify.ply exists, the reconstruction metrics are computed on that file's points (metric.py:156-163).
+`mesh` selects the model file as `metric` does, fuses the map's rendered depth and colour (or, with --depth-source sensor, the
+dataset's own) over the trajectory into a TSDF volume and writes save_model/mesh_tsdf.ply and save_model/mesh_report.json
+(rtg_slam_amd.meshing).  `metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -173,6 +177,8 @@ def cmd_slam(opts) -> int:
 
 
 DENSIFY_PLY = "pcd_densify.ply"
+MESH_PLY = "mesh_tsdf.ply"
+MESH_REPORT = "mesh_report.json"
 
 
 def geometry_ply(args, model_base: str, select_ply: str) -> str:
@@ -223,6 +229,59 @@ def load_map(args, device, ply_path: str):
     return mapper
 
 
+def select_model(args, opts):
+    """metric.py:120-135: the frame directory (--load-frame, default the last) and the model file in it (filter_models) ->
+    (save_model directory, frame directory name, model path, its iteration as the 4 digits of the file name)."""
+    model_base = os.path.join(args.save_path, "save_model")
+    frames = sorted(i for i in os.listdir(model_base) if os.path.isdir(os.path.join(model_base, i)))
+    if opts.load_frame < 0:
+        check_frame = frames[-1]
+    else:
+        check_frame = [i for i in frames if "%04d" % opts.load_frame in i][0]
+    frame_path = os.path.join(model_base, check_frame)
+    model = filter_models(frame_path, opts.eval_merge, opts.load_iter)[0]
+    return model_base, check_frame, os.path.join(frame_path, model), model[5:9]
+
+
+def cmd_mesh(opts) -> int:
+    import torch
+    from . import config, datasets, io_formats as iof, meshing
+    args = config.load_config(opts.config)
+    _apply_resolution_scale(args, opts)
+    device = torch.device(opts.device)
+    torch.cuda.set_device(device)
+    model_base, check_frame, select_ply, test_iter = select_model(args, opts)
+    last = int(check_frame.split("_")[-1])
+    n_frames = last if opts.frames is None or opts.frames < 0 else min(opts.frames, last)
+    log(f"meshing {select_ply} over {n_frames} frames ({opts.depth_source} depth, every {opts.every}, voxel {opts.voxel:g} m)")
+    mapper = load_map(args, device, select_ply)
+    mapper.time = int(check_frame.split("_")[1])
+    mapper.iter = int(test_iter)
+    poses = None
+    if not args.use_gt_pose:
+        poses = np.load(os.path.join(args.save_path, "save_traj", "pose_es.npy")).reshape(-1, 4, 4)[int(args.frame_start):]
+    args.frame_num = n_frames
+    info = datasets.load_dataset(args)
+    source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
+    log(f"fusing at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
+    t0 = time.perf_counter()
+    vertices, faces, colors, report = meshing.mesh_from_map(
+        mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
+        trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device)
+    report["total_s"] = time.perf_counter() - t0
+    path = os.path.join(model_base, MESH_PLY)
+    t0 = time.perf_counter()
+    iof.save_mesh_ply(path, vertices, faces, colors)
+    report["write_s"] = time.perf_counter() - t0
+    report["model"] = select_ply
+    with open(os.path.join(model_base, MESH_REPORT), "w") as f:
+        json.dump(report, f, indent=1, default=float)
+    log(f"mesh: {report['V']} vertices, {report['F']} faces from {report['frames_fused']} frames into a "
+        f"{'x'.join(str(d) for d in report['dims'])} grid: render {report['render_s']:.3f} s, integrate "
+        f"{report['integrate_s']:.3f} s, extract {report['extract_s']:.3f} s, write {report['write_s']:.3f} s -> {path}")
+    return 0
+
+
 def cmd_metric(opts) -> int:
     import torch
     from . import config, datasets, evaluation, io_formats as iof
@@ -230,22 +289,18 @@ def cmd_metric(opts) -> int:
     _apply_resolution_scale(args, opts)
     device = torch.device(opts.device)
     torch.cuda.set_device(device)
-    model_base = os.path.join(args.save_path, "save_model")
-    frames = sorted(i for i in os.listdir(model_base) if os.path.isdir(os.path.join(model_base, i)))
-    if opts.load_frame < 0:
-        check_frame = frames[-1]
-    else:
-        check_frame = [i for i in frames if "%04d" % opts.load_frame in i][0]
+    model_base, check_frame, select_ply, test_iter = select_model(args, opts)
     last = int(check_frame.split("_")[-1])
     max_cams = last if opts.eval_frames < 0 else min(opts.eval_frames, last)
-    frame_path = os.path.join(model_base, check_frame)
-    select = filter_models(frame_path, opts.eval_merge, opts.load_iter)
-    model = select[0]
-    test_iter = model[5:9]
-    log(f"evaluating {os.path.join(frame_path, model)} over {max_cams} frames")
-    select_ply = os.path.join(frame_path, model)
+    log(f"evaluating {select_ply} over {max_cams} frames")
     pcd_path = geometry_ply(args, model_base, select_ply)
     log(f"geometry eval ply: {pcd_path}")
+    mesh_path = None
+    if opts.mesh:
+        mesh_path = os.path.join(model_base, MESH_PLY)
+        if not os.path.isfile(mesh_path):
+            log(f"--mesh: {mesh_path} does not exist; write it first with `python -m rtg_slam_amd mesh --config {opts.config}`")
+            return 2
     mapper = load_map(args, device, select_ply)
     mapper.time = int(check_frame.split("_")[1])
     mapper.iter = int(test_iter)
@@ -261,7 +316,13 @@ def cmd_metric(opts) -> int:
         v, f = iof.load_mesh_ply(info.mesh_path)
         gt_points, _ = iof.sample_mesh_surface(v, f, 1_000_000)
         transform = datasets.read_pose_t0(args)
-        if pcd_path != select_ply:
+        if mesh_path is not None:
+            log(f"geometry eval mesh: {mesh_path}")
+            mv, mf = iof.load_mesh_ply(mesh_path)
+            if mf.shape[0] == 0:
+                raise ValueError(f"rtg_slam_amd: {mesh_path} holds no faces")
+            rec_points = evaluation.sample_mesh_points(mv, mf, 1_000_000, 0, device)
+        elif pcd_path != select_ply:
             xyz, _ = iof.load_point_cloud_ply(pcd_path)
             if xyz.shape[0] == 0:
                 raise ValueError(f"rtg_slam_amd: {pcd_path} holds no points")
@@ -298,12 +359,30 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("--io-workers", type=int, default=None)
     m.add_argument("--resolution-scale", type=float, default=None,
                    help="overrides resolution_scales[0]; evaluate at the scale the map was built at (metric.py:131,177)")
+    m.add_argument("--mesh", action="store_true",
+                   help="compute the reconstruction metrics on 1 M points sampled from save_model/mesh_tsdf.ply (written by `mesh`)")
+    t = sub.add_parser("mesh", help="fuse the map into a TSDF volume and write save_model/mesh_tsdf.ply")
+    t.add_argument("--config", required=True)
+    t.add_argument("--load-frame", type=int, default=-1)
+    t.add_argument("--load-iter", type=int, nargs="+", default=[])
+    t.add_argument("--eval-merge", action="store_true")
+    t.add_argument("--voxel", type=float, default=0.01, help="voxel edge in metres")
+    t.add_argument("--trunc-voxels", type=float, default=4.0, help="truncation distance in voxels")
+    t.add_argument("--depth-source", choices=("render", "sensor"), default="render",
+                   help="fuse the map's rendered depth and colour (default) or the dataset's own")
+    t.add_argument("--every", type=int, default=1, help="fuse every K-th frame")
+    t.add_argument("--frames", type=int, default=None, help="fuse at most this many frames of the trajectory")
+    t.add_argument("--min-weight", type=float, default=1.0, help="observations a cell's 8 corners need to be meshed")
+    t.add_argument("--device", default="cuda:0")
+    t.add_argument("--io-workers", type=int, default=None)
+    t.add_argument("--resolution-scale", type=float, default=None,
+                   help="overrides resolution_scales[0]; mesh at the scale the map was built at")
     return p
 
 
 def main(argv=None) -> int:
     opts = build_parser().parse_args(argv)
-    return cmd_slam(opts) if opts.cmd == "slam" else cmd_metric(opts)
+    return {"slam": cmd_slam, "metric": cmd_metric, "mesh": cmd_mesh}[opts.cmd](opts)
 
 
 if __name__ == "__main__":

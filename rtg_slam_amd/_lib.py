@@ -232,6 +232,14 @@ _SIGNATURES = {
                                           _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
     # densification
     "rtgs_densify_discs": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    # meshing
+    "rtgs_tsdf_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtgs_tsdf_integrate": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, C.c_float, _P, _P,
+                                      C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "rtgs_tsdf_count": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    "rtgs_tsdf_emit": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, _P, _P, C.c_int64,
+                                 _P, _P, _P, _P]),
+    "rtgs_tsdf_set_dense": (None, [C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -9,6 +9,7 @@
     eval_frame         SLAM/eval.py:225-270   render the map at a frame (under no_grad), then the two above
     evaluate_sequence  metric.py:137-219      every frame of a finished run with the evaluation renderer, the reconstruction
                                               once, per-frame rows and the mean row
+    eval_mesh          (no counterpart)       eval_pcd of points sampled on a triangle mesh's surface (rtg_slam_amd.meshing)
 
 Each metric call reads its float64 result vector from the device once; that read is its only synchronisation.  The results
 are bitwise reproducible run to run (fixed-order reductions, no float atomics).  There is no CPU path."""
@@ -155,6 +156,27 @@ def eval_pcd(rec_points, gt_points, dist_thres: Sequence[float] = (0.03,), trans
     res.update(Rs)
     res.update(Fs)
     return res
+
+
+def sample_mesh_points(vertices, faces, n: int, seed: int = 0, device=None) -> torch.Tensor:
+    """n points on a mesh's surface (io_formats.sample_mesh_surface: face by area, then uniform inside it; drawn on the host
+    in float64) as a float32 [n,3] tensor on `device` (default: the current HIP device)."""
+    from .io_formats import sample_mesh_surface
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    if device is None:
+        device = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    pts, _ = sample_mesh_surface(to_np(vertices), to_np(faces), int(n), seed)
+    return torch.from_numpy(pts).to(device=device, dtype=torch.float32)
+
+
+def eval_mesh(vertices, faces, gt_points, dist_thres: Sequence[float] = (0.03,), transform=None, sample_nums: int = 1_000_000,
+              seed: int = 0) -> Dict[str, float]:
+    """The reconstruction metrics of a triangle mesh: sample_nums points drawn on its surface (sample_mesh_points, `seed`),
+    then eval_pcd of them against gt_points; the same keys.  vertices [V,3], faces [F,3]: tensors or arrays."""
+    dev = gt_points.device if torch.is_tensor(gt_points) and gt_points.is_cuda else None
+    if torch.is_tensor(vertices) and vertices.is_cuda:
+        dev = vertices.device
+    return eval_pcd(sample_mesh_points(vertices, faces, sample_nums, seed, dev), gt_points, dist_thres, transform, sample_nums)
 
 
 def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: Optional[float] = None,

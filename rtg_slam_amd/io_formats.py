@@ -308,14 +308,15 @@ def _triangulate(polys) -> np.ndarray:
     return np.asarray(tris, dtype=np.int64).reshape(-1, 3)
 
 
-def load_mesh_ply(path: str):
+def load_mesh_ply(path: str, with_colors: bool = False):
     """A triangle mesh from a PLY file, ascii or binary little-endian (what trimesh.load reads for eval_pcd's GT mesh,
     SLAM/eval.py:155): -> (vertices float64 [V,3], faces int64 [F,3]).  Faces are lists of 3 or more vertex indices;
-    quads (and larger polygons) are split into triangles (a,b,c), (a,c,d).  Other elements are skipped."""
+    quads (and larger polygons) are split into triangles (a,b,c), (a,c,d).  Other elements are skipped.  with_colors adds a
+    third result: the vertices' red / green / blue as float64 [V,3] in 0..1 (uchar properties / 255), or None without them."""
     with open(path, "rb") as f:
         fmt, elements = _ply_header(f, path)
         body = f.read()
-    verts, faces = None, np.zeros((0, 3), np.int64)
+    verts, faces, colors = None, np.zeros((0, 3), np.int64), None
     if fmt == "ascii":
         tokens, pos = body.decode("ascii").split(), 0
         read = lambda count, props, pos: _ply_ascii_element(tokens, pos, count, props)
@@ -326,6 +327,9 @@ def load_mesh_ply(path: str):
         cols, pos = read(count, props, pos)
         if name == "vertex":
             verts = np.stack([np.asarray(cols[k], dtype=np.float64) for k in ("x", "y", "z")], axis=1)
+            if all(k in cols for k in ("red", "green", "blue")):
+                unit = 255.0 if dict(props)["red"] == "u1" else 1.0
+                colors = np.stack([np.asarray(cols[k], dtype=np.float64) for k in ("red", "green", "blue")], axis=1) / unit
         elif name == "face":
             key = next((n for n, t in props if isinstance(t, tuple) and n in ("vertex_indices", "vertex_index")), None)
             if key is None:
@@ -333,7 +337,42 @@ def load_mesh_ply(path: str):
             faces = _triangulate(cols[key])
     if verts is None:
         raise ValueError(f"{path}: no vertex element")
-    return verts, faces
+    return (verts, faces, colors) if with_colors else (verts, faces)
+
+
+def save_mesh_ply(path: str, vertices, faces, colors=None) -> None:
+    """An indexed triangle mesh as a binary little-endian PLY: float x y z (and uchar red green blue when colors [V,3] in
+    0..1 are given, rounded to the nearest of 255 steps) per vertex, `list uchar int vertex_indices` per face.  Tensors or
+    arrays; load_mesh_ply reads the file back with the vertices bit-equal."""
+    to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    v = np.ascontiguousarray(to_np(vertices), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(to_np(faces)).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"save_mesh_ply: face indices must lie in 0..{v.shape[0] - 1}")
+    if v.shape[0] > 0x7fffffff:
+        raise ValueError("save_mesh_ply: more vertices than an int index holds")
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
+    lines += [f"property float {c}" for c in "xyz"]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = to_np(colors).reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"save_mesh_ply: {c.shape[0]} colours for {v.shape[0]} vertices")
+        lines += [f"property uchar {n}" for n in ("red", "green", "blue")]
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    lines += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    vt = np.empty(v.shape[0], dtype=np.dtype(fields))
+    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        q = np.clip(np.rint(np.nan_to_num(c.astype(np.float64)) * 255.0), 0, 255).astype(np.uint8)
+        vt["red"], vt["green"], vt["blue"] = q[:, 0], q[:, 1], q[:, 2]
+    ft = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    ft["n"] = 3
+    ft["i"] = f
+    with open(path, "wb") as out:
+        out.write(("\n".join(lines) + "\n").encode("ascii"))
+        out.write(vt.tobytes())
+        out.write(ft.tobytes())
 
 
 def sample_mesh_surface(vertices, faces, n: int, seed: int = 0):

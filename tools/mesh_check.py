@@ -1,0 +1,133 @@
+"""Times the mesher (rtg_slam_amd.meshing) on the device and prints one JSON line (also written to OUT when given):
+  * rtgs_tsdf_integrate per frame at 1200 x 680 (the Replica camera in the box room, poses of synth.room_tour) into the
+    room-sized volume (the room padded by 10 cm) at 2 cm and at 1 cm voxels, in the block-skipping and in the dense form, on the
+    same frames and the same (already fused) planes; the voxels a frame updates are counted from the weight plane, the bytes
+    moved are 40 B per updated voxel (20 B read, 20 B written) plus the frame (16 B per pixel, read at least once);
+  * the streaming yardstick of the dense form: a volume that lies wholly inside the frustum and in front of the surface, so
+    that every voxel is updated and the launch moves exactly 40 B per voxel;
+  * extract_mesh of the fused room at both voxel sizes (count + scan + emit + weld), with V and F;
+  * the box-room end-to-end case of tests/test_mesh_gpu.py (sensor depth, 20 frames, 2 cm): vertex-to-wall statistics.
+Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
+blocks are reported.  python tools/mesh_check.py [OUT] [reps = 10] [blocks = 5]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from rtg_slam_amd import meshing, synth   # noqa: E402
+
+
+def blocks_ms(fn, reps, blocks, warmup=3):
+    """fn(i) launches the i-th call; -> per-call milliseconds of every block."""
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(blocks):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(reps):
+            fn(i)
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / reps)
+    return {"median_ms": round(float(np.median(out)), 4), "min_ms": round(float(np.min(out)), 4),
+            "max_ms": round(float(np.max(out)), 4), "reps_per_block": reps, "blocks": blocks}
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else None
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    blocks = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    dev = torch.device("cuda", 0)
+    cam = synth.REPLICA
+    res = {"device": torch.cuda.get_device_name(dev), "camera": [cam.W, cam.H], "bytes_per_updated_voxel": 40}
+    poses = synth.room_tour(reps * 40, seed=3)[::40]
+    frames = []
+    for p in poses:
+        d = synth.box_room_depth(cam, p, device=dev)
+        frames.append((d.reshape(cam.H, cam.W).contiguous(), synth.box_room_color(cam, p, d), p.numpy()))
+    frame_bytes = cam.H * cam.W * 16
+    half = (2.5, 1.5, 3.0)
+    lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        n = vol.dims[0] * vol.dims[1] * vol.dims[2]
+        updated = []
+        for d, c, p in frames:
+            before = vol.weight.clone()
+            vol.integrate(d, c, cam, p)
+            updated.append(int((vol.weight != before).sum()))
+            del before
+        entry = {"dims": list(vol.dims), "voxels": n, "plane_bytes": n * 20,
+                 "updated_voxels_per_frame_mean": int(np.mean(updated)), "updated_share_mean": round(float(np.mean(updated)) / n, 4)}
+        moved = float(np.mean(updated)) * 40 + frame_bytes
+        entry["bytes_moved_per_frame_mean"] = int(moved)
+        call = lambda i: vol.integrate(*frames[i % len(frames)][:2], cam, frames[i % len(frames)][2])
+        for form in ("block", "dense"):
+            meshing.set_dense_form(form == "dense")
+            try:
+                t = blocks_ms(call, reps, blocks)
+            finally:
+                meshing.set_dense_form(False)
+            t["TB_per_s_of_moved_bytes_at_median"] = round(moved / (t["median_ms"] * 1e-3) / 1e12, 3)
+            entry[form] = t
+        entry["block_over_dense_time_ratio"] = round(entry["block"]["median_ms"] / entry["dense"]["median_ms"], 3)
+        torch.cuda.synchronize()
+        ext = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            v, f, c = vol.extract_mesh()
+            torch.cuda.synchronize()
+            ext.append(time.perf_counter() - t0)
+        entry["extract"] = {"median_s": round(float(np.median(ext)), 4), "min_s": round(min(ext), 4), "max_s": round(max(ext), 4),
+                            "runs": 3, "V": int(v.shape[0]), "F": int(f.shape[0]),
+                            "bytes_read_lower_bound": n * 8 + n * 4 + int(f.shape[0]) * 3 * 32,
+                            "includes": "count, cumsum, emit, unique / inverse weld, gathers; wall clock with a final synchronise"}
+        res[f"room_voxel_{voxel:g}"] = entry
+        del vol, v, f, c
+        torch.cuda.empty_cache()
+
+    # streaming yardstick: every voxel inside the frustum and in front of a constant 10 m depth
+    voxel = 0.008
+    vol = meshing.TsdfVolume((-1.9, -1.1, 2.0), (1.9, 1.1, 4.0), voxel, device=dev)
+    n = vol.dims[0] * vol.dims[1] * vol.dims[2]
+    depth = torch.full((cam.H, cam.W), 10.0, device=dev)
+    color = frames[0][1]
+    vol.integrate(depth, color, cam, np.eye(4))
+    assert int((vol.weight == 1).sum()) == n, "the yardstick volume must be updated everywhere"
+    entry = {"dims": list(vol.dims), "voxels": n, "bytes_moved": n * 40 + frame_bytes,
+             "yardstick": "rtgs_densify_discs writes at 5.0-5.3 TB/s on this chip (profiles/r09_densify_check.json)"}
+    for form in ("dense", "block"):
+        meshing.set_dense_form(form == "dense")
+        try:
+            t = blocks_ms(lambda i: vol.integrate(depth, color, cam, np.eye(4)), reps, blocks)
+        finally:
+            meshing.set_dense_form(False)
+        t["TB_per_s_at_median"] = round((n * 40 + frame_bytes) / (t["median_ms"] * 1e-3) / 1e12, 3)
+        entry[form] = t
+    res["all_voxels_updated"] = entry
+    del vol
+
+    # the end-to-end case of tests/test_mesh_gpu.py
+    from tests import tsdf_reference as tr
+    bcam, bframes, blo, bhi, bvoxel = tr.box_room_case()
+    stream = [(d.to(dev), c.to(dev), p) for d, c, p in bframes]
+    v, f, c, report = meshing.mesh_from_map(None, bcam, None, iter(stream), voxel=bvoxel, depth_source="sensor", bounds=(blo, bhi),
+                                            device=dev)
+    res["box_room_sensor_2cm"] = {"report": report, "vertex_to_wall_m": tr.wall_stats(v.cpu().numpy()),
+                                  "numpy_reference_on_cpu": {"mean": 0.01126, "p99": 0.03607, "max": 0.03778, "covered": 0.1844}}
+    line = json.dumps(res, default=float)
+    print(line)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fo:
+            json.dump(res, fo, indent=1, default=float)
+
+
+if __name__ == "__main__":
+    main()
