@@ -330,6 +330,52 @@ int rtgs_tsdf_emit(const float* tsdf, const float* weight, const float* rgb, int
                    const float* lo3_host, float voxel, float min_weight, const int32_t* counts, const int64_t* offsets,
                    int64_t n_tri, int64_t* keys, float* positions, float* colors, void* stream);
 
+/* The sparse brick volume (rtgs_tsdf_sparse_*): the same virtual grid - lo, dims, voxel, centres, 64-bit linear index
+ * (iz ny + iy) nx + ix - with planes only for the 8 x 8 x 8 bricks near an observed surface.  Brick (bx, by, bz) covers voxels
+ * [8 bx, 8 bx + 8) per axis, cut at the grid; brick dims nb = ceil(n / 8); brick linear index (bz nby + by) nbx + bx.
+ *   table  [nbz][nby][nbx] int32: the brick's slot, -1 without one (the caller fills a new table with -1)
+ *   pool   [slot][plane: tsdf, weight, r, g, b][z][y][x] float32, RTGS_TSDF_BRICK_BYTES a brick, 16-B aligned
+ *   coords [slot][3] int32: (bx, by, bz)
+ * A brick without a slot reads as a fresh volume (tsdf 1, weight 0, rgb 0), in extraction too.  One frame is three calls:
+ *   rtgs_tsdf_sparse_mark      packs the frame into scratch (rtgs_tsdf_scratch_bytes) and writes flags [nbz nby nbx] int32: 1 for
+ *                              every brick without a slot that holds one of the 27 neighbours (ix + dx, iy + dy, iz + dz),
+ *                              d in {-1, 0, 1}^3, inside the grid, of an IN-BAND voxel: one the dense rule above updates and
+ *                              whose sdf / trunc < 1 in float32; 0 elsewhere.
+ *   rtgs_tsdf_sparse_allocate  given flags, their EXCLUSIVE scan `offsets` in brick-linear order and their sum n_new, gives
+ *                              flagged brick i the slot base + offsets[i] (base = bricks allocated so far, base + n_new <=
+ *                              capacity, the pool's and coords' size in bricks), writes table and coords and makes the new
+ *                              bricks fresh.  Slots are thus in ascending brick linear index within a frame.
+ *   rtgs_tsdf_sparse_integrate applies the dense rule's float chain to every voxel of the n_bricks allocated bricks; scratch
+ *                              must still hold the frame packed by rtgs_tsdf_sparse_mark with the same arguments.  Voxels of
+ *                              bricks without a slot are not updated: what was seen before a brick's allocation is lost.
+ * Hence a voxel of an allocated brick equals the dense volume's bit for bit unless the dense voxel was updated before the
+ * brick was allocated; after one frame into a fresh volume every allocated voxel and the whole mesh equal the dense ones.
+ * rtgs_tsdf_sparse_count / _emit are rtgs_tsdf_count / _emit over the allocated bricks: counts and offsets are
+ * [n_bricks][8][8][8] (slot, then z, y, x of the cell's lower corner in the brick); keys use the virtual linear index;
+ * triangles leave in slot order, and cells [n_tri] receives each triangle's virtual cell linear index so that a stable sort
+ * on it restores the (cell, tetrahedron, triangle) order.  min_weight must be > 0.  rtgs_tsdf_sparse_to_dense writes the box
+ * window6_host = (x0, x1, y0, y1, z0, z1) (HOST, voxels, half-open) as dense planes tsdf, weight [wz][wy][wx], rgb [3][wz][wy][wx].
+ * Limits: every dim <= 2^24, nbx nby nbz and capacity <= RTGS_TSDF_SPARSE_MAX_BRICKS; nx ny nz only has to fit int64.
+ * Returns -1 on a bad argument. */
+#define RTGS_TSDF_SPARSE_MAX_BRICKS 2147483647LL
+#define RTGS_TSDF_BRICK_BYTES 10240
+int rtgs_tsdf_sparse_mark(const int32_t* table, int32_t* flags, int32_t nx, int32_t ny, int32_t nz, const float* lo3_host,
+                          float voxel, float trunc, const float* depth, const float* color, int32_t H, int32_t W, float fx, float fy,
+                          float cx, float cy, const float* w2c12_host, void* scratch, void* stream);
+int rtgs_tsdf_sparse_allocate(int32_t* table, const int32_t* flags, const int64_t* offsets, int32_t nx, int32_t ny, int32_t nz,
+                              int64_t base, int64_t n_new, int64_t capacity, int32_t* coords, float* pool, void* stream);
+int rtgs_tsdf_sparse_integrate(float* pool, const int32_t* coords, int64_t n_bricks, int32_t nx, int32_t ny, int32_t nz,
+                               const float* lo3_host, float voxel, float trunc, float max_weight, int32_t H, int32_t W, float fx,
+                               float fy, float cx, float cy, const float* w2c12_host, const void* scratch, void* stream);
+int rtgs_tsdf_sparse_count(const float* pool, const int32_t* coords, const int32_t* table, int64_t n_bricks, int32_t nx,
+                           int32_t ny, int32_t nz, float min_weight, int32_t* counts, void* stream);
+int rtgs_tsdf_sparse_emit(const float* pool, const int32_t* coords, const int32_t* table, int64_t n_bricks, int32_t nx, int32_t ny,
+                          int32_t nz, const float* lo3_host, float voxel, float min_weight, const int32_t* counts,
+                          const int64_t* offsets, int64_t n_tri, int64_t* cells, int64_t* keys, float* positions, float* colors,
+                          void* stream);
+int rtgs_tsdf_sparse_to_dense(const float* pool, const int32_t* table, int32_t nx, int32_t ny, int32_t nz, const int32_t* window6_host,
+                              float* tsdf, float* weight, float* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,8 @@ saved model over the same frames and writes statis_frame_F_iter_I.csv; when the 
 save_model/pcd_densify.ply exists, the reconstruction metrics are computed on that file's points (metric.py:156-163).
 `mesh` selects the model file as `metric` does, fuses the map's rendered depth and colour (or, with --depth-source sensor, the
 dataset's own) over the trajectory into a TSDF volume and writes save_model/mesh_tsdf.ply and save_model/mesh_report.json
-(rtg_slam_amd.meshing).  `metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
+(rtg_slam_amd.meshing); --volume sparse keeps planes only for the 8x8x8 bricks near the surface, for boxes whose dense planes
+would be refused.  `metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -267,7 +268,7 @@ def cmd_mesh(opts) -> int:
     t0 = time.perf_counter()
     vertices, faces, colors, report = meshing.mesh_from_map(
         mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
-        trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device)
+        trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume)
     report["total_s"] = time.perf_counter() - t0
     path = os.path.join(model_base, MESH_PLY)
     t0 = time.perf_counter()
@@ -279,6 +280,9 @@ def cmd_mesh(opts) -> int:
     log(f"mesh: {report['V']} vertices, {report['F']} faces from {report['frames_fused']} frames into a "
         f"{'x'.join(str(d) for d in report['dims'])} grid: render {report['render_s']:.3f} s, integrate "
         f"{report['integrate_s']:.3f} s, extract {report['extract_s']:.3f} s, write {report['write_s']:.3f} s -> {path}")
+    if opts.volume == "sparse":
+        log(f"sparse volume: {report['bricks']} bricks, {100 * report['brick_share']:.2f} % of the grid's, "
+            f"{report['pool_bytes'] / 2 ** 20:.1f} MiB of pool where the dense planes would take {report['dense_bytes'] / 2 ** 20:.1f} MiB")
     return 0
 
 
@@ -370,6 +374,8 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--trunc-voxels", type=float, default=4.0, help="truncation distance in voxels")
     t.add_argument("--depth-source", choices=("render", "sensor"), default="render",
                    help="fuse the map's rendered depth and colour (default) or the dataset's own")
+    t.add_argument("--volume", choices=("dense", "sparse"), default="dense",
+                   help="dense planes over the whole box (default) or planes only for the 8x8x8 bricks near the surface")
     t.add_argument("--every", type=int, default=1, help="fuse every K-th frame")
     t.add_argument("--frames", type=int, default=None, help="fuse at most this many frames of the trajectory")
     t.add_argument("--min-weight", type=float, default=1.0, help="observations a cell's 8 corners need to be meshed")

@@ -240,6 +240,17 @@ _SIGNATURES = {
     "rtgs_tsdf_emit": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, _P, _P, C.c_int64,
                                  _P, _P, _P, _P]),
     "rtgs_tsdf_set_dense": (None, [C.c_int]),
+    "rtgs_tsdf_sparse_mark": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, _P, _P, C.c_int32,
+                                        C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "rtgs_tsdf_sparse_allocate": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P,
+                                            _P]),
+    "rtgs_tsdf_sparse_integrate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float,
+                                             C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
+                                             _P]),
+    "rtgs_tsdf_sparse_count": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    "rtgs_tsdf_sparse_emit": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, _P, _P,
+                                        C.c_int64, _P, _P, _P, _P, _P]),
+    "rtgs_tsdf_sparse_to_dense": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -27,6 +27,20 @@
 // table is generated at compile time (make_table); orientation is fixed there with the crossings at the edge midpoints in
 // integer arithmetic.  A crossing is interpolated from the lower linear index a to the higher b:
 //   w = t_a / (t_a - t_b),  p = p_a + (p_b - p_a) w,  colour likewise.
+//
+// The sparse brick volume (rtgs_tsdf_sparse_*; tests/tsdf_sparse_reference.py is its definition): the same virtual grid with
+// planes only for the 8 x 8 x 8 bricks near an observed surface - a table of one int32 per brick (slot or -1), a pool
+// [slot][tsdf, weight, r, g, b][z][y][x] of 10 240 B a brick, the slots' brick coordinates.  project_voxel / observe / fuse,
+// the brick test (box_outside) and the case table are the dense form's, so an allocated voxel follows the same float chain.
+//   mark       one wave per brick of the virtual grid; the six-ballot test, then the brick's voxels are projected and tested in
+//              band (updated by the dense rule, s < 1); an in-band voxel flags its brick and the face / edge / corner
+//              neighbours it touches, where they have no slot yet (plain stores of 1)
+//   allocate   the caller scans the flags in brick-linear order and reads their sum; new bricks get the slots after the old
+//              ones in that order, their coordinates are recorded and their planes made fresh
+//   integrate  one wave per allocated brick, a lane per (x, y), the 8 z layers in two batched passes: 256 contiguous bytes per
+//              access of a wave to a plane, no LDS, no barrier
+//   count/emit one wave per allocated brick; lanes 0..7 look up the slots of the brick and its 7 upper neighbours once; 64-bit
+//              linear indices and keys; triangles leave in slot order with their cell's linear index for the caller's sort
 #include "../../include/rtgs_slam.h"
 #include "../../include/rtgs_debug.h"
 #include <hip/hip_runtime.h>
@@ -139,6 +153,29 @@ __global__ void __launch_bounds__(NT) integrate_dense_kernel(Grid g, Frame f, co
   integrate_voxel(g, f, ix, (int)(r % g.ny), (int)(r / g.ny), plane, frame, tsdf, weight, rgb);
 }
 
+// The six-ballot test of the box of voxels [x0, x1] x [y0, y1] x [z0, z1] (inclusive), by a whole wave: lanes 0..7 (every
+// lane, by lane & 7) transform the box's corner centres; true when every corner is behind the camera, farther than the
+// frame's largest depth + trunc, or outside one of the four side planes of the frustum, so that no voxel of the box updates.
+__device__ __forceinline__ bool box_outside(const Grid& g, const Frame& f, int lane, int x0, int y0, int z0, int x1, int y1, int z1,
+                                            const uint32_t* __restrict__ dmax_bits) {
+  const int c = lane & 7;
+  const float x = g.lox + ((float)((c & 1) ? x1 : x0) + 0.5f) * g.voxel;
+  const float y = g.loy + ((float)((c & 2) ? y1 : y0) + 0.5f) * g.voxel;
+  const float z = g.loz + ((float)((c & 4) ? z1 : z0) + 0.5f) * g.voxel;
+  float xc, yc, zc;
+  to_camera(f, x, y, z, xc, yc, zc);
+  const float dmax = __uint_as_float(*dmax_bits);
+  const float lx = f.fx * xc, ly = f.fy * yc;
+  const bool behind = zc < -f.mz;
+  const bool beyond = zc - f.mz > (dmax + f.trunc) + f.mz;
+  const bool left = lx + (f.cx + 0.5f) * zc < -f.mx;
+  const bool right = lx + (f.cx + 0.5f - (float)f.W) * zc > f.mx;
+  const bool top = ly + (f.cy + 0.5f) * zc < -f.my;
+  const bool bottom = ly + (f.cy + 0.5f - (float)f.H) * zc > f.my;
+  const auto all8 = [](bool p) { return (__ballot(p) & 0xffull) == 0xffull; };
+  return !(dmax > 0.0f) || all8(behind) || all8(beyond) || all8(left) || all8(right) || all8(top) || all8(bottom);
+}
+
 // One WAVE per block, no LDS and no barrier: lanes 0..7 (every lane, by lane & 7) transform the block's corner centres, six
 // ballots decide; a wave that stays walks its block with a lane per x (256 contiguous bytes of a plane per access) in passes
 // of PV rows, each pass as batches - project and gather the pixel of all PV, then load the planes of the ones that update,
@@ -155,25 +192,7 @@ __global__ void __launch_bounds__(NT) integrate_block_kernel(Grid g, Frame f, in
   const int64_t b = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
   if (b >= nblocks) return;                                   // wave-uniform
   const int x0 = (int)(b % nbx) * BX, y0 = (int)((b / nbx) % nby) * BY, z0 = (int)(b / ((int64_t)nbx * nby)) * BZ;
-  {
-    const int c = lane & 7;
-    const int x1 = min(x0 + BX, g.nx) - 1, y1 = min(y0 + BY, g.ny) - 1, z1 = min(z0 + BZ, g.nz) - 1;
-    const float x = g.lox + ((float)((c & 1) ? x1 : x0) + 0.5f) * g.voxel;
-    const float y = g.loy + ((float)((c & 2) ? y1 : y0) + 0.5f) * g.voxel;
-    const float z = g.loz + ((float)((c & 4) ? z1 : z0) + 0.5f) * g.voxel;
-    float xc, yc, zc;
-    to_camera(f, x, y, z, xc, yc, zc);
-    const float dmax = __uint_as_float(*dmax_bits);
-    const float lx = f.fx * xc, ly = f.fy * yc;
-    const bool behind = zc < -f.mz;
-    const bool beyond = zc - f.mz > (dmax + f.trunc) + f.mz;
-    const bool left = lx + (f.cx + 0.5f) * zc < -f.mx;
-    const bool right = lx + (f.cx + 0.5f - (float)f.W) * zc > f.mx;
-    const bool top = ly + (f.cy + 0.5f) * zc < -f.my;
-    const bool bottom = ly + (f.cy + 0.5f - (float)f.H) * zc > f.my;
-    const auto all8 = [](bool p) { return (__ballot(p) & 0xffull) == 0xffull; };
-    if (!(dmax > 0.0f) || all8(behind) || all8(beyond) || all8(left) || all8(right) || all8(top) || all8(bottom)) return;
-  }
+  if (box_outside(g, f, lane, x0, y0, z0, min(x0 + BX, g.nx) - 1, min(y0 + BY, g.ny) - 1, min(z0 + BZ, g.nz) - 1, dmax_bits)) return;
   const int64_t plane = (int64_t)g.nx * g.ny * g.nz;
   const int ix = x0 + lane;
 #pragma unroll
@@ -369,6 +388,299 @@ __global__ void __launch_bounds__(NT) emit_kernel(Grid g, const float* __restric
   }
 }
 
+// ---- sparse brick volume ------------------------------------------------------------------------------------------------
+// The virtual grid is the dense volume's; planes exist only for allocated 8 x 8 x 8 bricks.  table [nbz][nby][nbx] int32: a
+// brick's slot or -1.  pool [slot][plane: tsdf, weight, r, g, b][z][y][x] float32, 10 240 B a brick: with a lane per (x, y)
+// of a brick layer every access of a wave to a plane is 256 contiguous bytes.  coords [slot][3] int32: (bx, by, bz).
+constexpr int BR = 8;
+constexpr int BRICK_VOXELS = BR * BR * BR;                     // floats of one plane of a brick
+constexpr int BRICK_FLOATS = 5 * BRICK_VOXELS;
+static_assert(BR * BR == 64, "a lane per (x, y) of a brick layer");
+
+struct BrickGrid {
+  int nbx, nby, nbz;
+};
+
+// One WAVE per brick of the virtual grid.  The brick test first; a wave that stays projects its voxels (a lane per (x, y),
+// the 8 z layers in two batched passes) and tests them in band: the dense rule would update them and s < 1.  An in-band
+// voxel touches its own brick and, on a brick face, the face / edge / corner neighbours inside the grid: 27 bits a lane,
+// ORed over the wave; lanes 0..26 then flag the bricks that have no slot yet.  Every writer stores the same value.
+__global__ void __launch_bounds__(NT) sparse_mark_kernel(Grid g, Frame f, BrickGrid bg, int64_t nbricks,
+                                                         const float4* __restrict__ frame,
+                                                         const uint32_t* __restrict__ dmax_bits,
+                                                         const int32_t* __restrict__ table, int32_t* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (b >= nbricks) return;                                   // wave-uniform
+  const int bx = (int)(b % bg.nbx), by = (int)((b / bg.nbx) % bg.nby), bz = (int)(b / ((int64_t)bg.nbx * bg.nby));
+  const int x0 = bx * BR, y0 = by * BR, z0 = bz * BR;
+  if (box_outside(g, f, lane, x0, y0, z0, min(x0 + BR, g.nx) - 1, min(y0 + BR, g.ny) - 1, min(z0 + BR, g.nz) - 1, dmax_bits)) return;
+  const int lx = lane & 7, ly = lane >> 3;
+  const int ix = x0 + lx, iy = y0 + ly;
+  const uint32_t mx = 2u | (lx == 0 && ix > 0 ? 1u : 0u) | (lx == BR - 1 && ix + 1 < g.nx ? 4u : 0u);
+  const uint32_t my = 2u | (ly == 0 && iy > 0 ? 1u : 0u) | (ly == BR - 1 && iy + 1 < g.ny ? 4u : 0u);
+  const uint32_t row = ((my & 1u) ? mx : 0u) | (mx << 3) | ((my & 4u) ? mx << 6 : 0u);
+  uint32_t m27 = 0;
+#pragma unroll
+  for (int pass = 0; pass < BR / PV; ++pass) {
+    float zc[PV];
+    float4 q[PV];
+    bool ok[PV];
+#pragma unroll
+    for (int v = 0; v < PV; ++v) {
+      const int iz = z0 + pass * PV + v;
+      int p = 0;
+      zc[v] = 0.0f;
+      ok[v] = ix < g.nx && iy < g.ny && iz < g.nz && project_voxel(g, f, ix, iy, iz, p, zc[v]);
+      q[v] = frame[ok[v] ? p : 0];
+    }
+#pragma unroll
+    for (int v = 0; v < PV; ++v) {
+      const int lz = pass * PV + v, iz = z0 + lz;
+      float s = 1.0f;
+      if (ok[v] && observe(f, q[v].w, zc[v], s) && s < 1.0f) {
+        m27 |= row << 9;
+        if (lz == 0 && iz > 0) m27 |= row;
+        if (lz == BR - 1 && iz + 1 < g.nz) m27 |= row << 18;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m27 |= (uint32_t)__shfl_xor((int)m27, o);
+  if (lane < 27 && ((m27 >> lane) & 1u)) {
+    const int nx_ = bx + lane % 3 - 1, ny_ = by + (lane / 3) % 3 - 1, nz_ = bz + lane / 9 - 1;
+    if (nx_ >= 0 && nx_ < bg.nbx && ny_ >= 0 && ny_ < bg.nby && nz_ >= 0 && nz_ < bg.nbz) {
+      const int64_t n = ((int64_t)nz_ * bg.nby + ny_) * bg.nbx + nx_;
+      if (table[n] < 0) flags[n] = 1;
+    }
+  }
+}
+
+// flags: 1 for a new brick; offsets: their exclusive scan in brick-linear order.  New brick i gets slot base + offsets[i].
+__global__ void __launch_bounds__(NT) sparse_assign_kernel(BrickGrid bg, int64_t nbricks, const int32_t* __restrict__ flags,
+                                                           const int64_t* __restrict__ offsets, int64_t base, int64_t n_new,
+                                                           int32_t* __restrict__ table, int32_t* __restrict__ coords) {
+  const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (i >= nbricks || flags[i] == 0) return;
+  const int64_t k = offsets[i];
+  if (k < 0 || k >= n_new) return;                            // flags / offsets not of this frame: never write past the pool
+  const int64_t slot = base + k;
+  table[i] = (int32_t)slot;
+  coords[3 * slot] = (int32_t)(i % bg.nbx);
+  coords[3 * slot + 1] = (int32_t)((i / bg.nbx) % bg.nby);
+  coords[3 * slot + 2] = (int32_t)(i / ((int64_t)bg.nbx * bg.nby));
+}
+
+__global__ void __launch_bounds__(NT) sparse_fresh_kernel(float4* __restrict__ bricks, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (i >= n4) return;
+  const float v = (i % (BRICK_FLOATS / 4)) < BRICK_VOXELS / 4 ? 1.0f : 0.0f;            // the tsdf plane comes first
+  bricks[i] = make_float4(v, v, v, v);
+}
+
+// One WAVE per allocated brick, the walk of integrate_block_kernel: a lane per (x, y), the 8 z layers in passes of PV.
+__global__ void __launch_bounds__(NT) sparse_integrate_kernel(Grid g, Frame f, int64_t nslots, const int32_t* __restrict__ coords,
+                                                              const float4* __restrict__ frame,
+                                                              const uint32_t* __restrict__ dmax_bits, float* __restrict__ pool) {
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (slot >= nslots) return;                                 // wave-uniform
+  const int x0 = coords[3 * slot] * BR, y0 = coords[3 * slot + 1] * BR, z0 = coords[3 * slot + 2] * BR;
+  if (box_outside(g, f, lane, x0, y0, z0, min(x0 + BR, g.nx) - 1, min(y0 + BR, g.ny) - 1, min(z0 + BR, g.nz) - 1, dmax_bits)) return;
+  float* __restrict__ brick = pool + slot * BRICK_FLOATS;
+  const int ix = x0 + (lane & 7), iy = y0 + (lane >> 3);
+#pragma unroll
+  for (int pass = 0; pass < BR / PV; ++pass) {
+    int idx[PV];
+    float zc[PV], s[PV], w[PV], t[PV], c[PV][3];
+    float4 q[PV];
+    bool ok[PV];
+#pragma unroll
+    for (int v = 0; v < PV; ++v) {
+      const int lz = pass * PV + v, iz = z0 + lz;
+      int p = 0;
+      zc[v] = 0.0f;
+      ok[v] = ix < g.nx && iy < g.ny && iz < g.nz && project_voxel(g, f, ix, iy, iz, p, zc[v]);
+      idx[v] = lz * 64 + lane;
+      q[v] = frame[ok[v] ? p : 0];                             // pixel 0 for a voxel that does not project: never used
+    }
+#pragma unroll
+    for (int v = 0; v < PV; ++v) {
+      s[v] = 0.0f;
+      ok[v] = ok[v] && observe(f, q[v].w, zc[v], s[v]);
+      if (ok[v]) {
+        t[v] = brick[idx[v]];
+        w[v] = brick[BRICK_VOXELS + idx[v]];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[v][k] = brick[(2 + k) * BRICK_VOXELS + idx[v]];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < PV; ++v) {
+      if (ok[v]) {
+        const float w1 = w[v] + 1.0f;
+        brick[idx[v]] = fuse(t[v], w[v], s[v], w1);
+        const float o[3] = {q[v].x, q[v].y, q[v].z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) brick[(2 + k) * BRICK_VOXELS + idx[v]] = fuse(c[v][k], w[v], o[k], w1);
+        brick[BRICK_VOXELS + idx[v]] = fminf(w1, f.max_weight);
+      }
+    }
+  }
+}
+
+// The slots of a brick and its 7 upper neighbours (bit 0 = +x, 1 = +y, 2 = +z), looked up once per brick by lanes 0..7 and
+// handed to every lane; -1 outside the brick grid or without a slot.  Called by a whole wave.
+struct Slots {
+  int s[8];
+};
+
+__device__ __forceinline__ Slots neighbour_slots(const BrickGrid& bg, const int32_t* __restrict__ table, int lane, int bx, int by,
+                                                 int bz) {
+  int mine = -1;
+  if (lane < 8) {
+    const int nx_ = bx + (lane & 1), ny_ = by + ((lane >> 1) & 1), nz_ = bz + (lane >> 2);
+    if (nx_ < bg.nbx && ny_ < bg.nby && nz_ < bg.nbz) mine = table[((int64_t)nz_ * bg.nby + ny_) * bg.nbx + nx_];
+  }
+  Slots r;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r.s[k] = __shfl(mine, k);
+  return r;
+}
+
+// offset in the pool of the tsdf of the voxel at brick-local (X, Y, Z) in [0, 16)^3, or -1 when its brick has no slot
+__device__ __forceinline__ int64_t voxel_offset(const Slots& n, int X, int Y, int Z) {
+  const bool xb = X >= BR, yb = Y >= BR, zb = Z >= BR;
+  const int a0 = xb ? n.s[1] : n.s[0], a1 = xb ? n.s[3] : n.s[2], a2 = xb ? n.s[5] : n.s[4], a3 = xb ? n.s[7] : n.s[6];
+  const int b0 = yb ? a1 : a0, b1 = yb ? a3 : a2;
+  const int slot = zb ? b1 : b0;
+  if (slot < 0) return -1;
+  return (int64_t)slot * BRICK_FLOATS + ((Z & 7) * 64 + (Y & 7) * 8 + (X & 7));
+}
+
+// cell_mask on the brick pool: an unallocated corner has weight 0 and tsdf 1
+__device__ __forceinline__ int sparse_cell_mask(const Grid& g, const Slots& n, int ix, int iy, int iz, int lx, int ly, int lz,
+                                                const float* __restrict__ pool, float min_weight) {
+  if (ix >= g.nx - 1 || iy >= g.ny - 1 || iz >= g.nz - 1) return -1;
+  int mask = 0;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int64_t o = voxel_offset(n, lx + (c & 1), ly + ((c >> 1) & 1), lz + (c >> 2));
+    const float w = o >= 0 ? pool[o + BRICK_VOXELS] : 0.0f;
+    const float t = o >= 0 ? pool[o] : 1.0f;
+    ok = ok && w >= min_weight;
+    mask |= (t < 0.0f ? 1 : 0) << c;
+  }
+  return ok ? mask : -1;
+}
+
+// One WAVE per allocated brick: counts [slot][z][y][x] of the cells whose lower corner lies in the brick.
+__global__ void __launch_bounds__(NT) sparse_count_kernel(Grid g, BrickGrid bg, int64_t nslots, const int32_t* __restrict__ coords,
+                                                          const int32_t* __restrict__ table, const float* __restrict__ pool,
+                                                          float min_weight, int32_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (slot >= nslots) return;                                 // wave-uniform
+  const int bx = coords[3 * slot], by = coords[3 * slot + 1], bz = coords[3 * slot + 2];
+  const Slots n = neighbour_slots(bg, table, lane, bx, by, bz);
+  const int lx = lane & 7, ly = lane >> 3;
+  const int ix = bx * BR + lx, iy = by * BR + ly;
+  for (int lz = 0; lz < BR; ++lz) {
+    const int iz = bz * BR + lz;
+    int cnt = 0;
+    if (ix < g.nx && iy < g.ny && iz < g.nz) {
+      const int mask = sparse_cell_mask(g, n, ix, iy, iz, lx, ly, lz, pool, min_weight);
+      if (mask > 0 && mask < 255) {
+#pragma unroll
+        for (int t = 0; t < 6; ++t) cnt += TAB.ntri[t][tet_case(TAB, t, mask)];
+      }
+    }
+    counts[slot * BRICK_VOXELS + lz * 64 + lane] = cnt;
+  }
+}
+
+// emit_kernel on the brick pool; cells [n_tri]: the virtual linear index of every triangle's cell, for the caller's stable
+// sort into virtual-cell order (bricks leave in slot order).
+__global__ void __launch_bounds__(NT) sparse_emit_kernel(Grid g, BrickGrid bg, int64_t nslots, const int32_t* __restrict__ coords,
+                                                         const int32_t* __restrict__ table, const float* __restrict__ pool,
+                                                         float min_weight, const int32_t* __restrict__ counts,
+                                                         const int64_t* __restrict__ offsets, int64_t n_tri,
+                                                         int64_t* __restrict__ cells, int64_t* __restrict__ keys,
+                                                         float* __restrict__ pos, float* __restrict__ col) {
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  if (slot >= nslots) return;                                 // wave-uniform
+  const int bx = coords[3 * slot], by = coords[3 * slot + 1], bz = coords[3 * slot + 2];
+  const Slots n = neighbour_slots(bg, table, lane, bx, by, bz);
+  const int lx = lane & 7, ly = lane >> 3;
+  const int ix = bx * BR + lx, iy = by * BR + ly;
+  const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
+  for (int lz = 0; lz < BR; ++lz) {
+    const int iz = bz * BR + lz;
+    const int64_t cslot = slot * BRICK_VOXELS + lz * 64 + lane;
+    if (!(ix < g.nx && iy < g.ny && iz < g.nz) || counts[cslot] == 0) continue;
+    const int mask = sparse_cell_mask(g, n, ix, iy, iz, lx, ly, lz, pool, min_weight);
+    if (mask <= 0 || mask >= 255) continue;
+    const int64_t i = ((int64_t)iz * g.ny + iy) * g.nx + ix;
+    int64_t tri = offsets[cslot];
+    for (int t = 0; t < 6; ++t) {
+      const int m = tet_case(TAB, t, mask);
+      const int nt = TAB.ntri[t][m];
+      for (int j = 0; j < nt; ++j, ++tri) {
+        if (tri >= n_tri) return;                           // counts / offsets not of this volume: never write past the buffers
+        cells[tri] = i;
+        for (int k = 0; k < 3; ++k) {
+          const int e = TAB.edge[t][m][3 * j + k];
+          const int a = e >> 3, b = e & 7;
+          const int ax = a & 1, ay = (a >> 1) & 1, az = a >> 2, bx_ = b & 1, by_ = (b >> 1) & 1, bz_ = b >> 2;
+          const int64_t ia = i + ax + ay * sy + az * sz;
+          const int64_t oa = voxel_offset(n, lx + ax, ly + ay, lz + az), ob = voxel_offset(n, lx + bx_, ly + by_, lz + bz_);
+          if (oa < 0 || ob < 0) return;                     // a meshed cell has all 8 corners allocated (min_weight > 0)
+          const float ta = pool[oa], tb = pool[ob];
+          const float w = ta / (ta - tb);
+          const float pax = g.lox + ((float)(ix + ax) + 0.5f) * g.voxel, pbx = g.lox + ((float)(ix + bx_) + 0.5f) * g.voxel;
+          const float pay = g.loy + ((float)(iy + ay) + 0.5f) * g.voxel, pby = g.loy + ((float)(iy + by_) + 0.5f) * g.voxel;
+          const float paz = g.loz + ((float)(iz + az) + 0.5f) * g.voxel, pbz = g.loz + ((float)(iz + bz_) + 0.5f) * g.voxel;
+          const int64_t o = 3 * tri + k;
+          keys[o] = ia * 7 + ((a ^ b) - 1);
+          pos[3 * o] = pax + (pbx - pax) * w;
+          pos[3 * o + 1] = pay + (pby - pay) * w;
+          pos[3 * o + 2] = paz + (pbz - paz) * w;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float ca = pool[oa + (2 + c) * BRICK_VOXELS], cb = pool[ob + (2 + c) * BRICK_VOXELS];
+            col[3 * o + c] = ca + (cb - ca) * w;
+          }
+        }
+      }
+    }
+  }
+}
+
+// the box [x0, x0 + wx) x [y0, y0 + wy) x [z0, z0 + wz) of the virtual grid as dense planes; unallocated bricks read fresh
+__global__ void __launch_bounds__(NT) sparse_to_dense_kernel(BrickGrid bg, const int32_t* __restrict__ table,
+                                                             const float* __restrict__ pool, int x0, int y0, int z0, int wx, int wy,
+                                                             int64_t n, float* __restrict__ tsdf, float* __restrict__ weight,
+                                                             float* __restrict__ rgb) {
+  const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (i >= n) return;
+  const int ix = x0 + (int)(i % wx);
+  const int64_t r = i / wx;
+  const int iy = y0 + (int)(r % wy), iz = z0 + (int)(r / wy);
+  const int slot = table[((int64_t)(iz >> 3) * bg.nby + (iy >> 3)) * bg.nbx + (ix >> 3)];
+  float v[5] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (slot >= 0) {
+    const float* __restrict__ p = pool + (int64_t)slot * BRICK_FLOATS + ((iz & 7) * 64 + (iy & 7) * 8 + (ix & 7));
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] = p[k * BRICK_VOXELS];
+  }
+  tsdf[i] = v[0];
+  weight[i] = v[1];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) rgb[k * n + i] = v[2 + k];
+}
+
 static int g_dense = -1;
 
 static bool dense_form() {
@@ -381,6 +693,49 @@ static bool dense_form() {
 
 static bool grid_ok(int nx, int ny, int nz, float voxel) {
   return nx >= 1 && ny >= 1 && nz >= 1 && voxel > 0.0f && (int64_t)nx * ny * nz <= RTGS_TSDF_MAX_VOXELS;
+}
+
+static Frame make_frame(const float* lo3_host, int nx, int ny, int nz, float voxel, float trunc, float max_weight, int H, int W,
+                        float fx, float fy, float cx, float cy, const float* w2c12_host) {
+  Frame f;
+  for (int i = 0; i < 9; ++i) f.r[i] = w2c12_host[i];
+  for (int i = 0; i < 3; ++i) f.t[i] = w2c12_host[9 + i];
+  f.fx = fx; f.fy = fy; f.cx = cx; f.cy = cy; f.H = H; f.W = W; f.trunc = trunc; f.max_weight = max_weight;
+  // largest magnitude a camera-space coordinate can reach over the volume's voxel centres, per row
+  double ext[3];
+  const int n[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a) {
+    const double l = lo3_host[a], h = l + (double)n[a] * voxel;
+    ext[a] = fabs(l) > fabs(h) ? fabs(l) : fabs(h);
+  }
+  double B[3];
+  for (int row = 0; row < 3; ++row)
+    B[row] = fabs(f.r[3 * row]) * ext[0] + fabs(f.r[3 * row + 1]) * ext[1] + fabs(f.r[3 * row + 2]) * ext[2] + fabs(f.t[row]);
+  const double rel = 2e-5;                                 // ~170 ulp of float32: the chain has fewer than 16 roundings
+  f.mz = (float)(rel * (B[2] + trunc) + 1e-30);
+  f.mx = (float)(rel * (fabs(fx) * B[0] + (fabs(cx) + W + 1.0) * B[2]) + 1e-30);
+  f.my = (float)(rel * (fabs(fy) * B[1] + (fabs(cy) + H + 1.0) * B[2]) + 1e-30);
+  return f;
+}
+
+static bool sparse_grid_ok(int nx, int ny, int nz, float voxel) {
+  const int lim = 1 << 24;                                   // (float)i is exact
+  if (!(nx >= 1 && ny >= 1 && nz >= 1 && nx <= lim && ny <= lim && nz <= lim && voxel > 0.0f)) return false;
+  return (int64_t)((nx + BR - 1) / BR) * ((ny + BR - 1) / BR) * ((nz + BR - 1) / BR) <= RTGS_TSDF_SPARSE_MAX_BRICKS;
+}
+
+static BrickGrid brick_grid(int nx, int ny, int nz) { return BrickGrid{(nx + BR - 1) / BR, (ny + BR - 1) / BR, (nz + BR - 1) / BR}; }
+
+static bool frame_args_ok(float trunc, float max_weight, int H, int W) {
+  return trunc > 0.0f && max_weight >= 1.0f && H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffffLL;
+}
+
+// launch of one wave per item, WAVES waves a group; false when the grid would not fit
+static bool wave_groups(int64_t items, unsigned& groups) {
+  const int64_t n = (items + WAVES - 1) / WAVES;
+  if (n > 0x7fffffffLL) return false;
+  groups = (unsigned)n;
+  return true;
 }
 
 }  // namespace rtgs_tsdf
@@ -402,24 +757,7 @@ int rtgs_tsdf_integrate(float* tsdf, float* weight, float* rgb, int32_t nx, int3
       (int64_t)H * W > 0x7fffffffLL)
     return -1;
   const Grid g{nx, ny, nz, lo3_host[0], lo3_host[1], lo3_host[2], voxel};
-  Frame f;
-  for (int i = 0; i < 9; ++i) f.r[i] = w2c12_host[i];
-  for (int i = 0; i < 3; ++i) f.t[i] = w2c12_host[9 + i];
-  f.fx = fx; f.fy = fy; f.cx = cx; f.cy = cy; f.H = H; f.W = W; f.trunc = trunc; f.max_weight = max_weight;
-  // largest magnitude a camera-space coordinate can reach over the volume's voxel centres, per row
-  double ext[3];
-  const int n[3] = {nx, ny, nz};
-  for (int a = 0; a < 3; ++a) {
-    const double l = lo3_host[a], h = l + (double)n[a] * voxel;
-    ext[a] = fabs(l) > fabs(h) ? fabs(l) : fabs(h);
-  }
-  double B[3];
-  for (int row = 0; row < 3; ++row)
-    B[row] = fabs(f.r[3 * row]) * ext[0] + fabs(f.r[3 * row + 1]) * ext[1] + fabs(f.r[3 * row + 2]) * ext[2] + fabs(f.t[row]);
-  const double rel = 2e-5;                                 // ~170 ulp of float32: the chain has fewer than 16 roundings
-  f.mz = (float)(rel * (B[2] + trunc) + 1e-30);
-  f.mx = (float)(rel * (fabs(fx) * B[0] + (fabs(cx) + W + 1.0) * B[2]) + 1e-30);
-  f.my = (float)(rel * (fabs(fy) * B[1] + (fabs(cy) + H + 1.0) * B[2]) + 1e-30);
+  const Frame f = make_frame(lo3_host, nx, ny, nz, voxel, trunc, max_weight, H, W, fx, fy, cx, cy, w2c12_host);
   hipStream_t s = (hipStream_t)stream;
   const int64_t plane = (int64_t)nx * ny * nz;
   if (((uintptr_t)scratch & 15u) != 0) return -1;
@@ -467,6 +805,114 @@ int rtgs_tsdf_emit(const float* tsdf, const float* weight, const float* rgb, int
   const int64_t plane = (int64_t)nx * ny * nz;
   hipLaunchKernelGGL(emit_kernel, dim3((unsigned)((plane + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, g, tsdf, weight, rgb,
                      min_weight, counts, offsets, n_tri, keys, positions, colors);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_tsdf_sparse_mark(const int32_t* table, int32_t* flags, int32_t nx, int32_t ny, int32_t nz, const float* lo3_host,
+                          float voxel, float trunc, const float* depth, const float* color, int32_t H, int32_t W, float fx, float fy,
+                          float cx, float cy, const float* w2c12_host, void* scratch, void* stream) {
+  using namespace rtgs_tsdf;
+  if (!table || !flags || !lo3_host || !depth || !color || !w2c12_host || !scratch || ((uintptr_t)scratch & 15u) != 0) return -1;
+  if (!sparse_grid_ok(nx, ny, nz, voxel) || !frame_args_ok(trunc, 1.0f, H, W)) return -1;
+  const Grid g{nx, ny, nz, lo3_host[0], lo3_host[1], lo3_host[2], voxel};
+  const Frame f = make_frame(lo3_host, nx, ny, nz, voxel, trunc, 1.0f, H, W, fx, fy, cx, cy, w2c12_host);
+  const BrickGrid bg = brick_grid(nx, ny, nz);
+  const int64_t nbricks = (int64_t)bg.nbx * bg.nby * bg.nbz;
+  unsigned groups;
+  if (!wave_groups(nbricks, groups)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t* dmax = (uint32_t*)scratch;
+  float4* frame = (float4*)((char*)scratch + 16);
+  if (hipMemsetAsync(dmax, 0, sizeof(uint32_t), s) != hipSuccess) return -2;
+  if (hipMemsetAsync(flags, 0, (size_t)nbricks * sizeof(int32_t), s) != hipSuccess) return -2;
+  const int64_t npix = (int64_t)H * W;
+  const int64_t rb = (npix + NT - 1) / NT;
+  hipLaunchKernelGGL(pack_frame_kernel, dim3((unsigned)(rb < PACK_GROUPS ? rb : PACK_GROUPS)), dim3(NT), 0, s, depth, color, npix,
+                     frame, dmax);
+  hipLaunchKernelGGL(sparse_mark_kernel, dim3(groups), dim3(NT), 0, s, g, f, bg, nbricks, frame, dmax, table, flags);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_tsdf_sparse_allocate(int32_t* table, const int32_t* flags, const int64_t* offsets, int32_t nx, int32_t ny, int32_t nz,
+                              int64_t base, int64_t n_new, int64_t capacity, int32_t* coords, float* pool, void* stream) {
+  using namespace rtgs_tsdf;
+  if (n_new == 0) return 0;
+  if (!table || !flags || !offsets || !coords || !pool || ((uintptr_t)pool & 15u) != 0 || !sparse_grid_ok(nx, ny, nz, 1.0f)) return -1;
+  if (base < 0 || n_new < 0 || base + n_new > capacity || capacity > RTGS_TSDF_SPARSE_MAX_BRICKS) return -1;
+  const BrickGrid bg = brick_grid(nx, ny, nz);
+  const int64_t nbricks = (int64_t)bg.nbx * bg.nby * bg.nbz;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sparse_assign_kernel, dim3((unsigned)((nbricks + NT - 1) / NT)), dim3(NT), 0, s, bg, nbricks, flags, offsets,
+                     base, n_new, table, coords);
+  const int64_t n4 = n_new * (BRICK_FLOATS / 4);
+  if ((n4 + NT - 1) / NT > 0x7fffffffLL) return -1;
+  hipLaunchKernelGGL(sparse_fresh_kernel, dim3((unsigned)((n4 + NT - 1) / NT)), dim3(NT), 0, s,
+                     (float4*)(pool + base * BRICK_FLOATS), n4);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_tsdf_sparse_integrate(float* pool, const int32_t* coords, int64_t n_bricks, int32_t nx, int32_t ny, int32_t nz,
+                               const float* lo3_host, float voxel, float trunc, float max_weight, int32_t H, int32_t W, float fx,
+                               float fy, float cx, float cy, const float* w2c12_host, const void* scratch, void* stream) {
+  using namespace rtgs_tsdf;
+  if (n_bricks == 0) return 0;
+  if (!pool || !coords || !lo3_host || !w2c12_host || !scratch || ((uintptr_t)scratch & 15u) != 0) return -1;
+  if (n_bricks < 0 || n_bricks > RTGS_TSDF_SPARSE_MAX_BRICKS || !sparse_grid_ok(nx, ny, nz, voxel) ||
+      !frame_args_ok(trunc, max_weight, H, W))
+    return -1;
+  const Grid g{nx, ny, nz, lo3_host[0], lo3_host[1], lo3_host[2], voxel};
+  const Frame f = make_frame(lo3_host, nx, ny, nz, voxel, trunc, max_weight, H, W, fx, fy, cx, cy, w2c12_host);
+  unsigned groups;
+  if (!wave_groups(n_bricks, groups)) return -1;
+  hipLaunchKernelGGL(sparse_integrate_kernel, dim3(groups), dim3(NT), 0, (hipStream_t)stream, g, f, n_bricks, coords,
+                     (const float4*)((const char*)scratch + 16), (const uint32_t*)scratch, pool);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_tsdf_sparse_count(const float* pool, const int32_t* coords, const int32_t* table, int64_t n_bricks, int32_t nx,
+                           int32_t ny, int32_t nz, float min_weight, int32_t* counts, void* stream) {
+  using namespace rtgs_tsdf;
+  if (n_bricks == 0) return 0;
+  if (!pool || !coords || !table || !counts || n_bricks < 0 || n_bricks > RTGS_TSDF_SPARSE_MAX_BRICKS ||
+      !sparse_grid_ok(nx, ny, nz, 1.0f) || !(min_weight > 0.0f))
+    return -1;
+  const Grid g{nx, ny, nz, 0.0f, 0.0f, 0.0f, 1.0f};
+  unsigned groups;
+  if (!wave_groups(n_bricks, groups)) return -1;
+  hipLaunchKernelGGL(sparse_count_kernel, dim3(groups), dim3(NT), 0, (hipStream_t)stream, g, brick_grid(nx, ny, nz), n_bricks,
+                     coords, table, pool, min_weight, counts);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_tsdf_sparse_emit(const float* pool, const int32_t* coords, const int32_t* table, int64_t n_bricks, int32_t nx, int32_t ny,
+                          int32_t nz, const float* lo3_host, float voxel, float min_weight, const int32_t* counts,
+                          const int64_t* offsets, int64_t n_tri, int64_t* cells, int64_t* keys, float* positions, float* colors,
+                          void* stream) {
+  using namespace rtgs_tsdf;
+  if (n_tri == 0 || n_bricks == 0) return 0;
+  if (!pool || !coords || !table || !lo3_host || !counts || !offsets || !cells || !keys || !positions || !colors || n_tri < 0 ||
+      n_bricks < 0 || n_bricks > RTGS_TSDF_SPARSE_MAX_BRICKS || !sparse_grid_ok(nx, ny, nz, voxel) || !(min_weight > 0.0f))
+    return -1;
+  const Grid g{nx, ny, nz, lo3_host[0], lo3_host[1], lo3_host[2], voxel};
+  unsigned groups;
+  if (!wave_groups(n_bricks, groups)) return -1;
+  hipLaunchKernelGGL(sparse_emit_kernel, dim3(groups), dim3(NT), 0, (hipStream_t)stream, g, brick_grid(nx, ny, nz), n_bricks,
+                     coords, table, pool, min_weight, counts, offsets, n_tri, cells, keys, positions, colors);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_tsdf_sparse_to_dense(const float* pool, const int32_t* table, int32_t nx, int32_t ny, int32_t nz, const int32_t* window6_host,
+                              float* tsdf, float* weight, float* rgb, void* stream) {
+  using namespace rtgs_tsdf;
+  if (!pool || !table || !window6_host || !tsdf || !weight || !rgb || !sparse_grid_ok(nx, ny, nz, 1.0f)) return -1;
+  const int32_t* w = window6_host;
+  if (w[0] < 0 || w[1] <= w[0] || w[1] > nx || w[2] < 0 || w[3] <= w[2] || w[3] > ny || w[4] < 0 || w[5] <= w[4] || w[5] > nz)
+    return -1;
+  const int wx = w[1] - w[0], wy = w[3] - w[2], wz = w[5] - w[4];
+  const int64_t n = (int64_t)wx * wy * wz;
+  if ((n + NT - 1) / NT > 0x7fffffffLL) return -1;
+  hipLaunchKernelGGL(sparse_to_dense_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream,
+                     brick_grid(nx, ny, nz), table, pool, w[0], w[2], w[4], wx, wy, n, tsdf, weight, rgb);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

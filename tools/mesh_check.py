@@ -6,9 +6,14 @@
   * the streaming yardstick of the dense form: a volume that lies wholly inside the frustum and in front of the surface, so
     that every voxel is updated and the launch moves exactly 40 B per voxel;
   * extract_mesh of the fused room at both voxel sizes (count + scan + emit + weld), with V and F;
-  * the box-room end-to-end case of tests/test_mesh_gpu.py (sensor depth, 20 frames, 2 cm): vertex-to-wall statistics.
+  * the box-room end-to-end case of tests/test_mesh_gpu.py (sensor depth, 20 frames, 2 cm): vertex-to-wall statistics;
+  * the sparse leg (key "sparse"; alone with --sparse-only): SparseTsdfVolume against TsdfVolume's block form on the same
+    room and frames at 2 cm and 1 cm - per-frame integrate time (mark + scan + the host's read of the new-brick count +
+    allocate + integrate, on volumes that already hold the frames) in alternating blocks of the same run, extraction time,
+    pool bytes against dense bytes, and that the two meshes agree in V and F - and one sparse-only run at 4 mm, where the dense
+    planes (1300 x 800 x 1550 x 20 B) are over TsdfVolume's cap.
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
-blocks are reported.  python tools/mesh_check.py [OUT] [reps = 10] [blocks = 5]"""
+blocks are reported.  python tools/mesh_check.py [--sparse-only] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -39,10 +44,99 @@ def blocks_ms(fn, reps, blocks, warmup=3):
             "max_ms": round(float(np.max(out)), 4), "reps_per_block": reps, "blocks": blocks}
 
 
+def _summary(ms, reps):
+    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4),
+            "max_ms": round(float(np.max(ms)), 4), "reps_per_block": reps, "blocks": len(ms)}
+
+
+def alternating_blocks_ms(fns, reps, blocks, warmup=3):
+    """blocks_ms for several forms in one run: block k of every form before block k + 1 of any."""
+    for fn in fns.values():
+        for i in range(warmup):
+            fn(i)
+    torch.cuda.synchronize()
+    out = {name: [] for name in fns}
+    for _ in range(blocks):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(reps):
+                fn(i)
+            b.record()
+            b.synchronize()
+            out[name].append(a.elapsed_time(b) / reps)
+    return {name: _summary(ms, reps) for name, ms in out.items()}
+
+
+def _timed_extract(vol, runs=3):
+    ext = []
+    for _ in range(runs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        v, f, c = vol.extract_mesh()
+        torch.cuda.synchronize()
+        ext.append(time.perf_counter() - t0)
+    return {"median_s": round(float(np.median(ext)), 4), "min_s": round(min(ext), 4), "max_s": round(max(ext), 4), "runs": runs,
+            "V": int(v.shape[0]), "F": int(f.shape[0])}
+
+
+def _fuse_all(vol, frames, cam):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for d, c, p in frames:
+        vol.integrate(d, c, cam, p)
+    torch.cuda.synchronize()
+    return round((time.perf_counter() - t0) * 1e3 / len(frames), 4)
+
+
+def sparse_leg(dev, cam, frames, lo, hi, reps, blocks):
+    res = {"timing": "device events around reps integrate calls, sparse and dense (block form) blocks alternating; the sparse "
+                     "call holds one host synchronisation (the new-brick count)"}
+    for voxel in (0.02, 0.01):
+        sparse = meshing.SparseTsdfVolume(lo, hi, voxel, device=dev)
+        dense = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        entry = {"dims": list(sparse.dims), "first_pass_wall_ms_per_frame": {"sparse": _fuse_all(sparse, frames, cam),
+                                                                             "dense": _fuse_all(dense, frames, cam)}}
+        call = lambda vol: (lambda i: vol.integrate(*frames[i % len(frames)][:2], cam, frames[i % len(frames)][2]))
+        entry["integrate"] = alternating_blocks_ms({"sparse": call(sparse), "dense_block": call(dense)}, reps, blocks)
+        entry["sparse_over_dense_time_ratio"] = round(entry["integrate"]["sparse"]["median_ms"]
+                                                      / entry["integrate"]["dense_block"]["median_ms"], 3)
+        n_table = int(np.prod(sparse.brick_dims))
+        entry.update({"bricks": sparse.n_bricks, "brick_share": round(sparse.n_bricks / n_table, 4),
+                      "brick_bytes": sparse.n_bricks * meshing.BRICK_BYTES, "pool_bytes": sparse.pool_bytes,
+                      "table_bytes": 4 * n_table, "dense_bytes": sparse.dense_bytes,
+                      "pool_over_dense_bytes": round(sparse.pool_bytes / sparse.dense_bytes, 4),
+                      "updated_share_dense": round(float((dense.weight > 0).float().mean()), 4)})
+        entry["extract"] = {"sparse": _timed_extract(sparse), "dense": _timed_extract(dense)}
+        entry["same_V_and_F"] = all(entry["extract"]["sparse"][k] == entry["extract"]["dense"][k] for k in ("V", "F"))
+        res[f"room_voxel_{voxel:g}"] = entry
+        del sparse, dense
+        torch.cuda.empty_cache()
+    voxel = 0.004
+    refused = None
+    try:
+        meshing.TsdfVolume(lo, hi, voxel, device=dev)
+    except ValueError as e:
+        refused = str(e)
+    sparse = meshing.SparseTsdfVolume(lo, hi, voxel, device=dev)
+    entry = {"dims": list(sparse.dims), "dense_refuses": refused, "first_pass_wall_ms_per_frame": _fuse_all(sparse, frames, cam)}
+    entry["integrate"] = blocks_ms(lambda i: sparse.integrate(*frames[i % len(frames)][:2], cam, frames[i % len(frames)][2]), reps,
+                                   blocks)
+    n_table = int(np.prod(sparse.brick_dims))
+    entry.update({"bricks": sparse.n_bricks, "brick_share": round(sparse.n_bricks / n_table, 4),
+                  "brick_bytes": sparse.n_bricks * meshing.BRICK_BYTES, "pool_bytes": sparse.pool_bytes, "table_bytes": 4 * n_table,
+                  "dense_bytes": sparse.dense_bytes, "pool_over_dense_bytes": round(sparse.pool_bytes / sparse.dense_bytes, 4)})
+    entry["extract"] = _timed_extract(sparse)
+    res[f"room_voxel_{voxel:g}_sparse_only"] = entry
+    return res
+
+
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else None
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-    blocks = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    argv = [a for a in sys.argv[1:] if a != "--sparse-only"]
+    sparse_only = len(argv) != len(sys.argv) - 1
+    out_path = argv[0] if len(argv) > 0 else None
+    reps = int(argv[1]) if len(argv) > 1 else 10
+    blocks = int(argv[2]) if len(argv) > 2 else 5
     dev = torch.device("cuda", 0)
     cam = synth.REPLICA
     res = {"device": torch.cuda.get_device_name(dev), "camera": [cam.W, cam.H], "bytes_per_updated_voxel": 40}
@@ -54,6 +148,9 @@ def main():
     frame_bytes = cam.H * cam.W * 16
     half = (2.5, 1.5, 3.0)
     lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
+    if sparse_only:
+        res["sparse"] = sparse_leg(dev, cam, frames, lo, hi, reps, blocks)
+        return _finish(res, out_path)
     for voxel in (0.02, 0.01):
         vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
         n = vol.dims[0] * vol.dims[1] * vol.dims[2]
@@ -121,6 +218,11 @@ def main():
                                             device=dev)
     res["box_room_sensor_2cm"] = {"report": report, "vertex_to_wall_m": tr.wall_stats(v.cpu().numpy()),
                                   "numpy_reference_on_cpu": {"mean": 0.01126, "p99": 0.03607, "max": 0.03778, "covered": 0.1844}}
+    res["sparse"] = sparse_leg(dev, cam, frames, lo, hi, reps, blocks)
+    _finish(res, out_path)
+
+
+def _finish(res, out_path):
     line = json.dumps(res, default=float)
     print(line)
     if out_path:
