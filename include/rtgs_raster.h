@@ -254,6 +254,36 @@ int rtgs_raster_speculation_stats_ctx(rtgs_ctx* ctx, int64_t* out3_host);
  * which were redone. */
 void rtgs_raster_set_plain_onepass_ctx(rtgs_ctx* ctx, int enable);
 int rtgs_raster_plain_stats_ctx(rtgs_ctx* ctx, int64_t* out2_host);
+/* The cull cache.  Every map iteration opens with two passes over all P Gaussians - the cull (depth cull, radius, tile rect,
+ * depth bin, projected centre of every Gaussian) and the depth histograms - whose inputs hardly change between steps on one
+ * view: a row's result depends on the view, the intrinsics and that row's position, scale and rotation, and the step's tail
+ * moves a few thousand rows of a large map.  After a speculative forward (RTGS_FWD_SPECULATE) that took the near slice to
+ * the end (kind 1) or ran the single pass over the visible list (kind 2), the context remembers that radii, out_radii,
+ * tiles_touched, depth bins, centres and the three histograms in the geometry buffer are complete for a KEY: the geometry
+ * buffer (pointer, size), P, the image size, fx fy cx cy tanfovx tanfovy scale_modifier color_sigma, the device pointers of
+ * the view matrix, means3D, scales, rotations and out_radii, the stream, the near-slice mode and budget, the kind, and
+ * the caller's map epoch.  The next speculative forward of that kind with an equal key launches ONE kernel, recull_rows, in
+ * place of both passes: it clears what the cull clears and recomputes, with the cull's own code, the rows the tail marked
+ * (bit-identical to a full cull).  The view matrix may be rewritten in place: recull_rows compares it with a device copy of
+ * the last full cull's and, if it moved, raises the forward's speculation word - rtgs_raster_forward_verify_ctx then
+ * returns 1 and the step is redone plainly.  EVERY other forward on the context disarms the cache (plain renders, forwards
+ * that cannot speculate, another kind / P / image, the sort path, debug mode, the redo of a failed guess).
+ *   set_map_epoch      one-shot, consumed by the next forward: the caller's promise that between two forwards given the SAME
+ *                      non-zero epoch nothing wrote positions, scales or rotations except a tail that was handed
+ *                      rtgs_raster_cull_marks_ctx().  0 (the default) = that forward neither arms nor uses the cache.
+ *   cull_marks         NULL unless the most recent forward left the cache armed; else one byte per Gaussian: whoever steps
+ *                      row r afterwards sets byte r (rtgs_map_fused_tail_marked, rtgs_map_tail_rows_marked).
+ *   set_cull_cache     0 = off (RTGS_CULL_CACHE=0 at load time); default on.
+ *   set_cull_cache_check   1 = on every hit ALSO run the full cull and slice_hist into scratch copies and compare all seven
+ *                      arrays word for word on the device (RTGS_CULL_CACHE_CHECK=1 at load time) - slow, the proof that a
+ *                      hit equals a full cull.
+ *   cull_cache_stats   [0] hits [1] full culls that armed the cache [2] times an armed cache was dropped [3] redos because
+ *                      the view moved [4] differing words the self-check has seen (waits for the device). */
+void rtgs_raster_set_cull_cache_ctx(rtgs_ctx* ctx, int enable);
+void rtgs_raster_set_cull_cache_check_ctx(rtgs_ctx* ctx, int enable);
+void rtgs_raster_set_map_epoch_ctx(rtgs_ctx* ctx, uint64_t epoch);
+uint8_t* rtgs_raster_cull_marks_ctx(rtgs_ctx* ctx);
+int rtgs_raster_cull_cache_stats_ctx(rtgs_ctx* ctx, int64_t* out5_host);
 /* Byte offsets inside the image buffer - [0] tile ranges (uint2 per tile), [1] n_contrib (u32 per pixel), [2] BwdInfo,
  * [3] tile walk (u32 per tile: bits 0..1 = 0 strip / 1 row-granular / 2 MFMA, bits 8.. the measured share in 1/1000),
  * [4] total size, [5] list position of every pixel's depth owner (u32 per pixel). */
@@ -336,6 +366,16 @@ int rtgs_map_tail_rows(float* xyz, float* shs, float* raw8, const float* g_opaci
                        uint8_t* ever_xyz, uint8_t* ever_shs, uint8_t* ever_raw8, int64_t rows, int32_t step, float beta1,
                        float beta2, float eps, const rtgs_attach* attach, float* confidence, const uint32_t* skip_flag,
                        const rtgs_activated* refresh, void* stream);
+/* ... that also sets marks[r] (nullable; one byte per row, rtgs_raster_cull_marks_ctx moved to the first row) for every
+ * row whose xyz or raw8 it steps. */
+int rtgs_map_tail_rows_marked(float* xyz, float* shs, float* raw8, const float* g_opacity, const float* g_scales,
+                              const float* g_rotations, const float* g_normal, const float* g_xyz, const float* g_shs,
+                              float* g_raw8, const uint8_t* row_state, float* m_xyz, float* v_xyz, float* m_shs,
+                              float* v_shs, float* m_raw8, float* v_raw8, const float* lr_xyz, const float* lr_shs,
+                              const float* lr_raw8, uint8_t* ever_xyz, uint8_t* ever_shs, uint8_t* ever_raw8, int64_t rows,
+                              int32_t step, float beta1, float beta2, float eps, const rtgs_attach* attach,
+                              float* confidence, const uint32_t* skip_flag, const rtgs_activated* refresh, uint8_t* marks,
+                              void* stream);
 
 /* Fused SLAM loss: the image terms of Mapping.loss_update (mapper.py:402-448) - value and BOTH image gradients
  * (dL/dC [3,H,W], dL/dD [1,H,W]), so the autograd graph of ~40 elementwise launches collapses into a few kernels.
@@ -429,6 +469,10 @@ typedef struct rtgs_map_step_args {
    * live_counts (nullable, device uint32[2]): += {rows with gradient, rows stepped} of the fused tail. */
   int32_t tail_mode;
   uint32_t* live_counts;
+  /* The cull cache (rtgs_raster_set_map_epoch_ctx): the caller's promise that since the last rtgs_slam_map_step_ctx it
+   * called with the SAME non-zero value nothing but that call's own tail wrote xyz, the activated scales or rotations.
+   * 0 = no promise (every step culls the whole map). */
+  uint64_t map_epoch;
 } rtgs_map_step_args;
 /* The normal term on its own: value added to loss4[0], gradient added to d_normal[owner] with the row marked live in
  * row_state (nullable: dense gradients) - a row that carried no gradient is all-zero by the arena's invariant, so marking
@@ -466,12 +510,18 @@ int rtgs_map_fused_tail(const rtgs_raster_settings* settings, const rtgs_map_ste
 int rtgs_map_fused_tail_hint(const rtgs_raster_settings* settings, const rtgs_map_step_args* args, void* geom_buffer,
                              const void* image_buffer, const uint32_t* spec_fail, uint32_t* live_counts2,
                              uint32_t listed_hint, void* stream);
+/* ... that also sets marks[r] (nullable; rtgs_raster_cull_marks_ctx of the step's forward) for every row whose xyz or raw8
+ * it steps. */
+int rtgs_map_fused_tail_marked(const rtgs_raster_settings* settings, const rtgs_map_step_args* args, void* geom_buffer,
+                               const void* image_buffer, const uint32_t* spec_fail, uint32_t* live_counts2,
+                               uint32_t listed_hint, uint8_t* marks, void* stream);
 /* Gaussians the last VERIFIED speculative forward on the context listed for binning (near-slice work list, or the list of
  * the visible ones when the slice was declined); 0 when unknown. */
 uint32_t rtgs_raster_last_listed_ctx(rtgs_ctx* ctx);
 /* Byte offsets of what a backward's walk leaves for a fused consumer: [0] clamp flags (u8[P], geometry buffer), [1] first
  * gradient slot per Gaussian (u32[P], geometry), [2] slots taken per Gaussian (u32[P], geometry), [3] BwdInfo (image
- * buffer), [4] touched bytes (u8[P], inside grad_scratch, behind the P SplatGrad records). */
+ * buffer), [4] touched bytes (u8[P], inside grad_scratch, behind the P SplatGrad records), [5] radii (i32[P], geometry),
+ * [6] the cull cache's mark bytes (u8[P], geometry). */
 int rtgs_raster_backward_buffers(int32_t P, int32_t image_height, int32_t image_width, size_t* out8_host);
 /* The geometry / binning / image buffers the most recent forward on the context obtained from its resize callbacks
  * (out3_host[0..2]) - for a native caller that enqueues forward and backward back to back and would otherwise have to

@@ -79,7 +79,7 @@ class MapStepArgsC(C.Structure):
         + [("geom_resize", RESIZE_FN), ("geom_user", C.c_void_p), ("binning_resize", RESIZE_FN),
            ("binning_user", C.c_void_p), ("image_resize", RESIZE_FN), ("image_user", C.c_void_p)]
         + [("normal_weight", C.c_float), ("gt_normal", C.c_void_p), ("train_begin", C.c_int32), ("train_end", C.c_int32),
-           ("tail_mode", C.c_int32), ("live_counts", C.c_void_p)])
+           ("tail_mode", C.c_int32), ("live_counts", C.c_void_p), ("map_epoch", C.c_uint64)])
 
 
 _SIGNATURES = {
@@ -109,6 +109,14 @@ _SIGNATURES = {
     "rtgs_map_fused_tail": (C.c_int, [C.POINTER(RasterSettingsC), C.POINTER(MapStepArgsC), _P, _P, _P, _P, _P]),
     "rtgs_map_fused_tail_hint": (C.c_int, [C.POINTER(RasterSettingsC), C.POINTER(MapStepArgsC), _P, _P, _P, _P, C.c_uint32, _P]),
     "rtgs_raster_last_listed_ctx": (C.c_uint32, [_P]),
+    "rtgs_raster_set_cull_cache_ctx": (None, [_P, C.c_int]),
+    "rtgs_raster_set_cull_cache_check_ctx": (None, [_P, C.c_int]),
+    "rtgs_raster_cull_cache_stats_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "rtgs_raster_set_map_epoch_ctx": (None, [_P, C.c_uint64]),
+    "rtgs_raster_cull_marks_ctx": (C.c_void_p, [_P]),
+    "rtgs_map_tail_rows_marked": (C.c_int, [_P] * 23 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                            C.POINTER(AttachC), _P, _P, C.POINTER(ActivatedC), _P, _P]),
+    "rtgs_map_fused_tail_marked": (C.c_int, [C.POINTER(RasterSettingsC), C.POINTER(MapStepArgsC), _P, _P, _P, _P, C.c_uint32, _P, _P]),
     "rtgs_stream_create_reserving": (C.c_void_p, [C.c_int]),
     "rtgs_stream_destroy": (None, [_P]),
     "rtgs_raster_backward_buffers": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),

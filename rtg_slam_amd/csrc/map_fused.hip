@@ -51,6 +51,7 @@ struct FusedArgs {
   float *act_opacity, *act_scales, *act_normal;
   float4* act_rots;
   uint32_t* live_counts;         // nullable: [0] += rows with gradient, [1] += rows stepped
+  uint8_t* marks;                // nullable: one byte per row of the map, set for every row whose xyz or raw8 is stepped (the cull cache)
   int t0, rows;                  // the trainable rows [t0, t0 + rows)
 };
 
@@ -217,6 +218,7 @@ __global__ void __launch_bounds__(256) map_fused_tail_kernel(FusedArgs a) {
           }
         }
         const bool grad = rgrad || sel;
+        if (a.marks && (grad || e_raw8 != 0 || e_xyz != 0)) a.marks[r] = 1;   // position, scale or rotation moves: the next cull redoes this row
         // ---- raw8: activation backward (+ attach), Adam, re-activation
         if (grad || e_raw8 != 0) {
           float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
@@ -317,6 +319,12 @@ extern "C" int rtgs_map_fused_tail(const rtgs_raster_settings* settings, const r
 extern "C" int rtgs_map_fused_tail_hint(const rtgs_raster_settings* settings, const rtgs_map_step_args* s, void* geom_buffer,
                                         const void* image_buffer, const uint32_t* spec_fail, uint32_t* live_counts2,
                                         uint32_t listed_hint, void* stream) {
+  return rtgs_map_fused_tail_marked(settings, s, geom_buffer, image_buffer, spec_fail, live_counts2, listed_hint, nullptr, stream);
+}
+
+extern "C" int rtgs_map_fused_tail_marked(const rtgs_raster_settings* settings, const rtgs_map_step_args* s, void* geom_buffer,
+                                          const void* image_buffer, const uint32_t* spec_fail, uint32_t* live_counts2,
+                                          uint32_t listed_hint, uint8_t* marks, void* stream) {
   using namespace rtgs;
   if (!settings || !s || !geom_buffer || !image_buffer) return RTGS_E_INVALID;
   const int32_t P = s->P;
@@ -365,6 +373,7 @@ extern "C" int rtgs_map_fused_tail_hint(const rtgs_raster_settings* settings, co
   a.confidence = s->confidence;
   a.act_opacity = s->opacity; a.act_scales = s->scales; a.act_normal = s->normal; a.act_rots = (float4*)s->rotations;
   a.live_counts = live_counts2;
+  a.marks = marks;
   a.t0 = t0; a.rows = t1 - t0;
   // chunk size from the number of Gaussians the last verified forward LISTED for binning (the rows with gradient are among
   // them; 0 = unknown): the largest chunk that still expects at most one wave pass (64 live rows) per workgroup

@@ -112,6 +112,7 @@ struct TailArgs {
   // optional: the caller's activated copies of raw8, re-activated for every row whose raw8 is stepped
   float *act_opacity, *act_scales, *act_normal;
   float4* act_rots;
+  uint8_t* marks;                 // nullable: one byte per row, set for every row whose xyz or raw8 is stepped (the cull cache)
 };
 
 __device__ __forceinline__ bool attach_selected(const float4 init_lo) {
@@ -163,6 +164,7 @@ __global__ void __launch_bounds__(256) map_tail_rows_kernel(TailArgs a) {
         hi.x += at_hi.x; hi.y += at_hi.y; hi.z += at_hi.z; hi.w += at_hi.w;
         a.g_raw8[2 * r] = lo; a.g_raw8[2 * r + 1] = hi;
       }
+      if (a.marks && (grad || e_raw8 != 0 || e_xyz != 0)) a.marks[r] = 1;   // position, scale or rotation moves
       if (grad || e_raw8 != 0) {                                 // raw8: 8 columns, this lane
         if (e_raw8 == 0) a.ever_raw8[r] = 1;
         const float4 g0 = lo, g1 = hi;                           // what was just stored - or the all-zero row of state 0
@@ -362,6 +364,21 @@ extern "C" int rtgs_map_tail_rows(float* xyz, float* shs, float* raw8, const flo
                                   int64_t rows, int32_t step, float beta1, float beta2, float eps,
                                   const rtgs_attach* attach, float* confidence, const uint32_t* skip_flag,
                                   const rtgs_activated* refresh, void* stream) {
+  return rtgs_map_tail_rows_marked(xyz, shs, raw8, g_opacity, g_scales, g_rotations, g_normal, g_xyz, g_shs, g_raw8, row_state,
+                                   m_xyz, v_xyz, m_shs, v_shs, m_raw8, v_raw8, lr_xyz, lr_shs, lr_raw8, ever_xyz, ever_shs,
+                                   ever_raw8, rows, step, beta1, beta2, eps, attach, confidence, skip_flag, refresh, nullptr,
+                                   stream);
+}
+
+extern "C" int rtgs_map_tail_rows_marked(float* xyz, float* shs, float* raw8, const float* g_opacity, const float* g_scales,
+                                         const float* g_rotations, const float* g_normal, const float* g_xyz,
+                                         const float* g_shs, float* g_raw8, const uint8_t* row_state, float* m_xyz,
+                                         float* v_xyz, float* m_shs, float* v_shs, float* m_raw8, float* v_raw8,
+                                         const float* lr_xyz, const float* lr_shs, const float* lr_raw8, uint8_t* ever_xyz,
+                                         uint8_t* ever_shs, uint8_t* ever_raw8, int64_t rows, int32_t step, float beta1,
+                                         float beta2, float eps, const rtgs_attach* attach, float* confidence,
+                                         const uint32_t* skip_flag, const rtgs_activated* refresh, uint8_t* marks,
+                                         void* stream) {
   if (rows < 0 || step < 1) return -1;
   if (rows == 0) return 0;
   if (!xyz || !shs || !raw8 || !g_opacity || !g_scales || !g_rotations || !g_normal || !g_xyz || !g_shs || !g_raw8 ||
@@ -378,6 +395,7 @@ extern "C" int rtgs_map_tail_rows(float* xyz, float* shs, float* raw8, const flo
   a.rows = rows; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
   a.init_xyz = nullptr; a.init_raw8 = nullptr; a.attach_info = nullptr; a.confidence = confidence;
   a.skip_flag = skip_flag;
+  a.marks = marks;
   a.act_opacity = a.act_scales = a.act_normal = nullptr; a.act_rots = nullptr;
   if (refresh) {
     if (!refresh->opacity || !refresh->scales || !refresh->rotations || !refresh->normal) return -1;

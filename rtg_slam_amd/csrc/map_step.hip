@@ -72,14 +72,17 @@ static int map_step_once(rtgs_ctx* ctx, const rtgs_map_step_args* a, int64_t* nu
   // one fused kernel for everything per-Gaussian behind the tile walk, unless the caller asks for the three-kernel form or
   // the normal term (which adds to the arena's d_normal rows) is on
   const bool fused = a->tail_mode == 0 && !(a->normal_weight > 0.f && a->gt_normal);
+  // the caller's promise for the cull cache (rtgs_map_step_args.map_epoch): only a speculative forward may use it, and both
+  // tails below leave a mark for every row they step while the cache is armed
+  rtgs_raster_set_map_epoch_ctx(ctx, speculate ? a->map_epoch : 0u);
   int rc = map_step_front(ctx, a, num_rendered_host, speculate ? RTGS_FWD_SPECULATE : 0, stream, fused);
   if (rc != RTGS_OK) return rc;
   if ((a->train_begin != 0 || a->train_end != 0) && a->train_end == a->train_begin) return RTGS_OK;   // empty range: no tail
   if (fused) {
     void* bufs[3];
     if (rtgs_raster_last_buffers_ctx(ctx, bufs) != RTGS_OK) return RTGS_E_ALLOC;
-    return rtgs_map_fused_tail_hint(a->settings, a, bufs[0], bufs[2], rtgs_raster_spec_fail_ptr_ctx(ctx), a->live_counts,
-                                    rtgs_raster_last_listed_ctx(ctx), stream);
+    return rtgs_map_fused_tail_marked(a->settings, a, bufs[0], bufs[2], rtgs_raster_spec_fail_ptr_ctx(ctx), a->live_counts,
+                                      rtgs_raster_last_listed_ctx(ctx), rtgs_raster_cull_marks_ctx(ctx), stream);
   }
   const int32_t P = a->P;
   // activation backward (+ attach gradient) + Adam on the three block tensors (+ confidence increment), one launch;
@@ -90,11 +93,13 @@ static int map_step_once(rtgs_ctx* ctx, const rtgs_map_step_args* a, int64_t* nu
   if (a->train_begin != 0 || a->train_end != 0) { t0 = a->train_begin; t1 = a->train_end; }
   const size_t o = (size_t)t0;
   const rtgs_activated act{a->opacity + o, a->scales + 3 * o, a->rotations + 4 * o, a->normal + 3 * o};
-  rc = rtgs_map_tail_rows(a->xyz + 3 * o, a->shs + 48 * o, a->raw8 + 8 * o, a->d_opacity + o, a->d_scales + 3 * o,
+  uint8_t* const marks = rtgs_raster_cull_marks_ctx(ctx);
+  rc = rtgs_map_tail_rows_marked(a->xyz + 3 * o, a->shs + 48 * o, a->raw8 + 8 * o, a->d_opacity + o, a->d_scales + 3 * o,
                           a->d_rotations + 4 * o, a->d_normal + 3 * o, a->d_xyz + 3 * o, a->d_shs + 48 * o, a->d_raw8 + 8 * o,
                           a->row_state + o, a->m_xyz, a->v_xyz, a->m_shs, a->v_shs, a->m_raw8, a->v_raw8,
                           a->lr_xyz, a->lr_shs, a->lr_raw8, a->ever_xyz, a->ever_shs, a->ever_raw8, (int64_t)(t1 - t0), a->step,
-                          a->beta1, a->beta2, a->eps, a->attach, a->confidence, rtgs_raster_spec_fail_ptr_ctx(ctx), &act, stream);
+                          a->beta1, a->beta2, a->eps, a->attach, a->confidence, rtgs_raster_spec_fail_ptr_ctx(ctx), &act,
+                          marks ? marks + o : nullptr, stream);
   return rc != 0 ? RTGS_E_HIP : RTGS_OK;
 }
 

@@ -49,7 +49,13 @@ void launch_slice_compact(int, SliceSel, uint32_t*, uint32_t*, const uint32_t*, 
 void launch_slice_publish(int, const int32_t*, const int32_t*, const uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t*, hipStream_t,
                           const uint32_t* seg_count = nullptr);
 void launch_preprocess_cull(const RasterParams&, const float*, const float*, const float*, uint32_t*, int32_t*, int32_t*,
-                            uint32_t*, int, uint8_t*, float2*, hipStream_t);
+                            uint32_t*, int, uint8_t*, float2*, uint32_t*, hipStream_t);
+void launch_recull_rows(const RasterParams&, const float*, const float*, const float*, uint32_t*, int32_t*, int32_t*, uint32_t*,
+                        int, uint8_t*, float2*, uint32_t*, unsigned long long*, uint8_t*, const float*, int, BwdInfoInit,
+                        hipStream_t);
+void launch_cull_check(int, const uint32_t*, const uint32_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
+                       const uint8_t*, const uint8_t*, const float2*, const float2*, const uint32_t*, const uint32_t*,
+                       const uint32_t*, unsigned long long*, hipStream_t);
 void launch_preprocess_shade(const RasterParams&, const float*, const float*, const float*, const float*, const float*,
                              const float*, Splat*, int32_t*, uint8_t*, float2*, SliceList, SliceSel, size_t, hipStream_t);
 void launch_bin_tilescan(int, const uint32_t*, uint2*, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*,
@@ -138,6 +144,27 @@ struct rtgs_ctx {
   Plan plan_plain0;                    // ... on maps below the large-map size (kind 0: one pass over every Gaussian)
   bool plain_onepass = true;           // RTGS_PLAIN_ONEPASS=0: count / scan / scatter with the two host waits, as before round 6
   int64_t plain_stats[2] = {0, 0};     // immediate one-pass forwards, those that had to be redone
+  // ---- the cull cache (see rtgs_raster.h: rtgs_raster_set_cull_cache_ctx) ----
+  // After a speculative forward of kind 1 or 2 ran the full cull and slice_hist, the per-row cull results in the geometry
+  // buffer (radii, out_radii, tiles_touched, zbin, uv) and the three depth histograms are complete for `key`.  The next
+  // such forward with an equal key launches recull_rows in their place: only the rows the map step's tail marked since
+  // are recomputed.  EVERY other forward on the context disarms the cache.
+  struct CullKey {
+    const void *geom, *view, *means, *scales, *rots, *out_radii, *stream;
+    uint64_t geom_bytes, epoch;
+    int32_t P, H, W, kind, slice_mode, slice_budget;
+    float fx, fy, cx, cy, tanfovx, tanfovy, scale_modifier, color_sigma;
+  };
+  struct CullCache {
+    bool enabled = true, check = false, armed = false;
+    CullKey key = {};
+    uint8_t* marks = nullptr;          // inside the key's geometry buffer; what the tails write while the cache is armed
+    uint64_t next_epoch = 0;           // one-shot, consumed by the next forward (0 = that forward may neither arm nor hit)
+    int64_t stats[4] = {0, 0, 0, 0};   // hits, full culls that armed the cache, times an armed cache was dropped, view redos
+    char* scratch = nullptr;           // self-check: a full cull's outputs
+    size_t scratch_bytes = 0;
+    unsigned long long* mismatches = nullptr;   // device word: differing words the self-check has seen
+  } cull;
 };
 
 namespace rtgs {
@@ -151,6 +178,8 @@ static rtgs_ctx* default_ctx() {
     if (const char* e = getenv("RTGS_BIN_ONEPASS")) n->onepass = atoi(e) != 0;
     if (const char* e = getenv("RTGS_PLAIN_ONEPASS")) n->plain_onepass = atoi(e) != 0;
     if (const char* e = getenv("RTGS_BWD_WALK")) { const int m = atoi(e); n->bwd_walk = (m >= 1 && m <= 4) ? m : 0; }
+    if (const char* e = getenv("RTGS_CULL_CACHE")) n->cull.enabled = atoi(e) != 0;
+    if (const char* e = getenv("RTGS_CULL_CACHE_CHECK")) n->cull.check = atoi(e) != 0;
     return n;
   }();
   return c;
@@ -236,9 +265,7 @@ static GeomLayout geom_layout(int32_t P, int gx, int gy, int budget) {
     off = L.tile_count + nt * sizeof(uint32_t);  // (re-lays cursor / info / block_counts behind the zeroed span)
     L.tile_count1 = off; off += nt * sizeof(uint32_t);
     L.ranges1_bwd = off; off += nt * sizeof(uint2);
-    L.slice_hist = off; off += 2 * SLICE_BINS * sizeof(uint32_t);
-    L.slice_cover = off; off += SLICE_BINS * sizeof(unsigned long long);
-    L.slice_ctr = off; off += 8 * sizeof(uint32_t);   // [0] unfinished tiles [2] slice list length [3] cut [4] slot cursor of the slice, or visible-list length with [5] its slot cursor
+    L.slice_ctr = off; off += 8 * sizeof(uint32_t);   // [0] unfinished tiles [2] slice list length [3] cut [4] slot cursor of the slice, or visible-list length with [5] its slot cursor [6] speculation word [7] raised with it by recull_rows: the view moved
     L.slot_count = off; off += Pn * sizeof(uint32_t);   // zero between calls: cleared here, and again by grad_reduce
     L.zero_end = off; off = align_up(off);
     L.cursor = off; off = align_up(off + nt * sizeof(uint32_t));
@@ -249,6 +276,11 @@ static GeomLayout geom_layout(int32_t P, int gx, int gy, int budget) {
     L.ranges1 = off; off = align_up(off + nt * sizeof(uint2));
     L.mask2 = off; off = align_up(off + nt * sizeof(int32_t));
     L.uv = off; off = align_up(off + Pn * sizeof(float2));
+    // outside the zeroed span (see GeomLayout): the full cull clears the histograms through its second span
+    L.slice_hist = off; off += 2 * SLICE_BINS * sizeof(uint32_t);
+    L.slice_cover = off; off = align_up(off + SLICE_BINS * sizeof(unsigned long long));
+    L.cull_marks = off; off = align_up(off + Pn + 16);
+    L.cull_view = off; off = align_up(off + 16 * sizeof(float));
     L.slice_cap = nt * (size_t)(budget > 0 ? budget : 1);
     L.slice_max_list = L.slice_cap < 65536 ? L.slice_cap : 65536;   // every listed Gaussian covers >= 1 tile
     if (L.slice_max_list > Pn) L.slice_max_list = Pn;
@@ -364,13 +396,15 @@ const char* rtgs_version(void) { return "rtgs-hip 0.2.0 (gfx950)"; }
 
 rtgs_ctx* rtgs_ctx_create(void) {
   rtgs_ctx* c = new (std::nothrow) rtgs_ctx();
-  if (c) { c->slice_mode = default_ctx()->slice_mode; c->slice_budget = default_ctx()->slice_budget; c->bwd_walk = default_ctx()->bwd_walk; c->onepass = default_ctx()->onepass; c->speculation = default_ctx()->speculation; c->plain_onepass = default_ctx()->plain_onepass; }
+  if (c) { c->slice_mode = default_ctx()->slice_mode; c->slice_budget = default_ctx()->slice_budget; c->bwd_walk = default_ctx()->bwd_walk; c->onepass = default_ctx()->onepass; c->speculation = default_ctx()->speculation; c->plain_onepass = default_ctx()->plain_onepass; c->cull.enabled = default_ctx()->cull.enabled; c->cull.check = default_ctx()->cull.check; }
   return c;
 }
 void rtgs_ctx_destroy(rtgs_ctx* c) {
   if (!c || c == default_ctx()) return;
   if (c->ev_init) for (int i = 0; i < EV_N; ++i) (void)hipEventDestroy(c->ev[i]);
   if (c->info_host) (void)hipHostFree(c->info_host);
+  if (c->cull.scratch) (void)hipFree(c->cull.scratch);
+  if (c->cull.mismatches) (void)hipFree(c->cull.mismatches);
   delete c;
 }
 
@@ -411,6 +445,12 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
   // unrelated forward on this context
   uint32_t* const aux_zero = c->aux_zero;
   c->aux_zero = nullptr;
+  // the cull cache: every forward disarms it; only the speculative kinds 1 and 2 below arm it again (or find it armed)
+  const uint64_t cull_epoch = c->cull.next_epoch;
+  c->cull.next_epoch = 0;
+  const bool cull_was_armed = c->cull.armed;
+  c->cull.armed = false;
+  if (cull_was_armed) ++c->cull.stats[2];
   RasterParams p;
   int rc = make_params(s, P, M, p);
   if (rc != RTGS_OK) return rc;
@@ -533,11 +573,69 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
       if (++c->seq == 0u) c->seq = 1u;
       size_t b_total = 0;
       bool seg_main = false;                     // main pass placed into per-tile segments: no bound on the total
+      // The geometry of every Gaussian and the depth histograms: the cull (MODE 1) and slice_hist over the whole map - or, when
+      // the cache holds both for exactly this call, recull_rows over the rows the last tail marked.
+      auto cull_stage = [&](const BwdInfoInit& bi) -> int {
+        rtgs_ctx::CullCache& cc = c->cull;
+        rtgs_ctx::CullKey key;
+        memset(&key, 0, sizeof(key));
+        key.geom = geom; key.view = s->viewmatrix; key.means = means3D; key.scales = scales; key.rots = rotations;
+        key.out_radii = out_radii; key.stream = stream; key.geom_bytes = (uint64_t)G.total; key.epoch = cull_epoch;
+        key.P = P; key.H = p.H; key.W = p.W; key.kind = pl.kind; key.slice_mode = c->slice_mode; key.slice_budget = c->slice_budget;
+        key.fx = p.fx; key.fy = p.fy; key.cx = p.cx; key.cy = p.cy; key.tanfovx = p.tanfovx; key.tanfovy = p.tanfovy;
+        key.scale_modifier = p.scale_modifier; key.color_sigma = p.color_sigma;
+        const bool usable = cc.enabled && !immediate && cull_epoch != 0;
+        uint8_t* const marks = (uint8_t*)(geom + G.cull_marks);
+        float* const view_copy = (float*)(geom + G.cull_view);
+        float2* const uv = (float2*)(geom + G.uv);
+        if (usable && cull_was_armed && memcmp(&key, &cc.key, sizeof(key)) == 0) {
+          launch_recull_rows(p, means3D, scales, rotations, tiles_touched, radii, out_radii, zero_words, zero_n, zbin, uv,
+                             slice_hist, slice_cover, marks, view_copy, (int)(fail - zero_words), bi, st);
+          cc.armed = true;
+          ++cc.stats[0]; --cc.stats[2];
+          if (cc.check) {
+            // self-check: a full cull and slice_hist into scratch copies, compared word for word on the device (uv of a
+            // culled row is not written by the cull: the scratch starts from the maintained array)
+            const size_t Pn = (size_t)P;
+            const size_t o_tt = 0, o_rad = align_up(o_tt + Pn * 4), o_orad = align_up(o_rad + Pn * 4), o_zb = align_up(o_orad + Pn * 4),
+                         o_uv = align_up(o_zb + Pn), o_hist = align_up(o_uv + Pn * 8), need = align_up(o_hist + CULL_HIST_WORDS * 4);
+            if (cc.scratch_bytes < need) {
+              if (cc.scratch) (void)hipFree(cc.scratch);
+              cc.scratch = nullptr; cc.scratch_bytes = 0;
+              HIP_TRY(hipMalloc((void**)&cc.scratch, need));
+              cc.scratch_bytes = need;
+            }
+            if (!cc.mismatches) {
+              HIP_TRY(hipMalloc((void**)&cc.mismatches, sizeof(unsigned long long)));
+              HIP_TRY(hipMemset(cc.mismatches, 0, sizeof(unsigned long long)));
+            }
+            char* sc = cc.scratch;
+            HIP_TRY(hipMemcpyAsync(sc + o_uv, uv, Pn * 8, hipMemcpyDeviceToDevice, st));
+            launch_preprocess_cull(p, means3D, scales, rotations, (uint32_t*)(sc + o_tt), (int32_t*)(sc + o_rad),
+                                   out_radii ? (int32_t*)(sc + o_orad) : nullptr, nullptr, 0, (uint8_t*)(sc + o_zb),
+                                   (float2*)(sc + o_uv), (uint32_t*)(sc + o_hist), st);
+            launch_slice_hist(P, (const uint8_t*)(sc + o_zb), (const uint32_t*)(sc + o_tt), (const int32_t*)(sc + o_rad),
+                              (uint32_t*)(sc + o_hist), (unsigned long long*)(sc + o_hist + 2 * SLICE_BINS * 4), st);
+            launch_cull_check(P, tiles_touched, (const uint32_t*)(sc + o_tt), radii, (const int32_t*)(sc + o_rad), out_radii,
+                              (const int32_t*)(sc + o_orad), zbin, (const uint8_t*)(sc + o_zb), uv, (const float2*)(sc + o_uv),
+                              slice_hist, (const uint32_t*)(sc + o_hist), fail + 1, cc.mismatches, st);
+          }
+          return RTGS_OK;
+        }
+        launch_preprocess_cull(p, means3D, scales, rotations, tiles_touched, radii, out_radii, zero_words, zero_n, zbin, uv,
+                               slice_hist, st);
+        launch_slice_hist(P, zbin, tiles_touched, radii, slice_hist, slice_cover, st, bi);
+        if (usable) {
+          // the arrays are complete for this key from here on: no stale marks, and the view they were computed with
+          HIP_TRY(hipMemsetAsync(marks, 0, align_up((size_t)P + 16), st));
+          HIP_TRY(hipMemcpyAsync(view_copy, s->viewmatrix, 16 * sizeof(float), hipMemcpyDeviceToDevice, st));
+          memcpy(&cc.key, &key, sizeof(key)); cc.marks = marks; cc.armed = true;
+          ++cc.stats[1];
+        }
+        return RTGS_OK;
+      };
       if (pl.kind == 1) {
         // the near slice finished every tile last time: pass 1 only, the slot space is the slice's instance budget
-        launch_preprocess_cull(p, means3D, scales, rotations, tiles_touched, radii, out_radii, zero_words, zero_n, zbin,
-                               (float2*)(geom + G.uv), st);
-        prof_mark(c, EV_PRE, st);
         const uint32_t sl = (uint32_t)G.slice_cap;
         const bool use_sl = sl > 0 && sl <= SLOTS_MAX;
         const BinLayout B = bin_layout(0, ntiles, false, use_sl ? (size_t)sl : 0);
@@ -545,8 +643,10 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
         if (!bin) return RTGS_E_ALLOC;
         c->last_bin = bin;
         b_total = B.total;
-        launch_slice_hist(P, zbin, tiles_touched, radii, slice_hist, slice_cover, st,
-                          BwdInfoInit{(BwdInfo*)(img + I.bwd_info), (SplatGrad*)(bin + B.slot_grads), use_sl ? sl : 0u, use_sl ? 1u : 0u});
+        if ((rc = cull_stage(BwdInfoInit{(BwdInfo*)(img + I.bwd_info), (SplatGrad*)(bin + B.slot_grads), use_sl ? sl : 0u,
+                                         use_sl ? 1u : 0u})) != RTGS_OK)
+          return rc;
+        prof_mark(c, EV_PRE, st);
         launch_slice_compact(P, sel1, (uint32_t*)(geom + G.slice_ids), slice_ctr + 2, tiles_touched, offsets, slice_ctr + 4,
                              nullptr, 0u, nullptr, st);
         const SliceList work{(const uint32_t*)(geom + G.slice_ids), slice_ctr + 2};
@@ -594,11 +694,10 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
         SliceList vl{nullptr, nullptr};
         if (pl.kind == 2) {
           // the kernels declined the slice last time: assume they do again, single pass over the visible list
-          launch_preprocess_cull(p, means3D, scales, rotations, tiles_touched, radii, out_radii, zero_words, zero_n, zbin,
-                                 (float2*)(geom + G.uv), st);
+          if ((rc = cull_stage(BwdInfoInit{(BwdInfo*)(img + I.bwd_info), (SplatGrad*)(bin + B.slot_grads), capS,
+                                           immediate ? 0u : 1u})) != RTGS_OK)
+            return rc;
           prof_mark(c, EV_PRE, st);
-          launch_slice_hist(P, zbin, tiles_touched, radii, slice_hist, slice_cover, st,
-                            BwdInfoInit{(BwdInfo*)(img + I.bwd_info), (SplatGrad*)(bin + B.slot_grads), capS, immediate ? 0u : 1u});
           // (the decision - is the slice still declined? - is re-derived inside visible_compact: no slice_compact launch)
           vl = SliceList{(const uint32_t*)(geom + G.vis_ids), slice_ctr + 4};
           launch_visible_compact(P, zbin, (uint32_t*)(geom + G.vis_ids), slice_ctr + 4, tiles_touched, offsets, slice_ctr + 5, fail, st,
@@ -696,7 +795,7 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
     } else {
       // geometry of every Gaussian now, Splat records only where a list will read them
       launch_preprocess_cull(p, means3D, scales, rotations, tiles_touched, radii, out_radii, zero_words, zero_n, zbin,
-                             (float2*)(geom + G.uv), st);
+                             (float2*)(geom + G.uv), slice_hist, st);
     }
     DBG(s, st);
     prof_mark(c, EV_PRE, st);
@@ -1060,12 +1159,15 @@ int rtgs_raster_forward_verify_ctx(rtgs_ctx* ctx, int64_t* num_rendered_host) {
   bool ok;
   if (c->spec.kind == 1) {
     const uint32_t n_left = pub[2];
-    ok = n_left == 0u;
+    ok = n_left == 0u && pub[5] == 0u;           // ... and recull_rows did not see the view move under the cached cull
+    if (pub[5] != 0u) ++c->cull.stats[3];
     pl.R1 = pub[4]; pl.n_fin = pub[3]; pl.R = 0; pl.longest = 0;
     c->last_listed = pub[0];
     c->slice_stats[1] = pub[4]; c->slice_stats[2] = pub[3]; c->slice_stats[3] = n_left;
   } else {
-    ok = pub[0] <= c->spec.capR && pub[1] <= c->spec.capL && pub[5] <= c->spec.capS && (c->spec.kind != 2 || (int32_t)pub[6] < 0);
+    ok = pub[0] <= c->spec.capR && pub[1] <= c->spec.capL && pub[5] <= c->spec.capS && (c->spec.kind != 2 || (int32_t)pub[6] < 0) &&
+         pub[4] == 0u;
+    if (pub[4] != 0u) ++c->cull.stats[3];
     pl.note(pub[0], pub[1], pub[5]); pl.R1 = 0;
     c->last_listed = pub[2];
   }
@@ -1102,6 +1204,26 @@ void rtgs_raster_set_plain_onepass_ctx(rtgs_ctx* ctx, int enable) {
   c->plan_plain0 = rtgs_ctx::Plan();
 }
 uint32_t rtgs_raster_last_listed_ctx(rtgs_ctx* c) { return use(c)->last_listed; }
+void rtgs_raster_set_cull_cache_ctx(rtgs_ctx* ctx, int enable) {
+  rtgs_ctx* c = use(ctx);
+  c->cull.enabled = enable != 0;
+  c->cull.armed = false;
+}
+void rtgs_raster_set_cull_cache_check_ctx(rtgs_ctx* ctx, int enable) { use(ctx)->cull.check = enable != 0; }
+void rtgs_raster_set_map_epoch_ctx(rtgs_ctx* ctx, uint64_t epoch) { use(ctx)->cull.next_epoch = epoch; }
+uint8_t* rtgs_raster_cull_marks_ctx(rtgs_ctx* ctx) {
+  rtgs_ctx* c = use(ctx);
+  return c->cull.armed ? c->cull.marks : nullptr;
+}
+int rtgs_raster_cull_cache_stats_ctx(rtgs_ctx* ctx, int64_t* out5) {
+  rtgs_ctx* c = use(ctx);
+  if (!out5) return RTGS_E_INVALID;
+  memcpy(out5, c->cull.stats, sizeof(c->cull.stats));
+  unsigned long long bad = 0;
+  if (c->cull.mismatches) HIP_TRY(hipMemcpy(&bad, c->cull.mismatches, sizeof(bad), hipMemcpyDeviceToHost));   // waits for the device
+  out5[4] = (int64_t)bad;
+  return RTGS_OK;
+}
 void rtgs_raster_set_bwd_debug(int bits) { rtgs::set_bwd_debug(bits); }
 void rtgs_raster_set_bwd_stamps(void* dev) { rtgs::set_bwd_stamps(dev); }
 void rtgs_raster_set_fwd_stamps(void* dev) { rtgs::set_fwd_stamps(dev); }
@@ -1120,7 +1242,7 @@ int rtgs_raster_backward_buffers(int32_t P, int32_t H, int32_t W, size_t* out) {
   const GeomLayout G = geom_layout(P, gx, gy, 1);        // budget-independent offsets only
   const ImgLayout I = img_layout(H, W, gx * gy);
   out[0] = G.clamped; out[1] = G.offsets; out[2] = G.slot_count; out[3] = I.bwd_info;
-  out[4] = align_up((size_t)(P > 0 ? P : 1) * sizeof(SplatGrad)); out[5] = G.radii; out[6] = 0; out[7] = 0;
+  out[4] = align_up((size_t)(P > 0 ? P : 1) * sizeof(SplatGrad)); out[5] = G.radii; out[6] = G.cull_marks; out[7] = 0;
   return RTGS_OK;
 }
 int rtgs_raster_image_offsets(int32_t H, int32_t W, size_t* out) {

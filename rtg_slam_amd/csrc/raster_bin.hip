@@ -268,7 +268,8 @@ __global__ void __launch_bounds__(1024) bin_tilescan_kernel(int ntiles, const ui
                     (caps.cut && cut >= 0)) ? 1u : 0u;
     if (info_host) {   // pinned host words the forward's one host sync reads: no device-to-host copy launch in between
       const uint32_t w[7] = {s_sum[1023], s_max[1023], extra_src ? extra_src[0] : 0u, extra_src ? extra_src[1] : 0u,   // near-slice tile counters
-                             extra_src2 ? extra_src2[0] : 0u,                                                  // near-slice instance total
+                             // near-slice instance total, or (speculative) the word beside the speculation word: recull_rows saw the view move
+                             extra_src2 ? extra_src2[0] : (caps.fail ? caps.fail[1] : 0u),
                              // size of the backward's gradient-slot space: last exclusive-scan value + last rect area
                              slots_total, (uint32_t)cut};
       // publish: the host spins on the sequence word instead of paying a blocking stream sync's wake-up latency
@@ -423,7 +424,8 @@ __device__ __forceinline__ void bin_finish(const BinFinish& f) {
   if (f.caps.fail && (R > f.caps.R || longest > f.caps.longest || slots_total > f.caps.slots || (f.caps.cut && cut >= 0)))
     *f.caps.fail = 1u;                           // only ever raised here: bin_place may have raised it already
   if (f.info_host) {
-    const uint32_t w[7] = {R, longest, f.listed ? f.listed[0] : 0u, 0u, 0u, slots_total, (uint32_t)cut};
+    // [4]: the word beside the speculation word - recull_rows saw the view move under a cached cull
+    const uint32_t w[7] = {R, longest, f.listed ? f.listed[0] : 0u, 0u, f.caps.fail ? f.caps.fail[1] : 0u, slots_total, (uint32_t)cut};
     publish_to_host(f.info_host, w, f.seq);
   }
 }

@@ -78,7 +78,11 @@ struct GeomLayout {
   size_t scan_temp_bytes;
   // near-slice pass (raster_api.hip): [zero_begin, zero_end) is cleared by preprocess_fwd on every call
   size_t zero_begin, zero_end;
-  size_t tile_count1, ranges1_bwd, slice_hist, slice_cover, slice_ctr;   // inside the zeroed span (tile_count is too)
+  size_t tile_count1, ranges1_bwd, slice_ctr;   // inside the zeroed span (tile_count is too)
+  // The cull cache (raster_api.hip): the depth histograms live OUTSIDE the zeroed span - a full cull clears them itself, a
+  // cache hit keeps them and moves only the stepped rows' contributions; one mark byte per row (written by the map step's
+  // tails for every row they step) and the view matrix the cached cull results were computed with.
+  size_t slice_hist, slice_cover, cull_marks, cull_view;
   size_t zbin, cursor1, ranges1, mask2, block_counts1, bucket1, list1, uv, slice_ids;
   size_t vis_ids, block_counts_vis;   // list of every visible Gaussian + its per-workgroup tile counts (declined single pass)
   size_t slot_count;                 // [P] u32: slots taken per Gaussian (backward; zeroed by it)
@@ -90,6 +94,7 @@ struct GeomLayout {
 // per octave from 0.2) is <= the cut every workgroup derives from the area histogram: the largest bin whose
 // cumulative 3-sigma-rect instance count still fits `cap`.
 constexpr int SLICE_BINS = 256;
+constexpr int CULL_HIST_WORDS = 2 * SLICE_BINS + 2 * SLICE_BINS;   // slice_hist (2 x u32) and slice_cover (u64) of a bin, contiguous
 constexpr int SLICE_MAX_LIST = 3072;        // longest near-slice tile list that is sorted (longer: tile left to pass 2)
 constexpr float SLICE_MIN_COVER = 24.f;     // automatic mode: sum(radius^2) of the slice per pixel of the image, at least
 constexpr float SLICE_MIN_RATIO = 2.f;      // automatic mode: instances of the whole map / instances of the slice, at least

@@ -41,62 +41,26 @@ __global__ void __launch_bounds__(256) mask_sat_kernel(const int32_t* __restrict
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// K1 preprocess_fwd: one lane per Gaussian.  Reads 62 floats (248 B), writes one 64-B Splat +
-// radius + tiles_touched + clamp flags.
-// ---------------------------------------------------------------------------------------------
-// MODE 0: everything for every Gaussian (single-pass forward).
-// MODE 1: geometry only - depth cull, radius, tile rect, depth bin, (u, v) - for every Gaussian: 52 B read and
-//         21 B written per Gaussian instead of 248 B + 77 B.  The two-pass forward shades lazily:
-// MODE 2: the rest (conic, SH colour, plane, the 64-B Splat) for the Gaussians of a work list (the near slice),
-//         or - list.ids == nullptr - for every visible Gaussian NOT in the slice, and only if the slice left tiles
-//         unfinished.  (u, v) and the radius are taken from MODE 1 so that every kernel derives the same tile rect.
-template <int MODE>
-__global__ void __launch_bounds__(256) preprocess_fwd_kernel(
-    RasterParams p, const float* __restrict__ means, const float* __restrict__ opac,
-    const float* __restrict__ shs, const float* __restrict__ scales, const float* __restrict__ rots,
-    const float* __restrict__ normal_w, const int32_t* __restrict__ sat,
-    Splat* __restrict__ splats, uint32_t* __restrict__ tiles_touched, int32_t* __restrict__ radii,
-    uint8_t* __restrict__ clamped, int32_t* __restrict__ out_radii, uint32_t* __restrict__ zero_words, int zero_n,
-    uint8_t* __restrict__ zbin, float2* __restrict__ uv, SliceList list, SliceSel sel) {
-  // no automatic FMA contraction: the three instantiations must round identically (the two-pass forward is tested
-  // bit for bit against the single pass)
+// The geometry of one Gaussian under the view: depth cull, 2D covariance, radius, projected centre and (RECT) its tile
+// rect.  ONE definition for the three instantiations of preprocess_fwd_kernel and for recull_rows_kernel, which redoes
+// MODE 1 for single rows: whoever computes a row's cull result computes the same bits.  false = culled.
+struct CullGeom {
+  float mx, my, mz, pcx, pcy, pcz, ca, cb, cc, idet, u, v;
+  int radius, touched;
+};
+template <bool RECT>
+__device__ __forceinline__ bool cull_geom(const RasterParams& p, const float* __restrict__ means,
+                                          const float* __restrict__ scales, const float* __restrict__ rots,
+                                          const int32_t* __restrict__ sat, int i, CullGeom& o) {
+  // no automatic FMA contraction: every caller must round identically (the two-pass forward is tested bit for bit
+  // against the single pass, a re-culled row against the full cull)
 #pragma clang fp contract(off)
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if constexpr (MODE != 2) {
-    // clears the per-tile counters bin_count accumulates into (saves a memset launch on the critical path)
-    for (int t = i; t < zero_n; t += gridDim.x * blockDim.x) zero_words[t] = 0u;
-    if (i >= p.P) return;
-    tiles_touched[i] = 0;
-    radii[i] = 0;
-    if (out_radii) out_radii[i] = 0;
-    if (zbin) zbin[i] = 255;
-  } else {
-    if (spec_failed(p.spec_fail)) return;      // speculative forward already known to be wrong: the work list is not valid
-    if (list.ids) {
-      if (i >= (int)*list.count) return;
-      i = (int)list.ids[i];
-    } else {
-      if (sel.ctr && sel.ctr[0] == 0u) return;   // the slice finished every tile: nobody will read the other Splats
-      const int cut = slice_cut(sel);            // (all 256 threads of the workgroup call)
-      if (i >= p.P) return;
-      const int zb = (int)sel.zbin[i];
-      if (zb == 255 || zb <= cut) return;        // invisible, or shaded with the slice already
-      if (sel.sat) {                              // no unfinished tile under its rect: bin_count will not read it either
-        const float2 c = uv[i];
-        int x0, y0, x1, y1;
-        tile_rect_of(c.x, c.y, radii[i], p.gx, p.gy, x0, y0, x1, y1);
-        if (sat_count(sel.sat, p.gx, x0, y0, x1, y1) == 0) return;
-      }
-    }
-  }
-
   const float* V = p.view;   // V[j*4+i] = W2C[i][j]
   const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
   const float pcx = V[0] * mx + V[4] * my + V[8] * mz + V[12];
   const float pcy = V[1] * mx + V[5] * my + V[9] * mz + V[13];
   const float pcz = V[2] * mx + V[6] * my + V[10] * mz + V[14];
-  if (!(pcz > 0.2f)) return;
+  if (!(pcz > 0.2f)) return false;
 
   // Sigma3D = (R S)(R S)^T
   const float4 q4 = reinterpret_cast<const float4*>(rots)[i];
@@ -137,31 +101,104 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
   const float cb = T00 * b0 + T01 * b1 + T02 * b2;
   const float cc = T10 * b0 + T11 * b1 + T12 * b2 + 0.3f;
   const float det = ca * cc - cb * cb;
-  if (det == 0.f) return;
+  if (det == 0.f) return false;
   const float idet = 1.f / det;
   const float mid = 0.5f * (ca + cc);
   const float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-  int radius = (int)ceilf(p.color_sigma * sqrtf(lam));
-  float u = p.fx * pcx / pcz + p.cx;
-  float v = p.fy * pcy / pcz + p.cy;
+  const int radius = (int)ceilf(p.color_sigma * sqrtf(lam));
+  const float u = p.fx * pcx / pcz + p.cx;
+  const float v = p.fy * pcy / pcz + p.cy;
   int touched = 0;
-  if constexpr (MODE == 2) {
-    const float2 t = uv[i];
-    u = t.x; v = t.y; radius = radii[i];
-  } else {
+  if constexpr (RECT) {
     int x0, y0, x1, y1;
     tile_rect_of(u, v, radius, p.gx, p.gy, x0, y0, x1, y1);
-    if ((x1 - x0) * (y1 - y0) == 0) return;
+    if ((x1 - x0) * (y1 - y0) == 0) return false;
     const int sw = p.gx + 1;
     touched = sat ? sat[y1 * sw + x1] - sat[y0 * sw + x1] - sat[y1 * sw + x0] + sat[y0 * sw + x0]
                   : (x1 - x0) * (y1 - y0);   // LDS binning path recounts exactly; this is a bound
   }
+  o.mx = mx; o.my = my; o.mz = mz; o.pcx = pcx; o.pcy = pcy; o.pcz = pcz;
+  o.ca = ca; o.cb = cb; o.cc = cc; o.idet = idet; o.u = u; o.v = v; o.radius = radius; o.touched = touched;
+  return true;
+}
+// what MODE 1 leaves for a visible row (a culled one keeps radius 0, no tiles, depth bin 255 and its old uv)
+__device__ __forceinline__ void cull_store(const CullGeom& g, int i, uint32_t* __restrict__ tiles_touched,
+                                           int32_t* __restrict__ radii, int32_t* __restrict__ out_radii,
+                                           uint8_t* __restrict__ zbin, float2* __restrict__ uv) {
+  radii[i] = g.radius;
+  if (out_radii) out_radii[i] = g.radius;
+  tiles_touched[i] = (uint32_t)g.touched;
+  zbin[i] = (uint8_t)slice_bin_of(g.pcz);
+  uv[i] = make_float2(g.u, g.v);
+}
+
+// ---------------------------------------------------------------------------------------------
+// K1 preprocess_fwd: one lane per Gaussian.  Reads 62 floats (248 B), writes one 64-B Splat +
+// radius + tiles_touched + clamp flags.
+// ---------------------------------------------------------------------------------------------
+// MODE 0: everything for every Gaussian (single-pass forward).
+// MODE 1: geometry only - depth cull, radius, tile rect, depth bin, (u, v) - for every Gaussian: 52 B read and
+//         21 B written per Gaussian instead of 248 B + 77 B.  The two-pass forward shades lazily:
+// MODE 2: the rest (conic, SH colour, plane, the 64-B Splat) for the Gaussians of a work list (the near slice),
+//         or - list.ids == nullptr - for every visible Gaussian NOT in the slice, and only if the slice left tiles
+//         unfinished.  (u, v) and the radius are taken from MODE 1 so that every kernel derives the same tile rect.
+template <int MODE>
+__global__ void __launch_bounds__(256) preprocess_fwd_kernel(
+    RasterParams p, const float* __restrict__ means, const float* __restrict__ opac,
+    const float* __restrict__ shs, const float* __restrict__ scales, const float* __restrict__ rots,
+    const float* __restrict__ normal_w, const int32_t* __restrict__ sat,
+    Splat* __restrict__ splats, uint32_t* __restrict__ tiles_touched, int32_t* __restrict__ radii,
+    uint8_t* __restrict__ clamped, int32_t* __restrict__ out_radii, uint32_t* __restrict__ zero_words, int zero_n,
+    uint8_t* __restrict__ zbin, float2* __restrict__ uv, SliceList list, SliceSel sel,
+    uint32_t* __restrict__ zero2, int zero2_n) {
+  // no automatic FMA contraction: the three instantiations must round identically (the two-pass forward is tested
+  // bit for bit against the single pass)
+#pragma clang fp contract(off)
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (MODE != 2) {
+    // clears the per-tile counters bin_count accumulates into (saves a memset launch on the critical path)
+    for (int t = i; t < zero_n; t += gridDim.x * blockDim.x) zero_words[t] = 0u;
+    // (MODE 1: the depth histograms slice_hist accumulates into - they sit outside that span, see GeomLayout)
+    for (int t = i; t < zero2_n; t += gridDim.x * blockDim.x) zero2[t] = 0u;
+    if (i >= p.P) return;
+    tiles_touched[i] = 0;
+    radii[i] = 0;
+    if (out_radii) out_radii[i] = 0;
+    if (zbin) zbin[i] = 255;
+  } else {
+    if (spec_failed(p.spec_fail)) return;      // speculative forward already known to be wrong: the work list is not valid
+    if (list.ids) {
+      if (i >= (int)*list.count) return;
+      i = (int)list.ids[i];
+    } else {
+      if (sel.ctr && sel.ctr[0] == 0u) return;   // the slice finished every tile: nobody will read the other Splats
+      const int cut = slice_cut(sel);            // (all 256 threads of the workgroup call)
+      if (i >= p.P) return;
+      const int zb = (int)sel.zbin[i];
+      if (zb == 255 || zb <= cut) return;        // invisible, or shaded with the slice already
+      if (sel.sat) {                              // no unfinished tile under its rect: bin_count will not read it either
+        const float2 c = uv[i];
+        int x0, y0, x1, y1;
+        tile_rect_of(c.x, c.y, radii[i], p.gx, p.gy, x0, y0, x1, y1);
+        if (sat_count(sel.sat, p.gx, x0, y0, x1, y1) == 0) return;
+      }
+    }
+  }
+
+  CullGeom cg;
+  if (!cull_geom<MODE != 2>(p, means, scales, rots, sat, i, cg)) return;
+  const float* V = p.view;
+  const float mx = cg.mx, my = cg.my, mz = cg.mz, pcx = cg.pcx, pcy = cg.pcy, pcz = cg.pcz;
+  const float ca = cg.ca, cb = cg.cb, cc = cg.cc, idet = cg.idet;
+  float u = cg.u, v = cg.v;
+  int radius = cg.radius;
+  const int touched = cg.touched;
+  if constexpr (MODE == 2) {
+    const float2 t = uv[i];
+    u = t.x; v = t.y; radius = radii[i];
+  }
   if constexpr (MODE == 1) {
-    radii[i] = radius;
-    if (out_radii) out_radii[i] = radius;
-    tiles_touched[i] = (uint32_t)touched;
-    zbin[i] = (uint8_t)slice_bin_of(pcz);
-    uv[i] = make_float2(u, v);
+    cull_store(cg, i, tiles_touched, radii, out_radii, zbin, uv);
     return;
   }
 
@@ -705,17 +742,19 @@ void launch_preprocess_fwd(const RasterParams& p, const float* means, const floa
   if (p.P == 0) return;
   hipLaunchKernelGGL(preprocess_fwd_kernel<0>, dim3((p.P + 255) / 256), dim3(256), 0, st, p, means, opac, shs, scales,
                      rots, normal_w, sat, splats, tiles_touched, radii, clamped, out_radii, zero_words, zero_n, zbin,
-                     (float2*)nullptr, SliceList{nullptr, nullptr}, SliceSel{0, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr});
+                     (float2*)nullptr, SliceList{nullptr, nullptr}, SliceSel{0, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr},
+                     (uint32_t*)nullptr, 0);
 }
 // two-pass forward, stage 1: geometry of every Gaussian
 void launch_preprocess_cull(const RasterParams& p, const float* means, const float* scales, const float* rots,
                             uint32_t* tiles_touched, int32_t* radii, int32_t* out_radii, uint32_t* zero_words, int zero_n,
-                            uint8_t* zbin, float2* uv, hipStream_t st) {
+                            uint8_t* zbin, float2* uv, uint32_t* hist_words, hipStream_t st) {
   if (p.P == 0) return;
   hipLaunchKernelGGL(preprocess_fwd_kernel<1>, dim3((p.P + 255) / 256), dim3(256), 0, st, p, means, (const float*)nullptr,
                      (const float*)nullptr, scales, rots, (const float*)nullptr, (const int32_t*)nullptr, (Splat*)nullptr,
                      tiles_touched, radii, (uint8_t*)nullptr, out_radii, zero_words, zero_n, zbin, uv,
-                     SliceList{nullptr, nullptr}, SliceSel{0, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr});
+                     SliceList{nullptr, nullptr}, SliceSel{0, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr},
+                     hist_words, hist_words ? CULL_HIST_WORDS : 0);
 }
 // two-pass forward, stage 2: Splat records of the work list (max_items bounds its length), or of everything else
 void launch_preprocess_shade(const RasterParams& p, const float* means, const float* opac, const float* shs,
@@ -726,8 +765,166 @@ void launch_preprocess_shade(const RasterParams& p, const float* means, const fl
   const size_t n = list.ids ? (max_items < (size_t)p.P ? max_items : (size_t)p.P) : (size_t)p.P;
   hipLaunchKernelGGL(preprocess_fwd_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, means, opac, shs,
                      scales, rots, normal_w, (const int32_t*)nullptr, splats, (uint32_t*)nullptr, radii, clamped,
-                     (int32_t*)nullptr, (uint32_t*)nullptr, 0, (uint8_t*)nullptr, uv, list, sel);
+                     (int32_t*)nullptr, (uint32_t*)nullptr, 0, (uint8_t*)nullptr, uv, list, sel, (uint32_t*)nullptr, 0);
 }
+// ---------------------------------------------------------------------------------------------
+// recull_rows: what a cache hit launches in place of the cull (MODE 1) and slice_hist (raster_api.hip: the cull cache).
+// The per-row cull results in the geometry buffer are those of the last step under the same view; the map step's tail
+// left one mark byte for every row it stepped.  This kernel clears the span the cull clears, writes the backward's
+// host-known words (as slice_hist's first thread does), and for every marked row takes the row's old contribution out of
+// the three depth histograms, recomputes the row with the cull's own code (cull_geom / cull_store), adds the new
+// contribution and clears the mark.  All histogram arithmetic is integer and wraps: the sums equal a full pass's.
+// The view matrix is device memory the caller may rewrite in place: every workgroup compares it with the copy the last
+// full cull kept and, on a difference, touches no row; the first thread then raises the speculation word (and the word
+// beside it, which tells the host why), and the step is redone plainly.
+// A workgroup owns RECULL_ROWS consecutive rows: their marks are read four per lane, the marked ones compacted into LDS and
+// then processed one row per lane - a few thousand rows of 1.2 M on the headline map, ~17 % of the rows on a surface map
+// (~175 of a workgroup's 1 024: one pass of the 256 lanes; at 4 096 rows per workgroup the same rows were three dependent
+// passes, each row six atomics on the same few LDS bins, and the kernel took 23 us there).
+// ---------------------------------------------------------------------------------------------
+constexpr int RECULL_ROWS = 1024;
+struct RecullArgs {
+  RasterParams p;
+  const float *means, *scales, *rots;
+  uint32_t* tiles_touched; int32_t* radii; int32_t* out_radii; uint8_t* zbin; float2* uv;
+  uint32_t* hist; unsigned long long* cover;
+  uint8_t* marks;                 // [P rounded up to 4]
+  const float* view_copy;         // [16]
+  uint32_t* zero_words; int zero_n;
+  int fail_idx;                   // index of the speculation word inside zero_words (the view word follows it)
+  BwdInfoInit bi;
+};
+__global__ void __launch_bounds__(256) recull_rows_kernel(RecullArgs a) {
+  __shared__ uint32_t s_h[SLICE_BINS], s_c[SLICE_BINS], s_r[SLICE_BINS];
+  __shared__ uint16_t s_list[RECULL_ROWS];
+  __shared__ uint32_t s_n;
+  const int tid = threadIdx.x;
+  const bool differs = tid < 16 && __float_as_uint(a.p.view[tid]) != __float_as_uint(a.view_copy[tid]);
+  s_h[tid] = 0; s_c[tid] = 0; s_r[tid] = 0;
+  if (tid == 0) s_n = 0;
+  const uint32_t moved = __syncthreads_or(differs ? 1 : 0) ? 1u : 0u;
+  if (a.bi.dst && blockIdx.x == 0 && tid == 0) {
+    a.bi.dst->slot_grads = a.bi.slot_grads; a.bi.dst->slots = a.bi.slots; a.bi.dst->use_slots = a.bi.use_slots;
+  }
+  {
+    // the zeroed span, 16 B per store; the two words that report a moved view are written with it (no second writer)
+    const int nv = a.zero_n >> 2, stride = (int)gridDim.x * 256;
+    uint4* z4 = reinterpret_cast<uint4*>(a.zero_words);
+    for (int t = (int)blockIdx.x * 256 + tid; t < nv; t += stride) {
+      uint4 w = make_uint4(0u, 0u, 0u, 0u);
+      const int d = a.fail_idx - 4 * t;
+      if (d >= -1 && d < 4) {
+        if (d == 0 || d == -1) w.x = moved;
+        if (d == 1 || d == 0) w.y = moved;
+        if (d == 2 || d == 1) w.z = moved;
+        if (d == 3 || d == 2) w.w = moved;
+      }
+      z4[t] = w;
+    }
+    for (int t = 4 * nv + (int)blockIdx.x * 256 + tid; t < a.zero_n; t += stride)
+      a.zero_words[t] = (t == a.fail_idx || t == a.fail_idx + 1) ? moved : 0u;
+  }
+  if (moved) return;
+  const int P = a.p.P;
+  const int row0 = (int)blockIdx.x * RECULL_ROWS + tid * 4;
+  if (row0 < P) {
+    // marks is padded to a multiple of 4 bytes and the padding is never set
+    uint32_t* m4 = reinterpret_cast<uint32_t*>(a.marks + row0);
+    const uint32_t m = *m4;
+    if (m != 0u) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) bits |= (((m >> (8 * k)) & 0xffu) != 0u ? 1u : 0u) << k;
+      uint32_t at = atomicAdd(&s_n, (uint32_t)__popc(bits));
+      while (bits) {
+        const int k = __ffs((int)bits) - 1;
+        bits &= bits - 1u;
+        s_list[at++] = (uint16_t)(tid * 4 + k);
+      }
+      *m4 = 0u;
+    }
+  }
+  __syncthreads();
+  const int n = (int)s_n;
+  for (int q = tid; q < n; q += 256) {
+    const int i = (int)blockIdx.x * RECULL_ROWS + (int)s_list[q];
+    if (i >= P) continue;
+    // the row's old contribution (a culled row has none: radius 0, no tiles)
+    const uint32_t zb0 = a.zbin[i], ar0 = a.tiles_touched[i], r0 = (uint32_t)min(a.radii[i], 256);
+    uint32_t zb = 255u, ar = 0u, r = 0u;
+    CullGeom cg;
+    if (cull_geom<true>(a.p, a.means, a.scales, a.rots, nullptr, i, cg)) {
+      cull_store(cg, i, a.tiles_touched, a.radii, a.out_radii, a.zbin, a.uv);
+      zb = slice_bin_of(cg.pcz); ar = (uint32_t)cg.touched; r = (uint32_t)min(cg.radius, 256);
+    } else if (zb0 != 255u) {
+      a.tiles_touched[i] = 0; a.radii[i] = 0;
+      if (a.out_radii) a.out_radii[i] = 0;
+      a.zbin[i] = 255;
+    }
+    // most stepped rows stay in their depth bin with their radius and rect (a step moves them by a fraction of a pixel):
+    // nothing to move then - on a single-layer map every row of a workgroup shares a few bins, and each of these atomics
+    // would queue up behind the others on one LDS word
+    if (zb != zb0 || ar != ar0 || r != r0) {
+      if (zb0 != 255u) { atomicSub(&s_h[zb0], ar0); atomicSub(&s_c[zb0], 1u); atomicSub(&s_r[zb0], r0 * r0); }
+      if (zb != 255u) { atomicAdd(&s_h[zb], ar); atomicAdd(&s_c[zb], 1u); atomicAdd(&s_r[zb], r * r); }
+    }
+  }
+  __syncthreads();
+  if (n > 0) {
+    // per-workgroup deltas (two's complement): at most RECULL_ROWS rows x 2^16 per bin, well inside 31 bits
+    const uint32_t dh = s_h[tid], dc = s_c[tid], dr = s_r[tid];
+    if (dh) atomicAdd(&a.hist[tid], dh);
+    if (dc) atomicAdd(&a.hist[SLICE_BINS + tid], dc);
+    if (dr) atomicAdd(&a.cover[tid], (unsigned long long)(long long)(int32_t)dr);
+  }
+}
+void launch_recull_rows(const RasterParams& p, const float* means, const float* scales, const float* rots,
+                        uint32_t* tiles_touched, int32_t* radii, int32_t* out_radii, uint32_t* zero_words, int zero_n,
+                        uint8_t* zbin, float2* uv, uint32_t* hist, unsigned long long* cover, uint8_t* marks,
+                        const float* view_copy, int fail_idx, BwdInfoInit bi, hipStream_t st) {
+  if (p.P == 0) return;
+  const RecullArgs a{p, means, scales, rots, tiles_touched, radii, out_radii, zbin, uv, hist, cover, marks, view_copy,
+                     zero_words, zero_n, fail_idx, bi};
+  hipLaunchKernelGGL(recull_rows_kernel, dim3((p.P + RECULL_ROWS - 1) / RECULL_ROWS), dim3(256), 0, st, a);
+}
+
+// The cull cache's self-check (RTGS_CULL_CACHE_CHECK): the maintained per-row arrays and histograms against those of a
+// full cull + slice_hist into scratch copies, word for word (depth bins byte for byte); *mismatches += differing words.
+struct CullCheckArgs {
+  int P;
+  const uint32_t *tt_a, *tt_b; const int32_t *rad_a, *rad_b, *orad_a, *orad_b; const uint8_t *zb_a, *zb_b;
+  const uint2 *uv_a, *uv_b; const uint32_t *hist_a, *hist_b;      // hist: CULL_HIST_WORDS words, the cover sums included
+  const uint32_t* skip;           // recull_rows' moved-view word: it touched nothing, the step is being redone
+  unsigned long long* mismatches;
+};
+__global__ void __launch_bounds__(256) cull_check_kernel(CullCheckArgs a) {
+  if (*a.skip != 0u) return;
+  uint32_t bad = 0;
+  const int stride = (int)gridDim.x * 256;
+  for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < a.P; i += stride) {
+    bad += a.tt_a[i] != a.tt_b[i]; bad += a.rad_a[i] != a.rad_b[i]; bad += a.zb_a[i] != a.zb_b[i];
+    if (a.orad_a) bad += a.orad_a[i] != a.orad_b[i];
+    const uint2 x = a.uv_a[i], y = a.uv_b[i];
+    bad += x.x != y.x; bad += x.y != y.y;
+  }
+  if (blockIdx.x == 0)
+    for (int t = (int)threadIdx.x; t < CULL_HIST_WORDS; t += 256) bad += a.hist_a[t] != a.hist_b[t];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) bad += (uint32_t)__shfl_xor((int)bad, off);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(a.mismatches, (unsigned long long)bad);
+}
+void launch_cull_check(int P, const uint32_t* tt_a, const uint32_t* tt_b, const int32_t* rad_a, const int32_t* rad_b,
+                       const int32_t* orad_a, const int32_t* orad_b, const uint8_t* zb_a, const uint8_t* zb_b,
+                       const float2* uv_a, const float2* uv_b, const uint32_t* hist_a, const uint32_t* hist_b,
+                       const uint32_t* skip, unsigned long long* mismatches, hipStream_t st) {
+  if (P == 0) return;
+  int blocks = (P + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  const CullCheckArgs a{P, tt_a, tt_b, rad_a, rad_b, orad_a, orad_b, zb_a, zb_b, (const uint2*)uv_a, (const uint2*)uv_b,
+                        hist_a, hist_b, skip, mismatches};
+  hipLaunchKernelGGL(cull_check_kernel, dim3(blocks), dim3(256), 0, st, a);
+}
+
 void launch_emit_keys(const RasterParams& p, const Splat* splats, const int32_t* radii, const uint32_t* offsets,
                       const int32_t* mask, uint64_t* keys, uint32_t* vals, hipStream_t st) {
   if (p.P == 0) return;
@@ -761,9 +958,10 @@ __global__ void __launch_bounds__(256) slice_publish_kernel(int ntiles, const in
   if (threadIdx.x == 0) {
     const uint32_t L = (uint32_t)(s_l[0] + s_l[1] + s_l[2] + s_l[3]), F = (uint32_t)(s_f[0] + s_f[1] + s_f[2] + s_f[3]);
     ctr[0] = L; ctr[1] = F;                      // device copy: pass 2's kernels exit at once when nothing is left
-    if (spec_fail) *spec_fail = L != 0u ? 1u : 0u;   // speculative forward: the host assumed the slice finishes every tile
+    // speculative forward: the host assumed the slice finishes every tile (recull_rows may have raised the word before)
+    if (spec_fail) *spec_fail = (L != 0u || *spec_fail != 0u) ? 1u : 0u;
     const uint32_t R1 = seg_count ? (uint32_t)(s_i[0] + s_i[1] + s_i[2] + s_i[3]) : r1[0];
-    const uint32_t w[7] = {ctr[2], 0u, L, F, R1, 0u, 0u};     // [0]: length of the slice's work list
+    const uint32_t w[7] = {ctr[2], 0u, L, F, R1, ctr[7], 0u};     // [0]: length of the slice's work list  [5]: the view moved under a cached cull
     publish_to_host(host, w, seq);
   }
 }

@@ -248,6 +248,10 @@ class ShardedMapOptimizer:
         self._scope = "local"          # "global": begin_global_optimization() - the stable prefix is what is rendered and trained
         self._lr_scope = None          # learning-rate columns of the running global optimisation
         self.version = 0               # bumped by everything that changes what a render of the map shows
+        # the map epoch step_slam hands the one-call step (rtgs_map_step_args.map_epoch): it stays the same only from one
+        # step_slam to the next with nothing in between that could have written rows (see _next_map_epoch)
+        self._map_epoch = 0
+        self._epoch_seen = None        # _epoch_state() as the last step_slam left it
         self._gd_views = {}            # gaussian_data's views per row range (see there)
         self._adam_dirty = None        # rows of state[.]["m" / "v" / "ever"] that may be non-zero: None, (lo, hi) or "all"
         self._frozen_version = 0       # bumped by everything that may change a FROZEN row (see frozen_key)
@@ -784,6 +788,7 @@ class ShardedMapOptimizer:
         dev = st["xyz"]["p"].device
         if N == 0:
             raise RuntimeError("step_slam() on an empty map")
+        epoch = self._next_map_epoch()
         self.version += 1
         if self._scope == "global":
             self._frozen_version += 1
@@ -851,7 +856,10 @@ class ShardedMapOptimizer:
             C.pointer(attach) if attach is not None else None, P(confidence) if confidence is not None else None,
             int(self._act_valid), geom.cb, None, binning.cb, None, img.cb, None,
             float(normal_weight) if gt_normal is not None else 0.0, P(gt_normal) if gt_normal is not None else None,
-            int(nf), int(N), int(self.tail_mode), P(self.live_counts) if self.live_counts is not None else None)
+            int(nf), int(N), int(self.tail_mode), P(self.live_counts) if self.live_counts is not None else None,
+            # only the single-GPU one-call step keeps the promise the epoch stands for: the other fronts run tails of their own
+            int(epoch) if (self.world == 1 and not tile_band) else 0)
+        self._epoch_seen = self._epoch_state()
         R = C.c_int64(0)
         stream = torch.cuda.current_stream(dev).cuda_stream
         if tile_band and self.world > 1:
@@ -878,6 +886,23 @@ class ShardedMapOptimizer:
         self.last_num_rendered = int(R.value)
         self.last_losses = ws["loss"]               # device float[4]: total, colour, depth, ssim (mapper.py:458-466)
         return ws["loss"][0]
+
+    def _next_map_epoch(self) -> int:
+        """The map epoch the next `step_slam` passes (called by it before its own version bump; pure bookkeeping).  The
+        rasterizer context may keep its per-row cull results from one step to the next only while the epoch stays the same,
+        so it stays the same only if NOTHING but the previous `step_slam` touched the map since: `version` - bumped by
+        everything that changes what a render of the map shows - stands where that call left it, the activated arrays are
+        current, the step's work arenas are the same and there is one rank.  Never 0 (0 = no promise)."""
+        same = (self.world == 1 and self._epoch_seen is not None and self._slam_ws is not None and self._act_valid
+                and self._epoch_seen == self._epoch_state())
+        if not same:
+            self._map_epoch += 1
+        return self._map_epoch
+
+    def _epoch_state(self):
+        """What has to stand still between two `step_slam` calls for the epoch to stay (step_slam records it after its own
+        version bump, with its work arenas in place)."""
+        return (int(self.version), id(self._slam_ws), self._scope, int(self.N), int(self.n_frozen))
 
     def band_tile_mask(self, tile_mask: torch.Tensor, with_region: bool = False):
         """This rank's share of the switched-on tiles: contiguous runs in row-major order with (almost) equal tile

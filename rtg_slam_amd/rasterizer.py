@@ -89,6 +89,21 @@ class RasterContext:
         _lib.check(_lib.load().rtgs_raster_speculation_stats_ctx(self.ptr, out), "rtgs_raster_speculation_stats")
         return dict(speculative=int(out[0]), failed=int(out[1]), not_eligible=int(out[2]))
 
+    def set_cull_cache(self, enable: bool):
+        """The map step's cull cache (include/rtgs_raster.h): same-view steps re-cull only the rows the last step moved;
+        default on (RTGS_CULL_CACHE=0 at load time switches it off)."""
+        _lib.load().rtgs_raster_set_cull_cache_ctx(self.ptr, int(bool(enable)))
+
+    def set_cull_cache_check(self, enable: bool):
+        """Self-check: every cache hit also runs the full cull and compares, on the device (slow; RTGS_CULL_CACHE_CHECK=1)."""
+        _lib.load().rtgs_raster_set_cull_cache_check_ctx(self.ptr, int(bool(enable)))
+
+    def cull_cache_stats(self):
+        """Counts since the context was made; `check_mismatches` waits for the device."""
+        out = (C.c_int64 * 5)()
+        _lib.check(_lib.load().rtgs_raster_cull_cache_stats_ctx(self.ptr, out), "rtgs_raster_cull_cache_stats")
+        return dict(hits=int(out[0]), full=int(out[1]), disarmed=int(out[2]), view_redos=int(out[3]), check_mismatches=int(out[4]))
+
     def set_plain_onepass(self, enable: bool):
         """Forwards without a backward: one-pass placement with the check inside the call (include/rtgs_raster.h)."""
         _lib.load().rtgs_raster_set_plain_onepass_ctx(self.ptr, int(bool(enable)))
