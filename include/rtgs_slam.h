@@ -376,6 +376,57 @@ int rtgs_tsdf_sparse_emit(const float* pool, const int32_t* coords, const int32_
 int rtgs_tsdf_sparse_to_dense(const float* pool, const int32_t* table, int32_t nx, int32_t ny, int32_t nz, const int32_t* window6_host,
                               float* tsdf, float* weight, float* rgb, void* stream);
 
+/* ---- mesh operations: normals, components, compaction, vertex clustering (no counterpart in the reference; csrc/mesh_ops.hip)
+ * An indexed triangle mesh on the device: vertices [V][3] float32, faces [F][3] int32, colours [V][3] float32, as
+ * rtgs_tsdf_emit's triangles are welded into, or as another of these operations leaves it.  The CALLER guarantees
+ * 0 <= faces[i] < V; V, F <= RTGS_MESH_MAX_ELEMENTS.  Every result is unique and independent of thread order (no float atomics):
+ * two runs are bit-equal, and tests/mesh_ops_reference.py restates each in numpy.  Scans and sorts are the caller's.
+ *
+ * rtgs_mesh_vertex_normals.  order [3 F] = the corner indices o = 3 f + k sorted STABLY by faces[o]; start [V + 1] = the first
+ *   position of every vertex's run in it (start[V] = 3 F).  Face normal n = e1 x e2 with e1 = p1 - p0, e2 = p2 - p0, a component
+ *   two rounded float32 products and a rounded difference (area-weighted); a vertex's sum starts at 0 and adds its corners'
+ *   face normals in ascending o, every addition rounded; normals [V][3] = sum / l, l = sqrtf((x x + y y) + z z), when l > 0,
+ *   else 0 0 0.
+ * rtgs_mesh_component_labels.  labels [V] = the smallest vertex index joined to v through faces (two vertices of a face are
+ *   joined); an unreferenced vertex labels itself.  parent [V] int32 is scratch (a lock-free union-find: a root is hooked
+ *   under a smaller root by compare-and-swap, so every chain descends and every retry lowers an index - no unbounded loop).
+ * rtgs_mesh_component_faces adds 1 to counts[labels[faces[f][0]]] for every face (counts [V], zeroed by the caller);
+ *   rtgs_mesh_keep_faces then writes keep [F] = 1 where the face's component has at least min_faces faces, else 0.
+ * rtgs_mesh_mark_vertices writes used[v] = 1 (used [V], zeroed by the caller) for the corners of every face with keep[f] != 0
+ *   (keep may be NULL: every face).  rtgs_mesh_compact_vertices, given used and its EXCLUSIVE scan offsets, copies every used
+ *   vertex and colour to row offsets[v], in order, and writes vmap [V] = the new index, -1 for a dropped vertex.
+ *   rtgs_mesh_compact_faces copies face f with keep[f] != 0 to row offsets[f] (the EXCLUSIVE scan of keep; keep NULL: every face
+ *   to its own row), its indices passed through vmap (NULL: unchanged).
+ * rtgs_mesh_cluster_cells.  cells [V][3] = (int) floorf((p - origin) / cell) per axis in float32, origin3_host 3 floats on the
+ *   HOST; err[0] (zeroed by the caller) is set to 1 when a coordinate is below origin or NaN, or its cell index is not below
+ *   RTGS_MESH_MAX_CELLS.  rtgs_mesh_cluster_means, given the vertex indices `order` sorted STABLY by cell key and the S + 1 run
+ *   starts, writes per run the mean position and colour: members added in float64 in that order, divided by the count in
+ *   float64, rounded to float32.  rtgs_mesh_cluster_faces maps faces through cluster [V] (a vertex's run index), rotates each
+ *   so that its smallest index comes first (winding kept) and writes valid [F] = 0 for a face with two corners in one run.
+ *   rtgs_mesh_mark_first, given those faces and ids [n] = the valid faces sorted STABLY by their three indices, writes
+ *   keep[ids[i]] = 1 for the first of every run of identical faces - the first in original order - and 0 for the others.
+ * Return 0 (also, without a launch, for an empty mesh), -1 on a bad argument, -2 on a launch failure. */
+#define RTGS_MESH_MAX_ELEMENTS 2147483647LL
+#define RTGS_MESH_MAX_CELLS 2097152
+int rtgs_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t V, int64_t F, const int64_t* order,
+                             const int64_t* start, float* normals, void* stream);
+int rtgs_mesh_component_labels(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* labels, void* stream);
+int rtgs_mesh_component_faces(const int32_t* faces, int64_t F, const int32_t* labels, int32_t* counts, void* stream);
+int rtgs_mesh_keep_faces(const int32_t* faces, int64_t F, const int32_t* labels, const int32_t* counts, int32_t min_faces,
+                         int32_t* keep, void* stream);
+int rtgs_mesh_mark_vertices(const int32_t* faces, int64_t F, const int32_t* keep, int32_t* used, void* stream);
+int rtgs_mesh_compact_vertices(const float* vertices, const float* colors, int64_t V, const int32_t* used, const int64_t* offsets,
+                               float* out_vertices, float* out_colors, int32_t* vmap, void* stream);
+int rtgs_mesh_compact_faces(const int32_t* faces, int64_t F, const int32_t* keep, const int64_t* offsets, const int32_t* vmap,
+                            int32_t* out_faces, void* stream);
+int rtgs_mesh_cluster_cells(const float* vertices, int64_t V, const float* origin3_host, float cell, int32_t* cells, int32_t* err,
+                            void* stream);
+int rtgs_mesh_cluster_means(const float* vertices, const float* colors, const int64_t* order, const int64_t* start, int64_t S,
+                            float* out_vertices, float* out_colors, void* stream);
+int rtgs_mesh_cluster_faces(const int32_t* faces, int64_t F, const int32_t* cluster, int32_t* out_faces, int32_t* valid,
+                            void* stream);
+int rtgs_mesh_mark_first(const int32_t* faces, const int64_t* ids, int64_t n, int32_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,14 @@ def cmd_mesh(opts) -> int:
     model_base, check_frame, select_ply, test_iter = select_model(args, opts)
     last = int(check_frame.split("_")[-1])
     n_frames = last if opts.frames is None or opts.frames < 0 else min(opts.frames, last)
+    if opts.simplify < 0 or opts.min_component_faces < 0:
+        log("--simplify and --min-component-faces must be >= 0")
+        return 2
+    if opts.simplify > 0 and not opts.simplify > opts.voxel:
+        log(f"--simplify {opts.simplify:g}: the cell must be larger than the voxel ({opts.voxel:g} m); a cell that holds one vertex "
+            "simplifies nothing")
+        return 2
+    cleanup = opts.min_component_faces > 0 or opts.simplify > 0 or opts.normals
     log(f"meshing {select_ply} over {n_frames} frames ({opts.depth_source} depth, every {opts.every}, voxel {opts.voxel:g} m)")
     mapper = load_map(args, device, select_ply)
     mapper.time = int(check_frame.split("_")[1])
@@ -266,13 +274,14 @@ def cmd_mesh(opts) -> int:
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
     log(f"fusing at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
     t0 = time.perf_counter()
-    vertices, faces, colors, report = meshing.mesh_from_map(
+    vertices, faces, colors, report, *normals = meshing.mesh_from_map(
         mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
-        trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume)
+        trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume,
+        min_component_faces=opts.min_component_faces, simplify_cell=opts.simplify, normals=opts.normals)
     report["total_s"] = time.perf_counter() - t0
     path = os.path.join(model_base, MESH_PLY)
     t0 = time.perf_counter()
-    iof.save_mesh_ply(path, vertices, faces, colors)
+    iof.save_mesh_ply(path, vertices, faces, colors, *normals)
     report["write_s"] = time.perf_counter() - t0
     report["model"] = select_ply
     with open(os.path.join(model_base, MESH_REPORT), "w") as f:
@@ -280,6 +289,11 @@ def cmd_mesh(opts) -> int:
     log(f"mesh: {report['V']} vertices, {report['F']} faces from {report['frames_fused']} frames into a "
         f"{'x'.join(str(d) for d in report['dims'])} grid: render {report['render_s']:.3f} s, integrate "
         f"{report['integrate_s']:.3f} s, extract {report['extract_s']:.3f} s, write {report['write_s']:.3f} s -> {path}")
+    if cleanup:
+        log(f"clean-up: {report['V_raw']} vertices, {report['F_raw']} faces raw -> {report['V']} vertices, {report['F']} faces; "
+            f"{report.get('components_removed', 0)} of {report.get('components', 'all')} components removed"
+            f"{', simplified at %g m' % report['simplify_cell'] if report['simplify_cell'] > 0 else ''}"
+            f"{', with normals' if report['normals'] else ''}: {report['cleanup_s']:.3f} s")
     if opts.volume == "sparse":
         log(f"sparse volume: {report['bricks']} bricks, {100 * report['brick_share']:.2f} % of the grid's, "
             f"{report['pool_bytes'] / 2 ** 20:.1f} MiB of pool where the dense planes would take {report['dense_bytes'] / 2 ** 20:.1f} MiB")
@@ -379,6 +393,11 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--every", type=int, default=1, help="fuse every K-th frame")
     t.add_argument("--frames", type=int, default=None, help="fuse at most this many frames of the trajectory")
     t.add_argument("--min-weight", type=float, default=1.0, help="observations a cell's 8 corners need to be meshed")
+    t.add_argument("--min-component-faces", type=int, default=0,
+                   help="drop the connected components with fewer faces (default 0: off)")
+    t.add_argument("--simplify", type=float, default=0.0, metavar="CELL",
+                   help="cluster the vertices on a grid of CELL metres, larger than the voxel (default 0: off)")
+    t.add_argument("--normals", action="store_true", help="write per-vertex normals (nx ny nz) into the PLY")
     t.add_argument("--device", default="cuda:0")
     t.add_argument("--io-workers", type=int, default=None)
     t.add_argument("--resolution-scale", type=float, default=None,

@@ -259,6 +259,18 @@ _SIGNATURES = {
     "rtgs_tsdf_sparse_emit": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, _P, _P,
                                         C.c_int64, _P, _P, _P, _P, _P]),
     "rtgs_tsdf_sparse_to_dense": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    # mesh operations
+    "rtgs_mesh_vertex_normals": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "rtgs_mesh_component_labels": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "rtgs_mesh_component_faces": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "rtgs_mesh_keep_faces": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P]),
+    "rtgs_mesh_mark_vertices": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "rtgs_mesh_compact_vertices": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "rtgs_mesh_compact_faces": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
+    "rtgs_mesh_cluster_cells": (C.c_int, [_P, C.c_int64, _P, C.c_float, _P, _P, _P]),
+    "rtgs_mesh_cluster_means": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    "rtgs_mesh_cluster_faces": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "rtgs_mesh_mark_first": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -340,10 +340,11 @@ def load_mesh_ply(path: str, with_colors: bool = False):
     return (verts, faces, colors) if with_colors else (verts, faces)
 
 
-def save_mesh_ply(path: str, vertices, faces, colors=None) -> None:
-    """An indexed triangle mesh as a binary little-endian PLY: float x y z (and uchar red green blue when colors [V,3] in
-    0..1 are given, rounded to the nearest of 255 steps) per vertex, `list uchar int vertex_indices` per face.  Tensors or
-    arrays; load_mesh_ply reads the file back with the vertices bit-equal."""
+def save_mesh_ply(path: str, vertices, faces, colors=None, normals=None) -> None:
+    """An indexed triangle mesh as a binary little-endian PLY: float x y z (then float nx ny nz when normals [V,3] are given,
+    then uchar red green blue when colors [V,3] in 0..1 are given, rounded to the nearest of 255 steps) per vertex,
+    `list uchar int vertex_indices` per face.  Tensors or arrays; load_mesh_ply reads the file back with the vertices
+    bit-equal (it skips the normals)."""
     to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
     v = np.ascontiguousarray(to_np(vertices), dtype="<f4").reshape(-1, 3)
     f = np.ascontiguousarray(to_np(faces)).reshape(-1, 3)
@@ -354,6 +355,12 @@ def save_mesh_ply(path: str, vertices, faces, colors=None) -> None:
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
     lines += [f"property float {c}" for c in "xyz"]
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = np.ascontiguousarray(to_np(normals), dtype="<f4").reshape(-1, 3)
+        if nrm.shape[0] != v.shape[0]:
+            raise ValueError(f"save_mesh_ply: {nrm.shape[0]} normals for {v.shape[0]} vertices")
+        lines += [f"property float {n}" for n in ("nx", "ny", "nz")]
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
         c = to_np(colors).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
@@ -363,6 +370,8 @@ def save_mesh_ply(path: str, vertices, faces, colors=None) -> None:
     lines += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     vt = np.empty(v.shape[0], dtype=np.dtype(fields))
     vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vt["nx"], vt["ny"], vt["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         q = np.clip(np.rint(np.nan_to_num(c.astype(np.float64)) * 255.0), 0, 255).astype(np.uint8)
         vt["red"], vt["green"], vt["blue"] = q[:, 0], q[:, 1], q[:, 2]

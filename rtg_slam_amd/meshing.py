@@ -413,7 +413,8 @@ def map_bounds(mapper, pad: float):
 
 def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *, voxel: float = 0.01, depth_source: str = "render",
                   every: int = 1, bounds=None, trunc: Optional[float] = None, max_weight: float = 64, min_weight: float = 1,
-                  args=None, device=None, max_bytes: int = MAX_BYTES, volume: str = "dense"):
+                  args=None, device=None, max_bytes: int = MAX_BYTES, volume: str = "dense", min_component_faces: int = 0,
+                  simplify_cell: float = 0.0, normals: bool = False):
     """Fuse a trajectory into a TsdfVolume (volume "dense") or a SparseTsdfVolume ("sparse") and extract its mesh ->
     (vertices, faces, colors, report).
 
@@ -424,7 +425,14 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
     its GT pose without poses; "render" needs poses or a stream, "sensor" a stream.  Every `every`-th frame is fused.
     bounds = (lo, hi); default: the box of the map's Gaussian centres padded by trunc.  report: voxel, trunc, dims, bounds,
     frames fused, V, F and the seconds spent rendering, integrating and extracting; with volume "sparse", and only then, also
-    "volume", "bricks", "brick_share" (allocated / all), "pool_bytes" and "dense_bytes" (what the dense planes would take)."""
+    "volume", "bricks", "brick_share" (allocated / all), "pool_bytes" and "dense_bytes" (what the dense planes would take).
+
+    Clean-up (rtg_slam_amd.mesh_ops), off by default and applied in this order: min_component_faces > 0 drops the connected
+    components with fewer faces; simplify_cell > 0 (metres, larger than the voxel) clusters the vertices on a grid of that
+    cell anchored at the volume's lo; normals=True adds the final mesh's vertex normals as a FIFTH result, (vertices, faces,
+    colors, report, normals).  With any of the three on, the report's V and F are the final counts and it gains "V_raw",
+    "F_raw", the removal's "components", "components_removed", "faces_removed" and "vertices_removed" (when it ran),
+    "simplify_cell", "normals" and "cleanup_s"."""
     from .mapping import Frame
     from .render import Renderer
     if volume not in ("dense", "sparse"):
@@ -435,6 +443,10 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         raise ValueError("rtg_slam_amd.meshing: depth_source='sensor' needs the frame stream")
     if stream is None and poses is None:
         raise ValueError("rtg_slam_amd.meshing: need poses or a stream")
+    min_component_faces, simplify_cell, normals = int(min_component_faces), float(simplify_cell), bool(normals)
+    if simplify_cell != 0 and not simplify_cell > float(voxel):
+        raise ValueError(f"rtg_slam_amd.meshing: simplify_cell {simplify_cell:g} m must be larger than the voxel ({float(voxel):g} m); "
+                         "a cell that holds one vertex simplifies nothing")
     every = max(1, int(every))
     trunc = 4 * float(voxel) if trunc is None else float(trunc)
     if device is None:
@@ -481,4 +493,15 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         n_table = vol.brick_dims[0] * vol.brick_dims[1] * vol.brick_dims[2]
         report.update({"volume": "sparse", "bricks": vol.n_bricks, "brick_share": vol.n_bricks / n_table,
                        "pool_bytes": vol.pool_bytes, "dense_bytes": vol.dense_bytes})
+    if min_component_faces > 0 or simplify_cell > 0 or normals:
+        from . import mesh_ops
+        t0 = time.perf_counter()
+        vertices, faces, colors, nrm, stats = mesh_ops.clean_mesh(
+            vertices, faces, colors, min_component_faces=min_component_faces, simplify_cell=simplify_cell, origin=vol.lo,
+            normals=normals)
+        torch.cuda.synchronize(device)
+        report.update({"V_raw": report["V"], "F_raw": report["F"], "V": int(vertices.shape[0]), "F": int(faces.shape[0]), **stats,
+                       "simplify_cell": simplify_cell, "normals": normals, "cleanup_s": time.perf_counter() - t0})
+        if normals:
+            return vertices, faces, colors, report, nrm
     return vertices, faces, colors, report

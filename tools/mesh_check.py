@@ -11,9 +11,13 @@
     room and frames at 2 cm and 1 cm - per-frame integrate time (mark + scan + the host's read of the new-brick count +
     allocate + integrate, on volumes that already hold the frames) in alternating blocks of the same run, extraction time,
     pool bytes against dense bytes, and that the two meshes agree in V and F - and one sparse-only run at 4 mm, where the dense
-    planes (1300 x 800 x 1550 x 20 B) are over TsdfVolume's cap.
+    planes (1300 x 800 x 1550 x 20 B) are over TsdfVolume's cap;
+  * the clean-up leg (key "cleanup"; alone with --cleanup): rtg_slam_amd.mesh_ops on the fused room's mesh at 2 cm and 1 cm -
+    vertex_normals, component_labels, remove_small_components (100 faces), compact and simplify_clusters (2.5 voxels), each
+    whole call (its torch sorts and scans and the host's reads of the counts included) in blocks of its own, with the counts
+    before and after and the removal's statistics.
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
-blocks are reported.  python tools/mesh_check.py [--sparse-only] [OUT] [reps = 10] [blocks = 5]"""
+blocks are reported.  python tools/mesh_check.py [--sparse-only | --cleanup] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -23,7 +27,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from rtg_slam_amd import meshing, synth   # noqa: E402
+from rtg_slam_amd import mesh_ops, meshing, synth   # noqa: E402
 
 
 def blocks_ms(fn, reps, blocks, warmup=3):
@@ -131,9 +135,40 @@ def sparse_leg(dev, cam, frames, lo, hi, reps, blocks):
     return res
 
 
+def cleanup_leg(dev, cam, frames, lo, hi, reps, blocks):
+    res = {"timing": "device events around reps whole calls of one operation (kernels, torch sorts / scans, and the host reads "
+                     "of counts that size the outputs), blocks after a warm-up of 3 calls",
+           "min_faces": 100, "simplify_cell_voxels": 2.5}
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        _fuse_all(vol, frames, cam)
+        entry = {"dims": list(vol.dims), "extract": _timed_extract(vol)}
+        v, f, c = vol.extract_mesh()
+        origin = vol.lo
+        del vol
+        torch.cuda.empty_cache()
+        cell = 2.5 * voxel
+        entry["vertex_normals"] = blocks_ms(lambda i: mesh_ops.vertex_normals(v, f), reps, blocks)
+        entry["component_labels"] = blocks_ms(lambda i: mesh_ops.component_labels(f, v.shape[0]), reps, blocks)
+        entry["remove_small_components"] = blocks_ms(lambda i: mesh_ops.remove_small_components(v, f, c, 100), reps, blocks)
+        entry["compact"] = blocks_ms(lambda i: mesh_ops.compact(v, f, c), reps, blocks)
+        entry["simplify_clusters"] = blocks_ms(lambda i: mesh_ops.simplify_clusters(v, f, c, cell, origin), reps, blocks)
+        rv, rf, rc, stats = mesh_ops.remove_small_components(v, f, c, 100)
+        sv, sf, sc = mesh_ops.simplify_clusters(rv, rf, rc, cell, origin)
+        n = mesh_ops.vertex_normals(sv, sf)
+        entry.update({"V": int(v.shape[0]), "F": int(f.shape[0]), "removal": stats, "V_after_removal": int(rv.shape[0]),
+                      "F_after_removal": int(rf.shape[0]), "simplify_cell": cell, "V_after_simplify": int(sv.shape[0]),
+                      "F_after_simplify": int(sf.shape[0]), "zero_normals_after_simplify": int((n.abs().sum(1) == 0).sum())})
+        res[f"room_voxel_{voxel:g}"] = entry
+        del v, f, c, rv, rf, rc, sv, sf, sc, n
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--sparse-only"]
-    sparse_only = len(argv) != len(sys.argv) - 1
+    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup")]
+    sparse_only = "--sparse-only" in sys.argv[1:]
+    cleanup_only = "--cleanup" in sys.argv[1:]
     out_path = argv[0] if len(argv) > 0 else None
     reps = int(argv[1]) if len(argv) > 1 else 10
     blocks = int(argv[2]) if len(argv) > 2 else 5
@@ -148,6 +183,9 @@ def main():
     frame_bytes = cam.H * cam.W * 16
     half = (2.5, 1.5, 3.0)
     lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
+    if cleanup_only:
+        res["cleanup"] = cleanup_leg(dev, cam, frames, lo, hi, reps, blocks)
+        return _finish(res, out_path)
     if sparse_only:
         res["sparse"] = sparse_leg(dev, cam, frames, lo, hi, reps, blocks)
         return _finish(res, out_path)
@@ -219,6 +257,7 @@ def main():
     res["box_room_sensor_2cm"] = {"report": report, "vertex_to_wall_m": tr.wall_stats(v.cpu().numpy()),
                                   "numpy_reference_on_cpu": {"mean": 0.01126, "p99": 0.03607, "max": 0.03778, "covered": 0.1844}}
     res["sparse"] = sparse_leg(dev, cam, frames, lo, hi, reps, blocks)
+    res["cleanup"] = cleanup_leg(dev, cam, frames, lo, hi, reps, blocks)
     _finish(res, out_path)
 
 
