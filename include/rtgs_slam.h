@@ -427,6 +427,30 @@ int rtgs_mesh_cluster_faces(const int32_t* faces, int64_t F, const int32_t* clus
                             void* stream);
 int rtgs_mesh_mark_first(const int32_t* faces, const int64_t* ids, int64_t n, int32_t* keep, void* stream);
 
+/* ---- visibility: which points a depth frame saw, which faces that leaves (no counterpart in the reference;
+ * csrc/visibility.hip).  tests/visibility_reference.py restates both in numpy; the kernels match it bit for bit.
+ *
+ * rtgs_visibility_add.  points [N][3] float32 in the frame w2c maps FROM; depth [H][W] float32 in metres; w2c12_host = the top
+ *   three rows of the world-to-camera matrix, 12 floats on the HOST (passed to the kernel by value); views [N] int32, the
+ *   caller's running counts.  Per point, float32, one correctly rounded operation per step:
+ *     1  xc = ((m0 x + m1 y) + m2 z) + m3, yc and zc likewise from rows 1 and 2
+ *     2  fail unless zc > 0
+ *     3  u = fx xc / zc + cx,  v = fy yc / zc + cy
+ *     4  pu = floorf(u + 0.5f),  pv = floorf(v + 0.5f)
+ *     5  fail unless 0 <= pu < W and 0 <= pv < H
+ *     6  d = depth[pv][pu]; fail unless d > 0 (a hole sees nothing)
+ *     7  fail when zc - d > tolerance (the point is behind what the sensor measured)
+ *     8  views[i] += 1
+ *   Every comparison is false for NaN, so a NaN coordinate fails.  views[i] is read and written only in step 8, by the one
+ *   thread that owns point i: no atomics.  tolerance >= 0.
+ * rtgs_visibility_keep_faces.  keep [F] = 1 where all three corners of faces [F][3] (any_vertex != 0: at least one) have
+ *   views >= min_views, else 0.  The CALLER guarantees 0 <= faces[i] < the length of views.
+ * Return 0 (also, without a launch, for N == 0 / F == 0), -1 on a bad argument, -2 on a launch failure. */
+int rtgs_visibility_add(const float* points, int64_t N, const float* depth, int32_t H, int32_t W, float fx, float fy, float cx,
+                        float cy, const float* w2c12_host, float tolerance, int32_t* views, void* stream);
+int rtgs_visibility_keep_faces(const int32_t* faces, int64_t F, const int32_t* views, int32_t min_views, int32_t any_vertex,
+                               int32_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ save_model/pcd_densify.ply exists, the reconstruction metrics are computed on th
 dataset's own) over the trajectory into a TSDF volume and writes save_model/mesh_tsdf.ply and save_model/mesh_report.json
 (rtg_slam_amd.meshing); --volume sparse keeps planes only for the 8x8x8 bricks near the surface, for boxes whose dense planes
 would be refused.  `metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
+`metric --cull-gt` scores them against the part of the GT mesh the evaluated frames saw (evaluation.VisibilityCull) and writes
+eval_metric/gt_mesh_culled.ply and eval_metric/gt_cull_report.json.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -180,6 +182,8 @@ def cmd_slam(opts) -> int:
 DENSIFY_PLY = "pcd_densify.ply"
 MESH_PLY = "mesh_tsdf.ply"
 MESH_REPORT = "mesh_report.json"
+GT_CULL_PLY = "gt_mesh_culled.ply"
+GT_CULL_REPORT = "gt_cull_report.json"
 
 
 def geometry_ply(args, model_base: str, select_ply: str) -> str:
@@ -319,6 +323,9 @@ def cmd_metric(opts) -> int:
         if not os.path.isfile(mesh_path):
             log(f"--mesh: {mesh_path} does not exist; write it first with `python -m rtg_slam_amd mesh --config {opts.config}`")
             return 2
+    if opts.cull_gt and (opts.cull_tolerance < 0 or opts.cull_min_views < 1):
+        log("--cull-tolerance must be >= 0 and --cull-min-views >= 1")
+        return 2
     mapper = load_map(args, device, select_ply)
     mapper.time = int(check_frame.split("_")[1])
     mapper.iter = int(test_iter)
@@ -327,13 +334,20 @@ def cmd_metric(opts) -> int:
         poses = np.load(os.path.join(args.save_path, "save_traj", "pose_es.npy")).reshape(-1, 4, 4)[int(args.frame_start):]
     args.frame_num = max_cams
     info = datasets.load_dataset(args)
+    if opts.cull_gt and not (info.mesh_path and os.path.isfile(info.mesh_path)):
+        log(f"--cull-gt: there is no GT mesh to cull ({info.mesh_path or 'this dataset type has none'})")
+        return 2
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
     log(f"evaluating at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
-    gt_points, transform, rec_points = None, None, None
+    gt_points, transform, rec_points, gt_cull = None, None, None, None
     if info.mesh_path and os.path.isfile(info.mesh_path):
         v, f = iof.load_mesh_ply(info.mesh_path)
-        gt_points, _ = iof.sample_mesh_surface(v, f, 1_000_000)
         transform = datasets.read_pose_t0(args)
+        if opts.cull_gt:                     # the GT points are sampled from the culled mesh, after the last frame
+            gt_cull = evaluation.VisibilityCull(v, f, info.camera(), transform=transform, tolerance=opts.cull_tolerance,
+                                                min_views=opts.cull_min_views, any_vertex=opts.cull_keep == "any", device=device)
+        else:
+            gt_points, _ = iof.sample_mesh_surface(v, f, 1_000_000)
         if mesh_path is not None:
             log(f"geometry eval mesh: {mesh_path}")
             mv, mf = iof.load_mesh_ply(mesh_path)
@@ -346,7 +360,18 @@ def cmd_metric(opts) -> int:
                 raise ValueError(f"rtg_slam_amd: {pcd_path} holds no points")
             rec_points = torch.from_numpy(xyz).to(device=device, dtype=torch.float32)
     res = evaluation.evaluate_sequence(mapper, info.camera(), source, poses=poses, args=args, gt_points=gt_points,
-                                       dist_thres=[0.03], transform=transform, sample_nums=1_000_000, rec_points=rec_points)
+                                       dist_thres=[0.03], transform=transform, sample_nums=1_000_000, rec_points=rec_points,
+                                       gt_cull=gt_cull)
+    if gt_cull is not None:
+        cull_dir = os.path.join(args.save_path, "eval_metric")
+        os.makedirs(cull_dir, exist_ok=True)
+        cull_path = os.path.join(cull_dir, GT_CULL_PLY)
+        iof.save_mesh_ply(cull_path, *gt_cull.mesh())
+        report = gt_cull.report()
+        report["gt_mesh"] = info.mesh_path
+        with open(os.path.join(cull_dir, GT_CULL_REPORT), "w") as fo:
+            json.dump(report, fo, indent=1, default=float)
+        log(f"geometry eval gt: culled {report['F_kept']} of {report['F']} faces over {report['frames']} frames -> {cull_path}")
     out = os.path.join(args.save_path, f"statis_frame_{mapper.time}_iter_{test_iter}.csv")
     iof.save_metrics_csv(out, res["rows"])
     m = res["mean"]
@@ -379,6 +404,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="overrides resolution_scales[0]; evaluate at the scale the map was built at (metric.py:131,177)")
     m.add_argument("--mesh", action="store_true",
                    help="compute the reconstruction metrics on 1 M points sampled from save_model/mesh_tsdf.ply (written by `mesh`)")
+    m.add_argument("--cull-gt", action="store_true",
+                   help="score the geometry against the part of the GT mesh the evaluated frames saw (so --eval-frames bounds "
+                        "it): a vertex is seen when it projects, at a frame's GT pose, into a pixel whose sensor depth is valid and "
+                        "not more than the tolerance in front of it; writes eval_metric/gt_mesh_culled.ply and gt_cull_report.json")
+    m.add_argument("--cull-tolerance", type=float, default=0.03,
+                   help="metres a vertex may lie behind the sensor depth and still count as seen (default 0.03, the F-score threshold)")
+    m.add_argument("--cull-min-views", type=int, default=1, help="frames that must see a vertex (default 1)")
+    m.add_argument("--cull-keep", choices=("all", "any"), default="all",
+                   help="keep a face when all of its corners were seen (default) or when any was")
     t = sub.add_parser("mesh", help="fuse the map into a TSDF volume and write save_model/mesh_tsdf.ply")
     t.add_argument("--config", required=True)
     t.add_argument("--load-frame", type=int, default=-1)

@@ -271,6 +271,10 @@ _SIGNATURES = {
     "rtgs_mesh_cluster_means": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "rtgs_mesh_cluster_faces": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "rtgs_mesh_mark_first": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    # visibility
+    "rtgs_visibility_add": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P,
+                                      C.c_float, _P, _P]),
+    "rtgs_visibility_keep_faces": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -10,6 +10,8 @@
     evaluate_sequence  metric.py:137-219      every frame of a finished run with the evaluation renderer, the reconstruction
                                               once, per-frame rows and the mean row
     eval_mesh          (no counterpart)       eval_pcd of points sampled on a triangle mesh's surface (rtg_slam_amd.meshing)
+    VisibilityCull     (no counterpart)       the part of the GT mesh the evaluated frames saw: per vertex, against the sensor
+                                              depth, at the GT poses (include/rtgs_slam.h, "visibility")
 
 Each metric call reads its float64 result vector from the device once; that read is its only synchronisation.  The results
 are bitwise reproducible run to run (fixed-order reductions, no float atomics).  There is no CPU path."""
@@ -179,6 +181,157 @@ def eval_mesh(vertices, faces, gt_points, dist_thres: Sequence[float] = (0.03,),
     return eval_pcd(sample_mesh_points(vertices, faces, sample_nums, seed, dev), gt_points, dist_thres, transform, sample_nums)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# visibility culling of the GT mesh
+# ---------------------------------------------------------------------------------------------------------------------
+
+def visibility_add(views: torch.Tensor, points: torch.Tensor, depth: torch.Tensor, K, w2c, tolerance: float) -> None:
+    """rtgs_visibility_add: views [N] int32 += 1, in place, for every point of points [N,3] float32 that the frame sees -
+    include/rtgs_slam.h, "visibility", steps 1-8.  depth [H,W] or [H,W,1] float32 metres; K = (fx, fy, cx, cy); w2c: the
+    world-to-camera matrix (4x4 or its top 3x4), cast to float32 here.  All tensors on one device and contiguous."""
+    dev = _dev(views, points, depth)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("rtg_slam_amd.evaluation: points must be [N,3] float32")
+    if depth.dim() == 3 and depth.shape[2] == 1:
+        depth = depth[:, :, 0] if depth.is_contiguous() else depth       # [H,W,1] contiguous is [H,W] contiguous
+    if depth.dim() != 2 or depth.dtype != torch.float32 or depth.numel() == 0:
+        raise ValueError("rtg_slam_amd.evaluation: depth must be a non-empty [H,W] or [H,W,1] float32 image")
+    N = int(points.shape[0])
+    if views.shape != (N,) or views.dtype != torch.int32:
+        raise ValueError("rtg_slam_amd.evaluation: views must be [N] int32, one count per point")
+    if not (points.is_contiguous() and depth.is_contiguous() and views.is_contiguous()):
+        raise ValueError("rtg_slam_amd.evaluation: points, depth and views must be contiguous")
+    if points.device != dev or depth.device != dev:
+        raise ValueError("rtg_slam_amd.evaluation: points, depth and views live on different devices")
+    tolerance = float(np.float32(tolerance))
+    if not tolerance >= 0:
+        raise ValueError(f"rtg_slam_amd.evaluation: the visibility tolerance must be >= 0, got {tolerance}")
+    m = np.ascontiguousarray(np.asarray(w2c, dtype=np.float32).reshape(-1)[:12])
+    if m.size != 12:
+        raise ValueError("rtg_slam_amd.evaluation: w2c must be a 4x4 or 3x4 matrix")
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    fx, fy, cx, cy = (float(np.float32(k)) for k in K)
+    with torch.cuda.device(dev):
+        rc = _lib.load().rtgs_visibility_add(_p(points), N, _p(depth), H, W, fx, fy, cx, cy, (C.c_float * 12)(*m.tolist()),
+                                             tolerance, _p(views), _stream(dev))
+    _lib.check(rc, "rtgs_visibility_add")
+
+
+def visibility_keep_faces(faces: torch.Tensor, views: torch.Tensor, min_views: int = 1, any_vertex: bool = False) -> torch.Tensor:
+    """rtgs_visibility_keep_faces -> keep [F] int32: 1 where all three corners of faces [F,3] int32 (any_vertex: at least one)
+    have views >= min_views.  The face indices are checked against len(views) here (one host synchronisation)."""
+    dev = _dev(faces, views)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError("rtg_slam_amd.evaluation: faces must be [F,3] int32")
+    if views.dim() != 1 or views.dtype != torch.int32 or views.device != dev:
+        raise ValueError("rtg_slam_amd.evaluation: views must be [V] int32 on the faces' device")
+    if not (faces.is_contiguous() and views.is_contiguous()):
+        raise ValueError("rtg_slam_amd.evaluation: faces and views must be contiguous")
+    min_views = int(min_views)
+    if not -2 ** 31 <= min_views < 2 ** 31:
+        raise ValueError("rtg_slam_amd.evaluation: min_views must fit int32")
+    F, V = int(faces.shape[0]), int(views.shape[0])
+    if F:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= V:
+            raise ValueError(f"rtg_slam_amd.evaluation: face indices must lie in 0..{V - 1}, found {lo}..{hi}")
+    keep = torch.empty(F, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().rtgs_visibility_keep_faces(_p(faces), F, _p(views), min_views, int(bool(any_vertex)), _p(keep),
+                                                    _stream(dev))
+    _lib.check(rc, "rtgs_visibility_keep_faces")
+    return keep
+
+
+class VisibilityCull:
+    """The part of a GT mesh that a sequence of frames saw.  A vertex is seen by a frame when it projects, at the frame's GT
+    pose, into a pixel whose SENSOR depth is valid and not more than `tolerance` metres in front of it (visibility_add); a face
+    stays when all of its corners (keep "any": at least one) were seen by min_views frames or more.
+
+        cull = VisibilityCull(vertices, faces, cam, transform=pose_t0)
+        for depth, _, gt_c2w in stream: cull.add(depth, gt_c2w)
+        v, f = cull.mesh()
+
+    vertices [V,3] and faces [F,3] are arrays or device tensors; they are cast to float32 / int32 once, here.  `transform` is
+    the 4x4 evaluate_sequence receives (datasets.read_pose_t0): the stream's poses are relative to the first frame, transform @
+    c2w is the camera in the mesh's frame.  The default tolerance is the F-score threshold of metric (dist_thres = [0.03])."""
+
+    def __init__(self, vertices, faces, cam, transform=None, tolerance: float = 0.03, min_views: int = 1, any_vertex: bool = False,
+                 device=None):
+        for t in (vertices, faces):
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise RuntimeError("rtg_slam_amd.evaluation: tensors must live on a HIP device; this build has no CPU path.")
+        if device is None:
+            device = next((t.device for t in (vertices, faces) if torch.is_tensor(t)), None)
+            device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("rtg_slam_amd.evaluation: VisibilityCull needs a HIP device; this build has no CPU path.")
+        V = int(vertices.shape[0])
+        if V >= 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.evaluation: {V} vertices do not fit the int32 face indices")
+        up = lambda a, dt: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=self.device, dtype=dt)
+        self.vertices = up(vertices, torch.float32).reshape(-1, 3).contiguous()
+        f = up(faces, torch.int64).reshape(-1, 3)
+        if f.shape[0]:
+            lo, hi = (int(x) for x in torch.aminmax(f))
+            if lo < 0 or hi >= V:
+                raise ValueError(f"rtg_slam_amd.evaluation: face indices must lie in 0..{V - 1}, found {lo}..{hi}")
+        self.faces = f.to(torch.int32).contiguous()
+        self.cam = cam
+        self.transform = np.eye(4) if transform is None else np.asarray(transform, dtype=np.float64).reshape(4, 4)
+        self.tolerance = float(np.float32(tolerance))
+        self.min_views = int(min_views)
+        self.any_vertex = bool(any_vertex)
+        if not self.tolerance >= 0:
+            raise ValueError(f"rtg_slam_amd.evaluation: the visibility tolerance must be >= 0, got {tolerance}")
+        if self.min_views < 1:
+            raise ValueError(f"rtg_slam_amd.evaluation: min_views must be >= 1, got {min_views}")
+        self.views = torch.zeros(V, dtype=torch.int32, device=self.device)
+        self.frames = 0
+        self._events: List = []
+        self._seconds = 0.0
+
+    def add(self, depth: torch.Tensor, c2w) -> None:
+        """One frame: depth [H,W] or [H,W,1] float32 on the device, at the camera's size; c2w its GT pose as the stream gives
+        it.  The matrix used is inv(transform @ c2w), inverted in float64 on the host, then cast to float32."""
+        if not torch.is_tensor(depth) or not depth.is_cuda:
+            raise RuntimeError("rtg_slam_amd.evaluation: tensors must live on a HIP device; this build has no CPU path.")
+        if tuple(depth.shape[:2]) != (self.cam.H, self.cam.W):
+            raise ValueError(f"rtg_slam_amd.evaluation: depth is {tuple(depth.shape)}, the camera {self.cam.H}x{self.cam.W}")
+        c2w = c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else np.asarray(c2w)
+        w2c = np.linalg.inv(self.transform @ c2w.astype(np.float64).reshape(4, 4)).astype(np.float32)
+        with torch.cuda.device(self.device):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            visibility_add(self.views, self.vertices, depth, (self.cam.fx, self.cam.fy, self.cam.cx, self.cam.cy), w2c, self.tolerance)
+            b.record()
+        self._events.append((a, b))
+        self.frames += 1
+
+    def keep(self) -> torch.Tensor:
+        """-> keep [F] int32 for the frames added so far."""
+        return visibility_keep_faces(self.faces, self.views, self.min_views, self.any_vertex)
+
+    def mesh(self):
+        """-> (vertices [V_kept,3] float32, faces [F_kept,3] int32) on the device: the kept faces in their order, the vertices
+        they use in theirs, faces re-indexed (mesh_ops.keep_faces)."""
+        from . import mesh_ops
+        v, f, _ = mesh_ops.keep_faces(self.vertices, self.faces, None, self.keep())
+        return v, f
+
+    def report(self) -> Dict:
+        """Counts before and after, the settings, and the device time of the .add launches (events; synchronises)."""
+        for a, b in self._events:
+            b.synchronize()
+            self._seconds += a.elapsed_time(b) * 1e-3
+        self._events = []
+        v, f = self.mesh()
+        return {"V": int(self.vertices.shape[0]), "F": int(self.faces.shape[0]), "V_kept": int(v.shape[0]), "F_kept": int(f.shape[0]),
+                "frames": self.frames, "tolerance": self.tolerance, "min_views": self.min_views,
+                "keep": "any" if self.any_vertex else "all", "seconds": self._seconds}
+
+
 def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: Optional[float] = None,
                max_depth: Optional[float] = None, renderer=None, run_picture: bool = True, run_pcd: bool = False,
                gt_points=None, dist_thres: Sequence[float] = (0.03,), sample_nums: int = 1_000_000, transform=None,
@@ -203,12 +356,16 @@ def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, mi
 
 def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_points=None, dist_thres: Sequence[float] = (0.03,),
                       transform=None, sample_nums: int = 1_000_000, generator: Optional[torch.Generator] = None,
-                      with_ms_ssim: bool = True, rec_points: Optional[torch.Tensor] = None) -> Dict:
+                      with_ms_ssim: bool = True, rec_points: Optional[torch.Tensor] = None,
+                      gt_cull: Optional["VisibilityCull"] = None) -> Dict:
     """metric.py:137-219 over a finished map.  `stream` yields (depth [H,W] metres, colour [3,H,W], GT c2w) as run_sequence's
     does; frame i is rendered at poses[i] (the estimated trajectory, e.g. tracker.pose_es) or, without poses, at its GT pose,
     by a Renderer whose opaque threshold is args.renderer_opaque_threshold_eval (metric.py:138).  With gt_points, the
     reconstruction metrics join the last frame's row, as metric.py runs them there: of rec_points [P,3] on the device (the
     points of pcd_densify.ply, metric.py:156-163) when given, else of the map's Gaussian centres.
+    With gt_cull (a VisibilityCull of the GT mesh), every frame's sensor depth and GT pose - never the estimated one, so the
+    culled GT does not depend on the run being scored - go to gt_cull.add while the stream passes, and the GT points of the
+    last frame's row are sampled from the culled mesh: as many as gt_points holds, 1 000 000 without gt_points.
     Returns {"rows": one dict per frame (with "frame" and "iter"), "mean": the mean row of metric.py:205-211}."""
     from .mapping import Frame
     from .render import Renderer
@@ -219,6 +376,8 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
     rows: List[Dict] = []
     for i, (depth, color, gt_c2w) in enumerate(stream):
         frame = Frame(cam, gt_c2w, mapper.device, uid=i)
+        if gt_cull is not None:
+            gt_cull.add(depth, gt_c2w)
         if poses is not None:
             frame.updatePose(np.asarray(poses[i], dtype=np.float64))         # metric.py:175-176
         row = eval_frame(mapper, frame, color, depth, args.min_depth, args.max_depth, renderer=renderer,
@@ -226,6 +385,12 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
         row["frame"] = i
         row["iter"] = int(getattr(mapper, "iter", 0))
         rows.append(row)
+    if gt_cull is not None and rows:
+        cv, cf = gt_cull.mesh()
+        if cf.shape[0] == 0:
+            raise ValueError(f"rtg_slam_amd.evaluation: no face of the GT mesh was seen within a tolerance of "
+                             f"{gt_cull.tolerance:g} m over {gt_cull.frames} frames; is the mesh in the frame the poses map into?")
+        gt_points = sample_mesh_points(cv, cf, len(gt_points) if gt_points is not None else 1_000_000, 0, mapper.device)
     if gt_points is not None and rows:
         with torch.no_grad():
             rec = mapper.opt.gaussian_data("all")["xyz"] if rec_points is None else rec_points

@@ -5,6 +5,7 @@ marching-tetrahedra mesh needs before it is usable.  The reference has no mesher
     component_labels          label[v] = the smallest vertex index joined to v through faces
     remove_small_components   drop the faces of components with fewer than min_faces faces, then the vertices nobody uses
     compact                   drop the vertices no face uses, by itself
+    keep_faces                keep the faces a caller's mask names, then drop the vertices nobody uses
     simplify_clusters         vertex clustering on a grid of `cell` metres: one vertex per occupied cell
 
 All take an indexed mesh on the device - vertices [V,3] float32, faces [F,3] int32, colours [V,3] float32 - from
@@ -153,6 +154,20 @@ def compact(vertices: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor):
     in theirs, re-indexed."""
     vertices, faces, colors, V, F = _check(vertices, faces, colors)
     return _compact(vertices, faces, colors, V, F, None)
+
+
+def keep_faces(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[torch.Tensor], keep: torch.Tensor):
+    """The faces with keep != 0 (keep [F] int32 on the device, the caller's mask) in their order, the vertices they use in
+    theirs, faces re-indexed -> (vertices, faces, colors).  colors may be None, and is then None in the result."""
+    vertices, faces, colors, V, F = _check(vertices, faces, colors)
+    if not torch.is_tensor(keep) or not keep.is_cuda:
+        raise RuntimeError("rtg_slam_amd.mesh_ops: tensors must live on a HIP device; this build has no CPU path.")
+    if keep.shape != (F,) or keep.dtype != torch.int32 or keep.device != vertices.device:
+        raise ValueError("rtg_slam_amd.mesh_ops: keep must be [F] int32, one flag per face, on the mesh's device")
+    keep = (keep.detach() != 0).to(torch.int32)           # the scan below sums the flags: 0 or 1
+    # without colours the vertices stand in for them: the copy kernel moves both, the second result is dropped
+    out_v, out_f, out_c = _compact(vertices, faces, vertices if colors is None else colors, V, F, keep)
+    return out_v, out_f, None if colors is None else out_c
 
 
 def remove_small_components(vertices: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor, min_faces: int):
