@@ -451,6 +451,33 @@ int rtgs_visibility_add(const float* points, int64_t N, const float* depth, int3
 int rtgs_visibility_keep_faces(const int32_t* faces, int64_t F, const int32_t* views, int32_t min_views, int32_t any_vertex,
                                int32_t* keep, void* stream);
 
+/* ---- mesh render: the depth map and the face map of an indexed triangle mesh at a pinhole pose (no counterpart in the
+ * reference; csrc/mesh_render.hip).  tests/mesh_render_reference.py restates it in numpy; the kernels match it bit for bit.
+ *
+ * vertices [V][3] float32 in the frame w2c maps FROM; faces [F][3] int32, the CALLER guarantees 0 <= faces[i] < V;
+ * w2c12_host = the top three rows of the world-to-camera matrix, 12 floats on the HOST; depth [H][W] float32 (0 where nothing
+ * was hit) and face [H][W] int32 (-1 there).  Float32, one correctly rounded operation per step:
+ *   per vertex  xc, yc, zc, u, v as steps 1 and 3 of rtgs_visibility_add, iz = 1 / zc; usable when zc > near (NaN fails)
+ *   per face    dropped whole when a corner is not usable (NO clipping: a face across the near plane leaves a hole) or when a
+ *               u or v is not finite.  x0 = max(ceil(min u), 0), x1 = min(floor(max u), W - 1), y0 and y1 likewise from v
+ *               and H, all in float; skipped unless x0 <= x1 and y0 <= y1; integers only after that.  Pixel centres are the
+ *               integer coordinates.
+ *   edge p->q   E = (qu - pu)(py - pv) - (qv - pv)(px - pu), evaluated with the ends in lexicographic (u, v) order and negated
+ *               when that reverses the edge; ends that project to one point drop the face.  w0 = E(b,c), w1 = E(c,a),
+ *               w2 = E(a,b), area = (w0 + w1) + w2; covered when all w >= 0 and area > 0, or all w <= 0 and area < 0.
+ *   depth       z = 1 / (((w0 iz_a + w1 iz_b) + w2 iz_c) / area), accepted when finite and > 0
+ *   resolve     the pixel keeps the smallest key (bits(z) << 32) | face: the nearest surface, then the lowest face index.
+ * One call is four launches on `stream` (clear, faces, large faces, resolve) with no host read.  A face whose box holds at
+ * most small_max (>= 0) pixels is walked by one thread, a larger one by a wave, through a queue of F entries in the scratch; the
+ * picture does not depend on small_max.  scratch: rtgs_mesh_render_scratch_bytes bytes (0 for sizes rtgs_mesh_render
+ * refuses), the caller's, reusable by the next call, 8-byte aligned.  F == 0 gives the empty picture.
+ * Return 0, -1 on a bad argument (F or H W >= 2^31, near <= 0 or NaN, small_max < 0, a null pointer that is needed), -2 on a
+ * launch failure. */
+size_t rtgs_mesh_render_scratch_bytes(int64_t V, int64_t F, int32_t H, int32_t W);
+int rtgs_mesh_render(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int32_t H, int32_t W, float fx, float fy,
+                     float cx, float cy, const float* w2c12_host, float near, int32_t small_max, void* scratch, float* depth,
+                     int32_t* face, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

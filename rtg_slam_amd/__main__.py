@@ -19,7 +19,10 @@ dataset's own) over the trajectory into a TSDF volume and writes save_model/mesh
 (rtg_slam_amd.meshing); --volume sparse keeps planes only for the 8x8x8 bricks near the surface, for boxes whose dense planes
 would be refused.  `metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
 `metric --cull-gt` scores them against the part of the GT mesh the evaluated frames saw (evaluation.VisibilityCull) and writes
-eval_metric/gt_mesh_culled.ply and eval_metric/gt_cull_report.json.
+eval_metric/gt_mesh_culled.ply and eval_metric/gt_cull_report.json; --cull-depth mesh decides that against the GT mesh's own
+rendered depth, not the sensor's.  `metric --mesh-depth` renders save_model/mesh_tsdf.ply at every evaluated pose
+(evaluation.MeshRenderer) and writes its depth L1 to eval_metric/mesh_depth_frame_F_iter_I.csv and mesh_depth_report.json.
+`mesh --cull-unseen` removes the surface no fused view could see before the mesh is written.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -184,6 +187,7 @@ MESH_PLY = "mesh_tsdf.ply"
 MESH_REPORT = "mesh_report.json"
 GT_CULL_PLY = "gt_mesh_culled.ply"
 GT_CULL_REPORT = "gt_cull_report.json"
+MESH_DEPTH_REPORT = "mesh_depth_report.json"
 
 
 def geometry_ply(args, model_base: str, select_ply: str) -> str:
@@ -265,6 +269,9 @@ def cmd_mesh(opts) -> int:
         log(f"--simplify {opts.simplify:g}: the cell must be larger than the voxel ({opts.voxel:g} m); a cell that holds one vertex "
             "simplifies nothing")
         return 2
+    if opts.cull_unseen_tolerance is not None and (not opts.cull_unseen or opts.cull_unseen_tolerance < 0):
+        log("--cull-unseen-tolerance must be >= 0 and needs --cull-unseen")
+        return 2
     cleanup = opts.min_component_faces > 0 or opts.simplify > 0 or opts.normals
     log(f"meshing {select_ply} over {n_frames} frames ({opts.depth_source} depth, every {opts.every}, voxel {opts.voxel:g} m)")
     mapper = load_map(args, device, select_ply)
@@ -281,7 +288,8 @@ def cmd_mesh(opts) -> int:
     vertices, faces, colors, report, *normals = meshing.mesh_from_map(
         mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
         trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume,
-        min_component_faces=opts.min_component_faces, simplify_cell=opts.simplify, normals=opts.normals)
+        min_component_faces=opts.min_component_faces, simplify_cell=opts.simplify, normals=opts.normals,
+        cull_unseen=opts.cull_unseen, cull_unseen_tolerance=opts.cull_unseen_tolerance)
     report["total_s"] = time.perf_counter() - t0
     path = os.path.join(model_base, MESH_PLY)
     t0 = time.perf_counter()
@@ -293,6 +301,10 @@ def cmd_mesh(opts) -> int:
     log(f"mesh: {report['V']} vertices, {report['F']} faces from {report['frames_fused']} frames into a "
         f"{'x'.join(str(d) for d in report['dims'])} grid: render {report['render_s']:.3f} s, integrate "
         f"{report['integrate_s']:.3f} s, extract {report['extract_s']:.3f} s, write {report['write_s']:.3f} s -> {path}")
+    if opts.cull_unseen:
+        log(f"cull unseen: {report['F_unseen_removed']} of {report['F_raw']} faces and {report['V_unseen_removed']} of "
+            f"{report['V_raw']} vertices no fused view saw (tolerance {report['cull_unseen']:g} m) removed: render "
+            f"{report['cull_render_s']:.3f} s")
     if cleanup:
         log(f"clean-up: {report['V_raw']} vertices, {report['F_raw']} faces raw -> {report['V']} vertices, {report['F']} faces; "
             f"{report.get('components_removed', 0)} of {report.get('components', 'all')} components removed"
@@ -323,6 +335,14 @@ def cmd_metric(opts) -> int:
         if not os.path.isfile(mesh_path):
             log(f"--mesh: {mesh_path} does not exist; write it first with `python -m rtg_slam_amd mesh --config {opts.config}`")
             return 2
+    if opts.mesh_depth:
+        mesh_depth_path = os.path.join(model_base, MESH_PLY)
+        if not os.path.isfile(mesh_depth_path):
+            log(f"--mesh-depth: {mesh_depth_path} does not exist; write it first with `python -m rtg_slam_amd mesh --config {opts.config}`")
+            return 2
+    if opts.cull_depth == "mesh" and not opts.cull_gt:
+        log("--cull-depth mesh needs --cull-gt")
+        return 2
     if opts.cull_gt and (opts.cull_tolerance < 0 or opts.cull_min_views < 1):
         log("--cull-tolerance must be >= 0 and --cull-min-views >= 1")
         return 2
@@ -340,6 +360,7 @@ def cmd_metric(opts) -> int:
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
     log(f"evaluating at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
     gt_points, transform, rec_points, gt_cull = None, None, None, None
+    mesh_renderer, gt_mesh_renderer = None, None
     if info.mesh_path and os.path.isfile(info.mesh_path):
         v, f = iof.load_mesh_ply(info.mesh_path)
         transform = datasets.read_pose_t0(args)
@@ -348,6 +369,8 @@ def cmd_metric(opts) -> int:
                                                 min_views=opts.cull_min_views, any_vertex=opts.cull_keep == "any", device=device)
         else:
             gt_points, _ = iof.sample_mesh_surface(v, f, 1_000_000)
+        if opts.mesh_depth or opts.cull_depth == "mesh":
+            gt_mesh_renderer = evaluation.MeshRenderer(v, f, info.camera(), transform=transform, device=device)
         if mesh_path is not None:
             log(f"geometry eval mesh: {mesh_path}")
             mv, mf = iof.load_mesh_ply(mesh_path)
@@ -359,9 +382,13 @@ def cmd_metric(opts) -> int:
             if xyz.shape[0] == 0:
                 raise ValueError(f"rtg_slam_amd: {pcd_path} holds no points")
             rec_points = torch.from_numpy(xyz).to(device=device, dtype=torch.float32)
+    if opts.mesh_depth:                      # the mesh lies in the stream's frame: no transform
+        mv, mf = iof.load_mesh_ply(os.path.join(model_base, MESH_PLY))
+        mesh_renderer = evaluation.MeshRenderer(mv, mf, info.camera(), device=device)
     res = evaluation.evaluate_sequence(mapper, info.camera(), source, poses=poses, args=args, gt_points=gt_points,
                                        dist_thres=[0.03], transform=transform, sample_nums=1_000_000, rec_points=rec_points,
-                                       gt_cull=gt_cull)
+                                       gt_cull=gt_cull, mesh_renderer=mesh_renderer, gt_mesh_renderer=gt_mesh_renderer,
+                                       gt_cull_depth=opts.cull_depth)
     if gt_cull is not None:
         cull_dir = os.path.join(args.save_path, "eval_metric")
         os.makedirs(cull_dir, exist_ok=True)
@@ -369,9 +396,27 @@ def cmd_metric(opts) -> int:
         iof.save_mesh_ply(cull_path, *gt_cull.mesh())
         report = gt_cull.report()
         report["gt_mesh"] = info.mesh_path
+        if opts.cull_depth == "mesh":
+            report["depth"] = "mesh"
         with open(os.path.join(cull_dir, GT_CULL_REPORT), "w") as fo:
             json.dump(report, fo, indent=1, default=float)
         log(f"geometry eval gt: culled {report['F_kept']} of {report['F']} faces over {report['frames']} frames -> {cull_path}")
+    if mesh_renderer is not None:
+        md_dir = os.path.join(args.save_path, "eval_metric")
+        os.makedirs(md_dir, exist_ok=True)
+        md_path = os.path.join(md_dir, f"mesh_depth_frame_{mapper.time}_iter_{test_iter}.csv")
+        rows = res["mesh_depth_rows"]
+        with open(md_path, "w") as fo:
+            keys = list(rows[0]) if rows else ["frame", "mesh_valid_ratio", "mesh_depth_l1"]
+            fo.write(",".join(keys) + "\n")
+            fo.write("".join(",".join(repr(r[k]) for k in keys) + "\n" for r in rows))
+        md = dict(res["mesh_depth_mean"])
+        md.update(frames=len(rows), near=mesh_renderer.near, mesh=os.path.join(model_base, MESH_PLY),
+                  render_s=mesh_renderer.seconds, gt_render_s=gt_mesh_renderer.seconds if gt_mesh_renderer is not None else None)
+        with open(os.path.join(md_dir, MESH_DEPTH_REPORT), "w") as fo:
+            json.dump(md, fo, indent=1, default=float)
+        log(f"mesh depth: L1 {100 * md.get('mesh_depth_l1', float('nan')):.3f} cm over {md.get('mesh_valid_ratio', float('nan')):.4f} "
+            f"of the pixels, {len(rows)} frames -> {md_path}")
     out = os.path.join(args.save_path, f"statis_frame_{mapper.time}_iter_{test_iter}.csv")
     iof.save_metrics_csv(out, res["rows"])
     m = res["mean"]
@@ -413,6 +458,13 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("--cull-min-views", type=int, default=1, help="frames that must see a vertex (default 1)")
     m.add_argument("--cull-keep", choices=("all", "any"), default="all",
                    help="keep a face when all of its corners were seen (default) or when any was")
+    m.add_argument("--cull-depth", choices=("sensor", "mesh"), default="sensor",
+                   help="with --cull-gt: test the GT vertices against the sensor depth (default) or against the GT mesh's own "
+                        "depth rendered at the GT pose, which has no holes and no noise")
+    m.add_argument("--mesh-depth", action="store_true",
+                   help="render save_model/mesh_tsdf.ply at every evaluated pose and write its depth L1 against the sensor depth "
+                        "(and against the GT mesh rendered at the GT pose, where there is one) to eval_metric/mesh_depth_frame_F_iter_I.csv "
+                        "and eval_metric/mesh_depth_report.json")
     t = sub.add_parser("mesh", help="fuse the map into a TSDF volume and write save_model/mesh_tsdf.ply")
     t.add_argument("--config", required=True)
     t.add_argument("--load-frame", type=int, default=-1)
@@ -432,6 +484,11 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--simplify", type=float, default=0.0, metavar="CELL",
                    help="cluster the vertices on a grid of CELL metres, larger than the voxel (default 0: off)")
     t.add_argument("--normals", action="store_true", help="write per-vertex normals (nx ny nz) into the PLY")
+    t.add_argument("--cull-unseen", action="store_true",
+                   help="after the extraction, remove the faces with a corner no fused view saw: the mesh is rendered at every "
+                        "fused pose and its vertices are tested against that depth")
+    t.add_argument("--cull-unseen-tolerance", type=float, default=None, metavar="T",
+                   help="metres a vertex may lie behind the rendered depth and still count as seen (default: the voxel)")
     t.add_argument("--device", default="cuda:0")
     t.add_argument("--io-workers", type=int, default=None)
     t.add_argument("--resolution-scale", type=float, default=None,

@@ -275,6 +275,10 @@ _SIGNATURES = {
     "rtgs_visibility_add": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P,
                                       C.c_float, _P, _P]),
     "rtgs_visibility_keep_faces": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
+    # mesh render
+    "rtgs_mesh_render_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "rtgs_mesh_render": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                   _P, C.c_float, C.c_int32, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

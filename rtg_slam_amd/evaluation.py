@@ -12,6 +12,8 @@
     eval_mesh          (no counterpart)       eval_pcd of points sampled on a triangle mesh's surface (rtg_slam_amd.meshing)
     VisibilityCull     (no counterpart)       the part of the GT mesh the evaluated frames saw: per vertex, against the sensor
                                               depth, at the GT poses (include/rtgs_slam.h, "visibility")
+    MeshRenderer       (no counterpart)       the depth and face maps of a triangle mesh at a pose (include/rtgs_slam.h, "mesh
+                                              render"); mesh_depth_metrics: the depth L1 of such a map
 
 Each metric call reads its float64 result vector from the device once; that read is its only synchronisation.  The results
 are bitwise reproducible run to run (fixed-order reductions, no float atomics).  There is no CPU path."""
@@ -332,6 +334,129 @@ class VisibilityCull:
                 "keep": "any" if self.any_vertex else "all", "seconds": self._seconds}
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# rendering a triangle mesh: depth and face maps
+# ---------------------------------------------------------------------------------------------------------------------
+
+MESH_RENDER_NEAR = 0.05
+# Boxes of more than this many pixels go to the wave path of csrc/mesh_render.hip (DESIGN.md §4h has the measurement).
+MESH_RENDER_SMALL_MAX = 16
+
+
+class MeshRenderer:
+    """The depth map and the face map of a triangle mesh at a pinhole pose (include/rtgs_slam.h, "mesh render"): per pixel
+    centre the nearest surface and the face it belongs to, both windings, bit for bit tests/mesh_render_reference.py.
+
+        r = MeshRenderer(vertices, faces, cam, transform=pose_t0)
+        depth, face = r.render(c2w)            # [H,W] float32 metres (0: nothing), [H,W] int32 (-1: nothing)
+
+    vertices [V,3] and faces [F,3] are arrays or device tensors, cast to float32 / int32 and checked once, here, as
+    VisibilityCull does; `transform @ c2w` is the camera in the mesh's frame.  A face with a corner at or behind `near` metres
+    is dropped whole, not clipped: a camera within `near` of a large triangle sees a hole there.  small_max: the largest pixel
+    box one thread walks (larger faces take a wave each); it changes the time only, never the picture."""
+
+    def __init__(self, vertices, faces, cam, transform=None, near: float = MESH_RENDER_NEAR, small_max: Optional[int] = None,
+                 device=None):
+        for t in (vertices, faces):
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise RuntimeError("rtg_slam_amd.evaluation: tensors must live on a HIP device; this build has no CPU path.")
+        if device is None:
+            device = next((t.device for t in (vertices, faces) if torch.is_tensor(t)), None)
+            device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("rtg_slam_amd.evaluation: MeshRenderer needs a HIP device; this build has no CPU path.")
+        self.near = float(np.float32(near))
+        if not self.near > 0:
+            raise ValueError(f"rtg_slam_amd.evaluation: near must be > 0, got {near}")
+        self.small_max = MESH_RENDER_SMALL_MAX if small_max is None else int(small_max)
+        if not 0 <= self.small_max < 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.evaluation: small_max must lie in 0..2^31 - 1, got {small_max}")
+        V = int(vertices.shape[0])
+        if V >= 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.evaluation: {V} vertices do not fit the int32 face indices")
+        up = lambda a, dt: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=self.device, dtype=dt)
+        self.vertices = up(vertices, torch.float32).reshape(-1, 3).contiguous()
+        f = up(faces, torch.int64).reshape(-1, 3)
+        if f.shape[0] >= 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.evaluation: {f.shape[0]} faces do not fit the int32 face map")
+        if f.shape[0]:
+            lo, hi = (int(x) for x in torch.aminmax(f))
+            if lo < 0 or hi >= V:
+                raise ValueError(f"rtg_slam_amd.evaluation: face indices must lie in 0..{V - 1}, found {lo}..{hi}")
+        self.faces = f.to(torch.int32).contiguous()
+        self.cam = cam
+        H, W = int(cam.H), int(cam.W)
+        if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.evaluation: cannot render a {H}x{W} picture")
+        self.transform = np.eye(4) if transform is None else np.asarray(transform, dtype=np.float64).reshape(4, 4)
+        n = _lib.load().rtgs_mesh_render_scratch_bytes(V, int(self.faces.shape[0]), H, W)
+        self._scratch = torch.empty((n + 7) // 8, dtype=torch.int64, device=self.device)      # once; 8-byte aligned keys
+        self.renders = 0
+        self._events: List = []
+        self._seconds = 0.0
+
+    def render(self, c2w):
+        """-> (depth [H,W] float32, face [H,W] int32), new tensors.  c2w: the camera's pose as the stream gives it; the matrix
+        used is inv(transform @ c2w), inverted in float64 on the host, then cast to float32.  No synchronisation."""
+        c2w = c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else np.asarray(c2w)
+        if c2w.size != 16:
+            raise ValueError(f"rtg_slam_amd.evaluation: c2w must be a 4x4 matrix, got shape {tuple(c2w.shape)}")
+        w2c = np.linalg.inv(self.transform @ c2w.astype(np.float64).reshape(4, 4)).astype(np.float32)
+        m = np.ascontiguousarray(w2c.reshape(-1)[:12])
+        H, W = int(self.cam.H), int(self.cam.W)
+        fx, fy, cx, cy = (float(np.float32(k)) for k in (self.cam.fx, self.cam.fy, self.cam.cx, self.cam.cy))
+        depth = torch.empty(H, W, dtype=torch.float32, device=self.device)
+        face = torch.empty(H, W, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            rc = _lib.load().rtgs_mesh_render(_p(self.vertices), int(self.vertices.shape[0]), _p(self.faces), int(self.faces.shape[0]),
+                                              H, W, fx, fy, cx, cy, (C.c_float * 12)(*m.tolist()), self.near, self.small_max,
+                                              _p(self._scratch), _p(depth), _p(face), _stream(self.device))
+            b.record()
+        _lib.check(rc, "rtgs_mesh_render")
+        self._events.append((a, b))
+        self.renders += 1
+        return depth, face
+
+    @property
+    def seconds(self) -> float:
+        """The device time of the renders so far (events, read here: synchronises on the last one)."""
+        for a, b in self._events:
+            b.synchronize()
+            self._seconds += a.elapsed_time(b) * 1e-3
+        self._events = []
+        return self._seconds
+
+
+def _mesh_depth_sums(mesh_depth: torch.Tensor, ref_depth: torch.Tensor, min_depth: float, max_depth: float) -> torch.Tensor:
+    """-> float64 [2] on the device: the number of valid pixels, the sum of |mesh_depth - ref_depth| over them."""
+    dev = _dev(mesh_depth, ref_depth)
+    if mesh_depth.dtype != torch.float32 or ref_depth.dtype != torch.float32:
+        raise ValueError("rtg_slam_amd.evaluation: mesh_depth and ref_depth must be float32")
+    if mesh_depth.numel() == 0 or mesh_depth.numel() != ref_depth.numel() or ref_depth.device != dev:
+        raise ValueError(f"rtg_slam_amd.evaluation: mesh_depth {tuple(mesh_depth.shape)} and ref_depth {tuple(ref_depth.shape)} "
+                         "must hold the same, non-zero number of pixels on one device")
+    m, r = mesh_depth.detach().reshape(-1), ref_depth.detach().reshape(-1)
+    lo, hi = float(np.float32(min_depth)), float(np.float32(max_depth))
+    valid = (m > 0) & (r > lo) & (r < hi)
+    diff = torch.where(valid, (m - r).abs(), torch.zeros_like(m))              # float32 differences, summed in float64
+    return torch.stack([valid.sum().to(torch.float64), diff.sum(dtype=torch.float64)])
+
+
+def _mesh_depth_result(sums, n_pixels: int, suffix: str = "") -> Dict[str, float]:
+    n, s = float(sums[0]), float(sums[1])
+    return {"mesh_valid_ratio" + suffix: n / n_pixels, "mesh_depth_l1" + suffix: s / n if n else 0.0}
+
+
+def mesh_depth_metrics(mesh_depth: torch.Tensor, ref_depth: torch.Tensor, min_depth: float, max_depth: float) -> Dict[str, float]:
+    """The depth L1 of a rendered mesh against a reference depth (a sensor frame, or a render of the GT mesh), in metres:
+    valid pixels are those with mesh_depth > 0 and min_depth < ref_depth < max_depth; "mesh_valid_ratio" is their share,
+    "mesh_depth_l1" the float64 mean of the float32 |mesh_depth - ref_depth| over them (0 without any).  One host read."""
+    return _mesh_depth_result(_mesh_depth_sums(mesh_depth, ref_depth, min_depth, max_depth).cpu().tolist(), mesh_depth.numel())
+
+
 def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: Optional[float] = None,
                max_depth: Optional[float] = None, renderer=None, run_picture: bool = True, run_pcd: bool = False,
                gt_points=None, dist_thres: Sequence[float] = (0.03,), sample_nums: int = 1_000_000, transform=None,
@@ -357,7 +482,8 @@ def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, mi
 def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_points=None, dist_thres: Sequence[float] = (0.03,),
                       transform=None, sample_nums: int = 1_000_000, generator: Optional[torch.Generator] = None,
                       with_ms_ssim: bool = True, rec_points: Optional[torch.Tensor] = None,
-                      gt_cull: Optional["VisibilityCull"] = None) -> Dict:
+                      gt_cull: Optional["VisibilityCull"] = None, mesh_renderer: Optional["MeshRenderer"] = None,
+                      gt_mesh_renderer: Optional["MeshRenderer"] = None, gt_cull_depth: str = "sensor") -> Dict:
     """metric.py:137-219 over a finished map.  `stream` yields (depth [H,W] metres, colour [3,H,W], GT c2w) as run_sequence's
     does; frame i is rendered at poses[i] (the estimated trajectory, e.g. tracker.pose_es) or, without poses, at its GT pose,
     by a Renderer whose opaque threshold is args.renderer_opaque_threshold_eval (metric.py:138).  With gt_points, the
@@ -366,7 +492,18 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
     With gt_cull (a VisibilityCull of the GT mesh), every frame's sensor depth and GT pose - never the estimated one, so the
     culled GT does not depend on the run being scored - go to gt_cull.add while the stream passes, and the GT points of the
     last frame's row are sampled from the culled mesh: as many as gt_points holds, 1 000 000 without gt_points.
+    With gt_cull_depth "mesh" the depth gt_cull.add receives is not the sensor's but gt_mesh_renderer's: the GT mesh's own depth
+    at the GT pose, which has no holes and no noise (gt_mesh_renderer is a MeshRenderer of the GT mesh with the cull's transform).
+    With mesh_renderer (a MeshRenderer of the reconstructed mesh, in the stream's frame) every frame also renders that mesh at
+    the pose the map is rendered at and scores its depth against the sensor depth (mesh_depth_metrics, args.min_depth and
+    max_depth) and, with gt_mesh_renderer, against the GT mesh rendered at the GT pose (keys ending in _gt).  These rows are
+    returned apart, under "mesh_depth_rows" and "mesh_depth_mean", and read from the device once, after the last frame: "rows"
+    and "mean" are what they are without the mesh renderers.
     Returns {"rows": one dict per frame (with "frame" and "iter"), "mean": the mean row of metric.py:205-211}."""
+    if gt_cull_depth not in ("sensor", "mesh"):
+        raise ValueError(f"rtg_slam_amd.evaluation: gt_cull_depth must be 'sensor' or 'mesh', got {gt_cull_depth!r}")
+    if gt_cull_depth == "mesh" and (gt_cull is None or gt_mesh_renderer is None):
+        raise ValueError("rtg_slam_amd.evaluation: gt_cull_depth='mesh' needs gt_cull and gt_mesh_renderer")
     from .mapping import Frame
     from .render import Renderer
     args = mapper.args if args is None else args
@@ -374,12 +511,22 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
     eval_args.renderer_opaque_threshold = float(getattr(args, "renderer_opaque_threshold_eval", 0.5))
     renderer = Renderer(eval_args)
     rows: List[Dict] = []
+    mesh_sums: List[torch.Tensor] = []
     for i, (depth, color, gt_c2w) in enumerate(stream):
         frame = Frame(cam, gt_c2w, mapper.device, uid=i)
+        gt_mesh_depth = None
+        if gt_mesh_renderer is not None and (mesh_renderer is not None or gt_cull_depth == "mesh"):
+            gt_mesh_depth, _ = gt_mesh_renderer.render(gt_c2w)
         if gt_cull is not None:
-            gt_cull.add(depth, gt_c2w)
+            gt_cull.add(gt_mesh_depth if gt_cull_depth == "mesh" else depth, gt_c2w)
         if poses is not None:
             frame.updatePose(np.asarray(poses[i], dtype=np.float64))         # metric.py:175-176
+        if mesh_renderer is not None:
+            mesh_depth, _ = mesh_renderer.render(poses[i] if poses is not None else gt_c2w)
+            sums = [_mesh_depth_sums(mesh_depth, depth.float(), args.min_depth, args.max_depth)]
+            if gt_mesh_depth is not None:
+                sums.append(_mesh_depth_sums(mesh_depth, gt_mesh_depth, args.min_depth, args.max_depth))
+            mesh_sums.append(torch.cat(sums))
         row = eval_frame(mapper, frame, color, depth, args.min_depth, args.max_depth, renderer=renderer,
                          with_ms_ssim=with_ms_ssim)
         row["frame"] = i
@@ -395,4 +542,16 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
         with torch.no_grad():
             rec = mapper.opt.gaussian_data("all")["xyz"] if rec_points is None else rec_points
             rows[-1].update(eval_pcd(rec, gt_points, dist_thres, transform, sample_nums, generator))
-    return {"rows": rows, "mean": metrics_mean_row(rows)}
+    res = {"rows": rows, "mean": metrics_mean_row(rows)}
+    if mesh_renderer is not None:
+        n_pixels = int(cam.H) * int(cam.W)
+        mesh_rows = []
+        for i, v in enumerate(torch.stack(mesh_sums).cpu().tolist() if mesh_sums else []):       # the one host read
+            row = {"frame": i, **_mesh_depth_result(v[:2], n_pixels)}
+            if len(v) > 2:
+                row.update(_mesh_depth_result(v[2:], n_pixels, "_gt"))
+            mesh_rows.append(row)
+        keys = [k for k in (mesh_rows[0] if mesh_rows else {}) if k != "frame"]
+        res["mesh_depth_rows"] = mesh_rows
+        res["mesh_depth_mean"] = {k: float(np.mean([r[k] for r in mesh_rows])) for k in keys}
+    return res

@@ -411,10 +411,40 @@ def map_bounds(mapper, pad: float):
     return [l - pad for l in lo], [h + pad for h in hi]
 
 
+def cull_unseen(vertices, faces, colors, cam, poses, tolerance: float, transform=None, near: Optional[float] = None):
+    """Remove the surface no pose could see -> (vertices, faces, colors, stats).  At every pose (c2w; `transform @ c2w` is the
+    camera in the mesh's frame) the mesh is rendered (evaluation.MeshRenderer) and its own vertices are tested against that
+    render (evaluation.VisibilityCull.add): a vertex is seen when it projects into a pixel whose rendered depth is not more
+    than `tolerance` metres in front of it.  A face stays when some pose saw each of its three corners (mesh_ops.keep_faces;
+    colours carried, colors may be None).  Visibility is decided per VERTEX, not by which faces won a pixel: at fine voxels
+    most faces cover no pixel centre, and a face-map rule would punch holes into visible surface.  stats: "tolerance",
+    "poses", "F_removed", "V_removed", "render_s" (device time of the renders) and "cull_s" (of the vertex tests)."""
+    from . import evaluation, mesh_ops
+    kw = {} if near is None else {"near": near}
+    renderer = evaluation.MeshRenderer(vertices, faces, cam, transform=transform, **kw)
+    cull = evaluation.VisibilityCull(renderer.vertices, renderer.faces, cam, transform=transform, tolerance=tolerance,
+                                     device=renderer.device)
+    for c2w in poses:
+        c2w = _host_pose(c2w)
+        depth, _ = renderer.render(c2w)
+        cull.add(depth, c2w)
+    if colors is not None:
+        colors = torch.as_tensor(colors).to(device=renderer.device)
+    v, f, c = mesh_ops.keep_faces(renderer.vertices, renderer.faces, colors, cull.keep())
+    rep = cull.report()
+    stats = {"tolerance": cull.tolerance, "poses": cull.frames, "F_removed": int(renderer.faces.shape[0]) - int(f.shape[0]),
+             "V_removed": int(renderer.vertices.shape[0]) - int(v.shape[0]), "render_s": renderer.seconds, "cull_s": rep["seconds"]}
+    return v, f, c, stats
+
+
+_cull_unseen = cull_unseen                        # mesh_from_map has a flag of that name
+
+
 def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *, voxel: float = 0.01, depth_source: str = "render",
                   every: int = 1, bounds=None, trunc: Optional[float] = None, max_weight: float = 64, min_weight: float = 1,
                   args=None, device=None, max_bytes: int = MAX_BYTES, volume: str = "dense", min_component_faces: int = 0,
-                  simplify_cell: float = 0.0, normals: bool = False):
+                  simplify_cell: float = 0.0, normals: bool = False, cull_unseen: bool = False,
+                  cull_unseen_tolerance: Optional[float] = None):
     """Fuse a trajectory into a TsdfVolume (volume "dense") or a SparseTsdfVolume ("sparse") and extract its mesh ->
     (vertices, faces, colors, report).
 
@@ -432,7 +462,12 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
     cell anchored at the volume's lo; normals=True adds the final mesh's vertex normals as a FIFTH result, (vertices, faces,
     colors, report, normals).  With any of the three on, the report's V and F are the final counts and it gains "V_raw",
     "F_raw", the removal's "components", "components_removed", "faces_removed" and "vertices_removed" (when it ran),
-    "simplify_cell", "normals" and "cleanup_s"."""
+    "simplify_cell", "normals" and "cleanup_s".
+
+    cull_unseen=True removes, after the extraction and before the clean-up, the surface no fused view could see (cull_unseen
+    below, at the fused poses, cull_unseen_tolerance metres, default the voxel): the report's V and F are the counts after it
+    and it gains "cull_unseen" (the tolerance), "F_unseen_removed", "V_unseen_removed", "cull_render_s" and, as with the
+    clean-up, "V_raw" and "F_raw": the extracted counts."""
     from .mapping import Frame
     from .render import Renderer
     if volume not in ("dense", "sparse"):
@@ -461,6 +496,7 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         eval_args.renderer_opaque_threshold = float(getattr(args, "renderer_opaque_threshold_eval", 0.5))
         renderer = Renderer(eval_args)
     t_render = t_integrate = 0.0
+    fused_poses = []
     source = stream if stream is not None else ((None, None, p) for p in poses)
     for i, (depth, color, gt_c2w) in enumerate(source):
         if poses is not None and i >= len(poses):
@@ -482,6 +518,7 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         vol.integrate(depth, color, cam, c2w)
         torch.cuda.synchronize(device)
         t_integrate += time.perf_counter() - t0
+        fused_poses.append(c2w)
     t0 = time.perf_counter()
     vertices, faces, colors = vol.extract_mesh(min_weight)
     torch.cuda.synchronize(device)
@@ -493,6 +530,14 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         n_table = vol.brick_dims[0] * vol.brick_dims[1] * vol.brick_dims[2]
         report.update({"volume": "sparse", "bricks": vol.n_bricks, "brick_share": vol.n_bricks / n_table,
                        "pool_bytes": vol.pool_bytes, "dense_bytes": vol.dense_bytes})
+    v_raw, f_raw = report["V"], report["F"]
+    if cull_unseen:
+        tolerance = float(vol.voxel if cull_unseen_tolerance is None else cull_unseen_tolerance)
+        vertices, faces, colors, stats = _cull_unseen(vertices, faces, colors, cam, fused_poses, tolerance)
+        report.update({"V_raw": v_raw, "F_raw": f_raw, "V": int(vertices.shape[0]), "F": int(faces.shape[0]),
+                       "cull_unseen": stats["tolerance"],
+                       "F_unseen_removed": f_raw - int(faces.shape[0]), "V_unseen_removed": v_raw - int(vertices.shape[0]),
+                       "cull_render_s": stats["render_s"]})
     if min_component_faces > 0 or simplify_cell > 0 or normals:
         from . import mesh_ops
         t0 = time.perf_counter()
@@ -500,7 +545,7 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
             vertices, faces, colors, min_component_faces=min_component_faces, simplify_cell=simplify_cell, origin=vol.lo,
             normals=normals)
         torch.cuda.synchronize(device)
-        report.update({"V_raw": report["V"], "F_raw": report["F"], "V": int(vertices.shape[0]), "F": int(faces.shape[0]), **stats,
+        report.update({"V_raw": v_raw, "F_raw": f_raw, "V": int(vertices.shape[0]), "F": int(faces.shape[0]), **stats,
                        "simplify_cell": simplify_cell, "normals": normals, "cleanup_s": time.perf_counter() - t0})
         if normals:
             return vertices, faces, colors, report, nrm
