@@ -427,6 +427,52 @@ int rtgs_mesh_cluster_faces(const int32_t* faces, int64_t F, const int32_t* clus
                             void* stream);
 int rtgs_mesh_mark_first(const int32_t* faces, const int64_t* ids, int64_t n, int32_t* keep, void* stream);
 
+/* ---- mesh decimation: parallel quadric-error half-edge collapse (no counterpart in the reference; csrc/mesh_decimate.hip).
+ * The same mesh and the same guarantees as the mesh operations above.  A collapse u -> v removes vertex u and moves nothing;
+ * the float work is float64, one rounded operation per step, in the order tests/mesh_decimate_reference.py writes out, and
+ * the kernels match it bit for bit.  The caller (rtg_slam_amd/mesh_ops.py decimate) runs rounds on the CURRENT faces, with
+ * `order` and `start` as for rtgs_mesh_vertex_normals; its sorts and scans sit between the calls.
+ *
+ * rtgs_mesh_decimate_quadrics, once.  quadrics [V][11] float64: per face in its stored corner order n = (pb - pa) x (pc - pa)
+ *   (a component two products and a difference), l = sqrt((nx nx + ny ny) + nz nz); nothing unless l > 0; pl = (n / l,
+ *   -(((nx/l) pax + (ny/l) pay) + (nz/l) paz)), w = l / 2; the record is w (pl_i pl_j) for the 10 pairs i <= j in row order,
+ *   then w.  A vertex's quadric starts at 0 and adds its corners' records in ascending corner index.
+ * rtgs_mesh_decimate_edge_keys.  keys [3 F] int64 = min V + max of the edges (a,b) (b,c) (c,a).  rtgs_mesh_decimate_locks,
+ *   given the n distinct keys in ascending order and their counts, writes locked[x] = 1 (locked [V], zeroed by the caller)
+ *   for both vertices of every edge whose count is not 2.
+ * rtgs_mesh_decimate_propose.  Vertex u is removable when it is not locked and has RTGS_MESH_DECIMATE_MIN_VALENCE ..
+ *   RTGS_MESH_DECIMATE_MAX_VALENCE faces.  A neighbour v is valid when (a) N(u) and N(v) share exactly 2 vertices, (b) every
+ *   face (u, x, y) of u without v has ((px - pu) x (py - pu)) . ((px - pv) x (py - pv)) > 0, the dot (xx + yy) + zz, or p_v == p_u, and (d)
+ *   with max_error > 0 (0: no bound), sqrt(cost / q[10]) <= max_error; (c) q = Q[u] + Q[v], cost = p_v^T q p_v as r_i =
+ *   ((q_i0 x + q_i1 y) + q_i2 z) + q_i3, ((r0 x + r1 y) + r2 z) + r3, and 0 unless that is > 0.  proposal [V] = the valid v
+ *   with the smallest (cost, v), -1 without one or for a vertex that is not removable; cost [V] float64 = its cost.
+ * rtgs_mesh_decimate_claim.  ranked [>= P] int64 = the proposing vertices in rank order.  Participant r < P lowers claim[x]
+ *   (claim [V] int32, filled with INT32_MAX by the caller) to r, by atomicMin, for every x of N[u] + N[v], the closed
+ *   neighbourhoods.  rtgs_mesh_decimate_select then writes selected [P] = 1 where claim[x] == r for all of them, else 0: two
+ *   selected collapses have disjoint N[u] + N[v].
+ * rtgs_mesh_decimate_apply.  For every r < P with applied[r] != 0: remap[u] = v (remap [V], the identity before the first
+ *   round) and Q[v] = Q[v] + Q[u].  rtgs_mesh_decimate_reindex writes keep [F] = 0 for a face two of whose corners are equal
+ *   after remap, else 1; rtgs_mesh_compact_faces with vmap = remap then gives the next round's faces.
+ * Return 0 (also, without a launch, for nothing to do), -1 on a bad argument (a null pointer that is needed, a count < 0 or
+ * >= 2^31, a NaN max_error), -2 on a launch failure. */
+#define RTGS_MESH_DECIMATE_MIN_VALENCE 4
+#define RTGS_MESH_DECIMATE_MAX_VALENCE 32
+#define RTGS_MESH_DECIMATE_MAX_ROUNDS 1000
+int rtgs_mesh_decimate_quadrics(const float* vertices, const int32_t* faces, int64_t V, int64_t F, const int64_t* order,
+                                const int64_t* start, double* quadrics, void* stream);
+int rtgs_mesh_decimate_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, void* stream);
+int rtgs_mesh_decimate_locks(const int64_t* keys, const int64_t* counts, int64_t n, int64_t V, int32_t* locked, void* stream);
+int rtgs_mesh_decimate_propose(const float* vertices, const int32_t* faces, int64_t V, int64_t F, const int64_t* order,
+                               const int64_t* start, const int32_t* locked, const double* quadrics, double max_error,
+                               int32_t* proposal, double* cost, void* stream);
+int rtgs_mesh_decimate_claim(const int32_t* faces, const int64_t* order, const int64_t* start, const int64_t* ranked,
+                             const int32_t* proposal, int64_t P, int32_t* claim, void* stream);
+int rtgs_mesh_decimate_select(const int32_t* faces, const int64_t* order, const int64_t* start, const int64_t* ranked,
+                              const int32_t* proposal, int64_t P, const int32_t* claim, int32_t* selected, void* stream);
+int rtgs_mesh_decimate_apply(const int64_t* ranked, const int32_t* proposal, const int32_t* applied, int64_t P, int32_t* remap,
+                             double* quadrics, void* stream);
+int rtgs_mesh_decimate_reindex(const int32_t* faces, int64_t F, const int32_t* remap, int32_t* keep, void* stream);
+
 /* ---- visibility: which points a depth frame saw, which faces that leaves (no counterpart in the reference;
  * csrc/visibility.hip).  tests/visibility_reference.py restates both in numpy; the kernels match it bit for bit.
  *

@@ -272,7 +272,13 @@ def cmd_mesh(opts) -> int:
     if opts.cull_unseen_tolerance is not None and (not opts.cull_unseen or opts.cull_unseen_tolerance < 0):
         log("--cull-unseen-tolerance must be >= 0 and needs --cull-unseen")
         return 2
-    cleanup = opts.min_component_faces > 0 or opts.simplify > 0 or opts.normals
+    if not 0 <= opts.decimate < 1:
+        log(f"--decimate {opts.decimate:g}: the share of faces to keep must be >= 0 (off) and < 1")
+        return 2
+    if opts.decimate_max_error is not None and not (opts.decimate > 0 and opts.decimate_max_error > 0):
+        log("--decimate-max-error must be > 0 and needs --decimate")
+        return 2
+    cleanup = opts.min_component_faces > 0 or opts.simplify > 0 or opts.normals or opts.decimate > 0
     log(f"meshing {select_ply} over {n_frames} frames ({opts.depth_source} depth, every {opts.every}, voxel {opts.voxel:g} m)")
     mapper = load_map(args, device, select_ply)
     mapper.time = int(check_frame.split("_")[1])
@@ -289,7 +295,8 @@ def cmd_mesh(opts) -> int:
         mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
         trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume,
         min_component_faces=opts.min_component_faces, simplify_cell=opts.simplify, normals=opts.normals,
-        cull_unseen=opts.cull_unseen, cull_unseen_tolerance=opts.cull_unseen_tolerance)
+        cull_unseen=opts.cull_unseen, cull_unseen_tolerance=opts.cull_unseen_tolerance, decimate=opts.decimate,
+        decimate_max_error=opts.decimate_max_error)
     report["total_s"] = time.perf_counter() - t0
     path = os.path.join(model_base, MESH_PLY)
     t0 = time.perf_counter()
@@ -310,6 +317,11 @@ def cmd_mesh(opts) -> int:
             f"{report.get('components_removed', 0)} of {report.get('components', 'all')} components removed"
             f"{', simplified at %g m' % report['simplify_cell'] if report['simplify_cell'] > 0 else ''}"
             f"{', with normals' if report['normals'] else ''}: {report['cleanup_s']:.3f} s")
+    if opts.decimate > 0:
+        log(f"decimation: {report['F_before_decimate']} faces -> {report['F']} faces ({100 * opts.decimate:g} % asked for"
+            f"{', error <= %g m' % report['decimate_max_error'] if report['decimate_max_error'] is not None else ''}); "
+            f"{report['decimate_collapses']} collapses in {report['decimate_rounds']} rounds, target "
+            f"{'reached' if report['decimate_target_reached'] else 'NOT reached'}: {report['decimate_s']:.3f} s")
     if opts.volume == "sparse":
         log(f"sparse volume: {report['bricks']} bricks, {100 * report['brick_share']:.2f} % of the grid's, "
             f"{report['pool_bytes'] / 2 ** 20:.1f} MiB of pool where the dense planes would take {report['dense_bytes'] / 2 ** 20:.1f} MiB")
@@ -484,6 +496,11 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--simplify", type=float, default=0.0, metavar="CELL",
                    help="cluster the vertices on a grid of CELL metres, larger than the voxel (default 0: off)")
     t.add_argument("--normals", action="store_true", help="write per-vertex normals (nx ny nz) into the PLY")
+    t.add_argument("--decimate", type=float, default=0.0, metavar="R",
+                   help="after the other clean-up, collapse edges by quadric error until the share R of the faces is left, "
+                        "0 <= R < 1 (default 0: off); vertices are removed, never moved")
+    t.add_argument("--decimate-max-error", type=float, default=None, metavar="E",
+                   help="with --decimate: refuse a collapse whose error exceeds E metres, even if the target is then not reached")
     t.add_argument("--cull-unseen", action="store_true",
                    help="after the extraction, remove the faces with a corner no fused view saw: the mesh is rendered at every "
                         "fused pose and its vertices are tested against that depth")

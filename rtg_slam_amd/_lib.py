@@ -271,6 +271,15 @@ _SIGNATURES = {
     "rtgs_mesh_cluster_means": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "rtgs_mesh_cluster_faces": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "rtgs_mesh_mark_first": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    # mesh decimation
+    "rtgs_mesh_decimate_quadrics": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "rtgs_mesh_decimate_edge_keys": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
+    "rtgs_mesh_decimate_locks": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    "rtgs_mesh_decimate_propose": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, _P, _P, _P]),
+    "rtgs_mesh_decimate_claim": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "rtgs_mesh_decimate_select": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    "rtgs_mesh_decimate_apply": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
+    "rtgs_mesh_decimate_reindex": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     # visibility
     "rtgs_visibility_add": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P,
                                       C.c_float, _P, _P]),

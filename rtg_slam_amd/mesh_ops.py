@@ -1,5 +1,6 @@
-"""Mesh clean-up on the HIP kernels of include/rtgs_slam.h, "mesh operations" (csrc/mesh_ops.hip): what a raw
-marching-tetrahedra mesh needs before it is usable.  The reference has no mesher and so none of this.
+"""Mesh clean-up on the HIP kernels of include/rtgs_slam.h, "mesh operations" (csrc/mesh_ops.hip) and "mesh decimation"
+(csrc/mesh_decimate.hip): what a raw marching-tetrahedra mesh needs before it is usable.  The reference has no mesher and
+so none of this.
 
     vertex_normals            area-weighted per-vertex normals, towards free space
     component_labels          label[v] = the smallest vertex index joined to v through faces
@@ -7,12 +8,14 @@ marching-tetrahedra mesh needs before it is usable.  The reference has no mesher
     compact                   drop the vertices no face uses, by itself
     keep_faces                keep the faces a caller's mask names, then drop the vertices nobody uses
     simplify_clusters         vertex clustering on a grid of `cell` metres: one vertex per occupied cell
+    decimate                  quadric-error half-edge collapse to a target face count (csrc/mesh_decimate.hip): vertices are
+                              removed, never moved, so corners stay sharp and the result stays manifold
 
 All take an indexed mesh on the device - vertices [V,3] float32, faces [F,3] int32, colours [V,3] float32 - from
 TsdfVolume.extract_mesh, SparseTsdfVolume.extract_mesh or another of these.  Every result is unique and independent of
-thread order: two runs are bit-equal, and tests/mesh_ops_reference.py restates each in numpy, matched bit for bit.  The
-kernels do the float work and the per-element decisions; the scans and stable sorts between them are torch's.
-There is no CPU path."""
+thread order: two runs are bit-equal, and tests/mesh_ops_reference.py (decimate: tests/mesh_decimate_reference.py) restates
+each in numpy, matched bit for bit.  The kernels do the float work and the per-element decisions; the scans and stable
+sorts between them are torch's.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,6 +27,10 @@ import torch
 from . import _lib
 
 MAX_CELLS = 1 << 21                  # RTGS_MESH_MAX_CELLS: cells per axis, so that a key fits int64
+DECIMATE_MIN_VALENCE = 4             # RTGS_MESH_DECIMATE_MIN_VALENCE
+DECIMATE_MAX_VALENCE = 32            # RTGS_MESH_DECIMATE_MAX_VALENCE
+DECIMATE_MAX_ROUNDS = 1000           # RTGS_MESH_DECIMATE_MAX_ROUNDS
+_DECIMATE_HASH = 2654435761          # h(u) = u * this mod 2^32: the tie-break between equal costs
 
 
 def _p(t):
@@ -258,14 +265,136 @@ def simplify_clusters(vertices: torch.Tensor, faces: torch.Tensor, colors: torch
     return out_v, out_f, out_c
 
 
+def _corner_lists(faces, V):
+    """-> (order, start): the corner indices 3 f + k sorted stably by their vertex, and every vertex's first position."""
+    corner_vertex = faces.reshape(-1)
+    order = torch.sort(corner_vertex, stable=True).indices
+    start = torch.zeros(V + 1, dtype=torch.int64, device=faces.device)
+    if faces.shape[0]:
+        torch.cumsum(torch.bincount(corner_vertex, minlength=V), 0, out=start[1:])
+    return order, start
+
+
+def _decimate_round(vertices, faces, V, quadrics, remap, target, max_error):
+    """One round on the current faces -> (the faces after it, the collapses applied).  quadrics and remap are updated."""
+    dev = vertices.device
+    lib = _lib.load()
+    s = _stream(dev)
+    Fn = int(faces.shape[0])
+    order, start = _corner_lists(faces, V)
+    # 1. locks: the vertices of every edge that does not have exactly 2 faces
+    keys = torch.empty(3 * Fn, dtype=torch.int64, device=dev)
+    locked = torch.zeros(V, dtype=torch.int32, device=dev)
+    prop = torch.empty(V, dtype=torch.int32, device=dev)
+    cost = torch.empty(V, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rtgs_mesh_decimate_edge_keys(_p(faces), Fn, V, _p(keys), s), "rtgs_mesh_decimate_edge_keys")
+        edges, counts = torch.unique_consecutive(torch.sort(keys).values, return_counts=True)
+        _lib.check(lib.rtgs_mesh_decimate_locks(_p(edges), _p(counts), int(edges.shape[0]), V, _p(locked), s),
+                   "rtgs_mesh_decimate_locks")
+        # 2. every removable vertex proposes its cheapest valid neighbour
+        _lib.check(lib.rtgs_mesh_decimate_propose(_p(vertices), _p(faces), V, Fn, _p(order), _p(start), _p(locked), _p(quadrics),
+                                                  0.0 if max_error is None else max_error, _p(prop), _p(cost), s),
+                   "rtgs_mesh_decimate_propose")
+    who = torch.nonzero(prop >= 0).reshape(-1)
+    if who.shape[0] == 0:
+        return faces, 0
+    # 3. rank by (cost, h(u), u): h and u in one key (h < 2^32, u < 2^31), then stably by the cost, whose bits order as it does
+    # (a cost is >= 0 and never NaN)
+    by_hash = torch.sort((((who * _DECIMATE_HASH) & 0xFFFFFFFF) << 31) | who).indices
+    by_cost = torch.sort(cost[who].view(torch.int64)[by_hash], stable=True).indices
+    ranked = who[by_hash[by_cost]].contiguous()
+    # 4. the 2 k lowest ranks claim their closed neighbourhoods; who holds all its claims is selected, the first k are applied
+    k = (Fn - target + 1) // 2
+    P = min(2 * k, int(ranked.shape[0]))
+    claim = torch.full((V,), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+    selected = torch.empty(P, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rtgs_mesh_decimate_claim(_p(faces), _p(order), _p(start), _p(ranked), _p(prop), P, _p(claim), s),
+                   "rtgs_mesh_decimate_claim")
+        _lib.check(lib.rtgs_mesh_decimate_select(_p(faces), _p(order), _p(start), _p(ranked), _p(prop), P, _p(claim), _p(selected), s),
+                   "rtgs_mesh_decimate_select")
+    applied = (selected * (torch.cumsum(selected, 0) <= k)).to(torch.int32)
+    # 5. apply, re-index, drop the faces that lost a corner
+    keep = torch.empty(Fn, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rtgs_mesh_decimate_apply(_p(ranked), _p(prop), _p(applied), P, _p(remap), _p(quadrics), s),
+                   "rtgs_mesh_decimate_apply")
+        _lib.check(lib.rtgs_mesh_decimate_reindex(_p(faces), Fn, _p(remap), _p(keep), s), "rtgs_mesh_decimate_reindex")
+    n = int(applied.sum())
+    f_off, n_f = _exclusive(keep)
+    if Fn - n_f != 2 * n:
+        raise RuntimeError(f"rtg_slam_amd.mesh_ops: decimate applied {n} collapses and lost {Fn - n_f} faces, not {2 * n}")
+    out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+    if n_f:
+        with torch.cuda.device(dev):
+            _lib.check(lib.rtgs_mesh_compact_faces(_p(faces), Fn, _p(keep), _p(f_off), _p(remap), _p(out_f), s),
+                       "rtgs_mesh_compact_faces")
+    return out_f, n
+
+
+def decimate(vertices: torch.Tensor, faces: torch.Tensor, colors: torch.Tensor, target_faces: int,
+             max_error: Optional[float] = None):
+    """Quadric-error decimation by HALF-EDGE collapse to target_faces faces -> (vertices, faces, colors, stats).  A collapse
+    u -> v removes vertex u and moves nothing: the output vertices and colours are a subset of the input's in their order,
+    the surviving faces keep their order and winding, re-indexed.  It runs in rounds on the current faces:
+      1  a vertex on an edge that does not have exactly 2 faces (boundary, non-manifold) is locked: never removed, but a
+         possible target; neither is a vertex with fewer than DECIMATE_MIN_VALENCE or more than DECIMATE_MAX_VALENCE faces
+      2  every other vertex u proposes the neighbour v of smallest (cost, v) among those that keep the surface sound (N(u) and
+         N(v) share exactly 2 vertices; no face of u flips or loses its area) and, with max_error (metres) given, have
+         sqrt(cost / weight) <= max_error; cost = p_v^T (Q[u] + Q[v]) p_v with the area-weighted plane quadrics Q in float64
+      3  proposals are ranked by (cost, u * 2654435761 mod 2^32, u); k = ceil((F_now - target_faces) / 2) are still needed,
+         the 2 k first take part
+      4  each claims the closed neighbourhoods of u and v with an atomic minimum of its rank; who holds all its claims is
+         selected, so no two selected collapses touch; the k first are applied: Q[v] += Q[u], faces re-indexed
+    until F <= target_faces, a round applies nothing or DECIMATE_MAX_ROUNDS rounds ran; then the unused vertices go.  Every
+    collapse removes exactly 2 faces, so the result has target_faces or target_faces - 1 faces when enough valid collapses
+    exist.  stats: "rounds", "collapses", "faces_removed", "vertices_removed", "target_reached".  F <= target_faces returns
+    the mesh compacted and otherwise untouched.  tests/mesh_decimate_reference.py is the definition, matched bit for bit."""
+    target = int(target_faces)
+    if target < 0:
+        raise ValueError(f"rtg_slam_amd.mesh_ops: decimate needs target_faces >= 0, got {target}")
+    if max_error is not None:
+        max_error = float(max_error)
+        if not max_error > 0:
+            raise ValueError(f"rtg_slam_amd.mesh_ops: decimate needs max_error > 0 (metres) or None, got {max_error}")
+    vertices, faces, colors, V, F = _check(vertices, faces, colors)
+    dev = vertices.device
+    rounds = collapses = 0
+    if F > target:
+        quadrics = torch.empty(V, 11, dtype=torch.float64, device=dev)
+        order, start = _corner_lists(faces, V)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().rtgs_mesh_decimate_quadrics(_p(vertices), _p(faces), V, F, _p(order), _p(start), _p(quadrics),
+                                                               _stream(dev)), "rtgs_mesh_decimate_quadrics")
+        remap = torch.arange(V, dtype=torch.int32, device=dev)
+        while faces.shape[0] > target and rounds < DECIMATE_MAX_ROUNDS:
+            faces, n = _decimate_round(vertices, faces, V, quadrics, remap, target, max_error)
+            rounds += 1
+            collapses += n
+            if n == 0:
+                break
+    out_v, out_f, out_c = _compact(vertices, faces, colors, V, int(faces.shape[0]), None)
+    stats = {"rounds": rounds, "collapses": collapses, "faces_removed": F - int(out_f.shape[0]),
+             "vertices_removed": V - int(out_v.shape[0]), "target_reached": int(out_f.shape[0]) <= target}
+    return out_v, out_f, out_c, stats
+
+
 def clean_mesh(vertices, faces, colors, *, min_component_faces: int = 0, simplify_cell: float = 0.0, origin=None,
-               normals: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor], Dict]:
+               normals: bool = False, decimate_faces: int = 0,
+               decimate_max_error: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor], Dict]:
     """The order meshing.mesh_from_map applies: removal (min_component_faces > 0), simplification (simplify_cell > 0, on the
-    grid anchored at `origin`), normals of the final mesh -> (vertices, faces, colors, normals or None, the removal stats)."""
+    grid anchored at `origin`), decimation (decimate_faces > 0: the target face count), normals of the final mesh ->
+    (vertices, faces, colors, normals or None, the removal stats).  A decimation adds its own stats to them as
+    "decimate_rounds", "decimate_collapses", "decimate_faces_removed", "decimate_vertices_removed" and
+    "decimate_target_reached"."""
     stats: Dict = {}
     if min_component_faces > 0:
         vertices, faces, colors, stats = remove_small_components(vertices, faces, colors, min_component_faces)
     if simplify_cell > 0:
         vertices, faces, colors = simplify_clusters(vertices, faces, colors, simplify_cell, origin)
+    if decimate_faces > 0:
+        vertices, faces, colors, dstats = decimate(vertices, faces, colors, decimate_faces, decimate_max_error)
+        stats = {**stats, **{"decimate_" + k: v for k, v in dstats.items()}}
     nrm = vertex_normals(vertices, faces) if normals else None
     return vertices, faces, colors, nrm, stats

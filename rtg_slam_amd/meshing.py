@@ -444,7 +444,8 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
                   every: int = 1, bounds=None, trunc: Optional[float] = None, max_weight: float = 64, min_weight: float = 1,
                   args=None, device=None, max_bytes: int = MAX_BYTES, volume: str = "dense", min_component_faces: int = 0,
                   simplify_cell: float = 0.0, normals: bool = False, cull_unseen: bool = False,
-                  cull_unseen_tolerance: Optional[float] = None):
+                  cull_unseen_tolerance: Optional[float] = None, decimate: float = 0.0,
+                  decimate_max_error: Optional[float] = None):
     """Fuse a trajectory into a TsdfVolume (volume "dense") or a SparseTsdfVolume ("sparse") and extract its mesh ->
     (vertices, faces, colors, report).
 
@@ -464,6 +465,12 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
     "F_raw", the removal's "components", "components_removed", "faces_removed" and "vertices_removed" (when it ran),
     "simplify_cell", "normals" and "cleanup_s".
 
+    decimate in (0, 1) is the share of the faces to keep: after the removal and the clustering, mesh_ops.decimate collapses
+    half-edges by quadric error down to floor(decimate * F) faces, F counted at that stage; decimate_max_error (metres)
+    bounds the error of every collapse and may stop it above the target.  It counts as clean-up (the keys above, "cleanup_s"
+    includes it), and the report gains, only then, "decimate", "decimate_max_error", "F_before_decimate", "decimate_rounds",
+    "decimate_collapses", "decimate_target_reached" and "decimate_s".
+
     cull_unseen=True removes, after the extraction and before the clean-up, the surface no fused view could see (cull_unseen
     below, at the fused poses, cull_unseen_tolerance metres, default the voxel): the report's V and F are the counts after it
     and it gains "cull_unseen" (the tolerance), "F_unseen_removed", "V_unseen_removed", "cull_render_s" and, as with the
@@ -482,6 +489,11 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
     if simplify_cell != 0 and not simplify_cell > float(voxel):
         raise ValueError(f"rtg_slam_amd.meshing: simplify_cell {simplify_cell:g} m must be larger than the voxel ({float(voxel):g} m); "
                          "a cell that holds one vertex simplifies nothing")
+    decimate = float(decimate)
+    if not 0 <= decimate < 1:
+        raise ValueError(f"rtg_slam_amd.meshing: decimate is the share of faces to keep, 0 (off) <= decimate < 1, got {decimate:g}")
+    if decimate_max_error is not None and not (decimate > 0 and float(decimate_max_error) > 0):
+        raise ValueError("rtg_slam_amd.meshing: decimate_max_error must be > 0 and needs decimate > 0")
     every = max(1, int(every))
     trunc = 4 * float(voxel) if trunc is None else float(trunc)
     if device is None:
@@ -538,15 +550,29 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
                        "cull_unseen": stats["tolerance"],
                        "F_unseen_removed": f_raw - int(faces.shape[0]), "V_unseen_removed": v_raw - int(vertices.shape[0]),
                        "cull_render_s": stats["render_s"]})
-    if min_component_faces > 0 or simplify_cell > 0 or normals:
+    if min_component_faces > 0 or simplify_cell > 0 or normals or decimate > 0:
         from . import mesh_ops
         t0 = time.perf_counter()
-        vertices, faces, colors, nrm, stats = mesh_ops.clean_mesh(
-            vertices, faces, colors, min_component_faces=min_component_faces, simplify_cell=simplify_cell, origin=vol.lo,
-            normals=normals)
+        extra: Dict = {}
+        if decimate > 0:
+            vertices, faces, colors, _, stats = mesh_ops.clean_mesh(
+                vertices, faces, colors, min_component_faces=min_component_faces, simplify_cell=simplify_cell, origin=vol.lo)
+            torch.cuda.synchronize(device)
+            t1 = time.perf_counter()
+            f_before = int(faces.shape[0])
+            vertices, faces, colors, dstats = mesh_ops.decimate(vertices, faces, colors, int(decimate * f_before), decimate_max_error)
+            torch.cuda.synchronize(device)
+            extra = {"decimate": decimate, "decimate_max_error": None if decimate_max_error is None else float(decimate_max_error),
+                     "F_before_decimate": f_before, "decimate_rounds": dstats["rounds"], "decimate_collapses": dstats["collapses"],
+                     "decimate_target_reached": dstats["target_reached"], "decimate_s": time.perf_counter() - t1}
+            nrm = mesh_ops.vertex_normals(vertices, faces) if normals else None
+        else:
+            vertices, faces, colors, nrm, stats = mesh_ops.clean_mesh(
+                vertices, faces, colors, min_component_faces=min_component_faces, simplify_cell=simplify_cell, origin=vol.lo,
+                normals=normals)
         torch.cuda.synchronize(device)
         report.update({"V_raw": v_raw, "F_raw": f_raw, "V": int(vertices.shape[0]), "F": int(faces.shape[0]), **stats,
-                       "simplify_cell": simplify_cell, "normals": normals, "cleanup_s": time.perf_counter() - t0})
+                       "simplify_cell": simplify_cell, "normals": normals, "cleanup_s": time.perf_counter() - t0, **extra})
         if normals:
             return vertices, faces, colors, report, nrm
     return vertices, faces, colors, report

@@ -15,9 +15,16 @@
   * the clean-up leg (key "cleanup"; alone with --cleanup): rtg_slam_amd.mesh_ops on the fused room's mesh at 2 cm and 1 cm -
     vertex_normals, component_labels, remove_small_components (100 faces), compact and simplify_clusters (2.5 voxels), each
     whole call (its torch sorts and scans and the host's reads of the counts included) in blocks of its own, with the counts
-    before and after and the removal's statistics.
+    before and after and the removal's statistics;
+  * the decimation leg (key "decimate"; alone with --decimate): mesh_ops.decimate of the same two meshes to 25 % and to 10 % of
+    their faces - whole calls (every round's kernels, torch sorts and host reads), one call per block after one warm-up call,
+    rounds, collapses per round and milliseconds per round; for quality, the mean and the maximum distance from 1 M points
+    sampled on the decimated mesh to the ORIGINAL mesh's vertices (evaluation's nearest-neighbour kernels; the original's
+    vertices lie at most a cell's diagonal apart, so this is the deviation from the original surface up to that), and beside
+    it the same figures, and the time, for simplify_clusters at the cell (a multiple of a quarter voxel) whose face count
+    comes nearest.
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
-blocks are reported.  python tools/mesh_check.py [--sparse-only | --cleanup] [OUT] [reps = 10] [blocks = 5]"""
+blocks are reported.  python tools/mesh_check.py [--sparse-only | --cleanup | --decimate] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -165,8 +172,63 @@ def cleanup_leg(dev, cam, frames, lo, hi, reps, blocks):
     return res
 
 
+def _deviation(v, f, original_index, n_original, seed=0):
+    """1 M points sampled on the mesh (v, f) -> their distance to the nearest vertex of the original mesh."""
+    from rtg_slam_amd import evaluation as ev, slam_ops as so
+    pts = ev.sample_mesh_points(v, f, 1_000_000, seed, v.device).contiguous()
+    d2, _ = so.knn_query_built(original_index, n_original, pts)
+    d = d2[:, 0].double().sqrt()
+    return {"mean_m": float(d.mean()), "max_m": float(d.max()), "p99_m": float(torch.quantile(d[::10], 0.99))}
+
+
+def decimate_leg(dev, cam, frames, lo, hi, blocks):
+    from rtg_slam_amd import slam_ops as so
+    res = {"timing": "device events around ONE whole mesh_ops.decimate call per block (every round's kernels, torch sorts and "
+                     "scans and host reads of counts), blocks after one warm-up call",
+           "quality": "distance from 1 M points sampled on the result to the nearest vertex of the original mesh"}
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        _fuse_all(vol, frames, cam)
+        entry = {"dims": list(vol.dims), "extract": _timed_extract(vol)}
+        v, f, c = vol.extract_mesh()
+        origin = vol.lo
+        del vol
+        torch.cuda.empty_cache()
+        V, F = int(v.shape[0]), int(f.shape[0])
+        entry.update({"V": V, "F": F})
+        index = so.knn_build_ref(v.contiguous())
+        entry["original_sampled"] = _deviation(v, f, index, V)
+        cells = {}
+        for i in range(36):
+            cell = voxel * (1.25 + 0.25 * i)
+            cells[cell] = int(mesh_ops.simplify_clusters(v, f, c, cell, origin)[1].shape[0])
+        for share in (0.25, 0.10):
+            target = int(share * F)
+            ov, of, oc, stats = mesh_ops.decimate(v, f, c, target)
+            e = {"target_faces": target, "V_after": int(ov.shape[0]), "F_after": int(of.shape[0]), **stats,
+                 "collapses_per_round": round(stats["collapses"] / max(stats["rounds"], 1), 1)}
+            e["call"] = blocks_ms(lambda i: mesh_ops.decimate(v, f, c, target), 1, blocks, warmup=1)
+            e["ms_per_round"] = round(e["call"]["median_ms"] / max(stats["rounds"], 1), 4)
+            e["deviation"] = _deviation(ov, of, index, V)
+            n = mesh_ops.vertex_normals(ov, of)
+            e["zero_normals"] = int((n.abs().sum(1) == 0).sum())
+            cell = min(cells, key=lambda k: abs(cells[k] - int(of.shape[0])))
+            sv, sf, sc = mesh_ops.simplify_clusters(v, f, c, cell, origin)
+            n = mesh_ops.vertex_normals(sv, sf)
+            e["simplify_clusters"] = {"cell": cell, "cell_voxels": round(cell / voxel, 2), "V_after": int(sv.shape[0]),
+                                      "F_after": int(sf.shape[0]), "deviation": _deviation(sv, sf, index, V),
+                                      "zero_normals": int((n.abs().sum(1) == 0).sum()),
+                                      "call": blocks_ms(lambda i: mesh_ops.simplify_clusters(v, f, c, cell, origin), 10, blocks)}
+            entry[f"to_{int(100 * share)}_percent"] = e
+            del ov, of, oc, sv, sf, sc, n
+        res[f"room_voxel_{voxel:g}"] = entry
+        del v, f, c, index
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup")]
+    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate")]
     sparse_only = "--sparse-only" in sys.argv[1:]
     cleanup_only = "--cleanup" in sys.argv[1:]
     out_path = argv[0] if len(argv) > 0 else None
@@ -183,6 +245,9 @@ def main():
     frame_bytes = cam.H * cam.W * 16
     half = (2.5, 1.5, 3.0)
     lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
+    if "--decimate" in sys.argv[1:]:
+        res["decimate"] = decimate_leg(dev, cam, frames, lo, hi, blocks)
+        return _finish(res, out_path)
     if cleanup_only:
         res["cleanup"] = cleanup_leg(dev, cam, frames, lo, hi, reps, blocks)
         return _finish(res, out_path)
