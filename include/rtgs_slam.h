@@ -524,6 +524,55 @@ int rtgs_mesh_render(const float* vertices, int64_t V, const int32_t* faces, int
                      float cx, float cy, const float* w2c12_host, float near, int32_t small_max, void* scratch, float* depth,
                      int32_t* face, void* stream);
 
+/* ---- mesh distance: the exact distance from a point to the nearest triangle of an indexed mesh, with that triangle's index (no
+ * counterpart in the reference; csrc/mesh_distance.hip).  tests/mesh_distance_reference.py restates it in numpy as a brute
+ * force over all faces; the kernels match it bit for bit, whatever the grid.
+ *
+ * vertices [V][3] float32, finite, |coordinate| <= 2^20; faces [F][3] int32, the CALLER guarantees 0 <= faces[i] < V; F >= 1.
+ * The grid is the caller's: origin_host (3 floats on the HOST), cell > 0, dims_host (3 ints on the HOST, each in
+ * 1..RTGS_MESH_DISTANCE_MAX_DIM, their product < 2^31), and vmax = the largest |coordinate| of the vertices.  The CALLER
+ * guarantees that every vertex lies at least half a cell inside the grid's box.  Cell (x, y, z) has the index (z ny + y) nx + x.
+ *   pair_d2(p, face)  float32, one correctly rounded operation per step: the minimum of the three edge values seg(p, s, e) - d = e - s,
+ *                     w = p - s, t = clamp01(w.d / d.d) (0 when d.d is not > 0), q = w - t d, q.q; the ends ordered by vertex
+ *                     index, lower first - and, when det = ab.ab ac.ac - (ab.ac)^2 > 0, of the interior value: s, t the
+ *                     barycentrics by Cramer's rule, s clamped into [0, 1], t into [0, 1 - s], q = (w - s ab) - t ac, q.q.
+ *                     u.v = (ux vx + uy vy) + uz vz; clamp01(NaN) = 0.
+ *   result            d2[i] = the minimum of pair_d2 over ALL faces, face[i] = the lowest face index attaining it; a point with a
+ *                     non-finite coordinate gives (+inf, -1).
+ * rtgs_mesh_distance_count   counts [cells] int32, ZEROED by the caller, += 1 per face registered in the cell (every cell of the
+ *   face's inflated box that its inflated plane crosses).  A box of more than large_max (>= 0) cells is walked by a wave
+ *   through the queue in queue_scratch: rtgs_mesh_distance_queue_bytes(F) bytes whose first 16 the caller ZEROED, 4-byte aligned.
+ * rtgs_mesh_distance_fill    after the caller's exclusive scan start [cells + 1] int32 of counts: entries [start[cells]] int32 are
+ *   written through cursor [cells] int32, ZEROED by the caller; queue_scratch as count left it, same large_max.  The order of a
+ *   cell's entries is not defined.
+ * rtgs_mesh_distance_blocks  occupied uint8: first one flag per block of B^3 cells, [ceil(nx/B) ceil(ny/B) ceil(nz/B)] = [bz][by][bx],
+ *   B = RTGS_MESH_DISTANCE_BLOCK, 1 where a cell of the block has an entry; then one flag per super block of S^3 blocks,
+ *   [ceil(bz/S)][ceil(by/S)][ceil(bx/S)], S = RTGS_MESH_DISTANCE_SUPER, 1 where a block of it is occupied.
+ * rtgs_mesh_distance_query   points [N][3] float32 (anywhere), order: NULL, or a permutation of 0..N-1 (int64) in which the threads
+ *   take the points; d2 [N] float32 and face [N] int32 are written at the points' own rows.  One launch, no host read.
+ * rtgs_mesh_distance_keys    keys [N] int64: the point's cell, clamped into the grid, block-major (0 for a non-finite point).
+ * rtgs_mesh_distance_normals normals [N][3] float32: n = (b - a) x (c - a) of face[i] as rtgs_mesh_vertex_normals forms it,
+ *   divided by l = sqrt((x x + y y) + z z) when l > 0; (0, 0, 0) otherwise and for face[i] < 0.
+ * Return 0 (also, without a launch, for N == 0), -1 on a bad argument, -2 on a launch failure. */
+#define RTGS_MESH_DISTANCE_BLOCK 4
+#define RTGS_MESH_DISTANCE_SUPER 4
+#define RTGS_MESH_DISTANCE_MAX_DIM 65536
+size_t rtgs_mesh_distance_queue_bytes(int64_t F);
+int rtgs_mesh_distance_count(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float* origin_host, float cell,
+                             const int32_t* dims_host, float vmax, int32_t large_max, int32_t* counts, void* queue_scratch, void* stream);
+int rtgs_mesh_distance_fill(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float* origin_host, float cell,
+                            const int32_t* dims_host, float vmax, int32_t large_max, const int32_t* start, int32_t* cursor, int32_t* entries,
+                            void* queue_scratch, void* stream);
+int rtgs_mesh_distance_blocks(const int32_t* start, const float* origin_host, float cell, const int32_t* dims_host, uint8_t* occupied,
+                              void* stream);
+int rtgs_mesh_distance_query(const float* points, int64_t N, const int64_t* order, const float* vertices, int64_t V, const int32_t* faces,
+                             int64_t F, const float* origin_host, float cell, const int32_t* dims_host, float vmax, const int32_t* start,
+                             const int32_t* entries, const uint8_t* occupied, float* d2, int32_t* face, void* stream);
+int rtgs_mesh_distance_keys(const float* points, int64_t N, const float* origin_host, float cell, const int32_t* dims_host, int64_t* keys,
+                            void* stream);
+int rtgs_mesh_distance_normals(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face, int64_t N,
+                               float* normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,15 @@ _SIGNATURES = {
     "rtgs_mesh_render_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "rtgs_mesh_render": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                    _P, C.c_float, C.c_int32, _P, _P, _P, _P]),
+    # mesh distance
+    "rtgs_mesh_distance_queue_bytes": (C.c_size_t, [C.c_int64]),
+    "rtgs_mesh_distance_count": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_float, C.c_int32, _P, _P, _P]),
+    "rtgs_mesh_distance_fill": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_float, C.c_int32, _P, _P, _P, _P, _P]),
+    "rtgs_mesh_distance_blocks": (C.c_int, [_P, _P, C.c_float, _P, _P, _P]),
+    "rtgs_mesh_distance_query": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, _P, _P, _P,
+                                           _P, _P]),
+    "rtgs_mesh_distance_keys": (C.c_int, [_P, C.c_int64, _P, C.c_float, _P, _P, _P]),
+    "rtgs_mesh_distance_normals": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -10,6 +10,8 @@
     evaluate_sequence  metric.py:137-219      every frame of a finished run with the evaluation renderer, the reconstruction
                                               once, per-frame rows and the mean row
     eval_mesh          (no counterpart)       eval_pcd of points sampled on a triangle mesh's surface (rtg_slam_amd.meshing)
+    eval_mesh_surface  (no counterpart)       the same keys from samples of each mesh to the other's SURFACE (exact point-to-
+                                              triangle distances, mesh_ops.MeshDistance), and the normal consistency
     VisibilityCull     (no counterpart)       the part of the GT mesh the evaluated frames saw: per vertex, against the sensor
                                               depth, at the GT poses (include/rtgs_slam.h, "visibility")
     MeshRenderer       (no counterpart)       the depth and face maps of a triangle mesh at a pose (include/rtgs_slam.h, "mesh
@@ -181,6 +183,74 @@ def eval_mesh(vertices, faces, gt_points, dist_thres: Sequence[float] = (0.03,),
     if torch.is_tensor(vertices) and vertices.is_cuda:
         dev = vertices.device
     return eval_pcd(sample_mesh_points(vertices, faces, sample_nums, seed, dev), gt_points, dist_thres, transform, sample_nums)
+
+
+def _surface_side(samples, own_face, own: "MeshDistance", target: "MeshDistance", thr):
+    """One direction of eval_mesh_surface -> float64 [3 + k] on the device: nn_stats of the samples' distances to the target's
+    surface, then the sum of |n_own . n_hit| and the number of samples it runs over."""
+    d2, face, n_hit = target.query(samples, normals=True)
+    n_own = own.face_normals(own_face)
+    dot = ((n_own[:, 0] * n_hit[:, 0] + n_own[:, 1] * n_hit[:, 1]) + n_own[:, 2] * n_hit[:, 2]).abs()      # float32, step by step
+    ok = (n_own != 0).any(1) & (n_hit != 0).any(1)                   # a degenerate face has the normal (0, 0, 0)
+    nc = torch.stack([torch.where(ok, dot, torch.zeros_like(dot)).sum(dtype=torch.float64), ok.sum().to(torch.float64)])
+    return torch.cat([nn_stats(d2[:, None].expand(-1, 3), thr), nc])
+
+
+def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres: Sequence[float] = (0.03,), transform=None,
+                      sample_nums: int = 1_000_000, seed: int = 0, device=None, reports: Optional[Dict] = None) -> Dict[str, float]:
+    """The reconstruction metrics of a triangle mesh against a GT mesh with the SURFACE on the far side of every distance
+    (mesh_ops.MeshDistance), so that no figure carries the sample spacing of the other mesh: accuracy and precision from
+    sample_nums points drawn on the reconstruction (sample_mesh_surface, `seed`, as eval_mesh draws them; moved by `transform`
+    as eval_pcd moves them) to the GT surface, completion and recall from sample_nums points drawn on the GT mesh (`seed`) to
+    the reconstruction's surface (its vertices moved by `transform`).  The keys of eval_pcd, and
+        normal_consistency_acc / _comp   the mean |n_sample_face . n_hit_face| of each direction: float32 unit normals, the
+                                         absolute value because GT meshes are not all wound towards free space, the sum in
+                                         float64; samples whose own or hit face has no area are counted out
+        normal_samples_acc / _comp       the samples they run over
+        normal_consistency               the mean of the two.
+    Meshes are arrays or device tensors.  `reports`, a dict, receives "gt" and "rec": the two MeshDistance.report()s."""
+    from . import mesh_ops, slam_ops as so
+    from .io_formats import sample_mesh_surface
+    if device is None:
+        device = next((t.device for t in (rec_vertices, rec_faces, gt_vertices, gt_faces) if torch.is_tensor(t) and t.is_cuda), None)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    dev = torch.device(device)
+    thres = [float(t) for t in dist_thres]
+    if len(thres) > MAX_THRESHOLDS:
+        raise ValueError(f"rtg_slam_amd.evaluation: at most {MAX_THRESHOLDS} thresholds")
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(to_np(a))).to(device=dev, dtype=dt).contiguous()
+    sides = {}
+    for name, v, f in (("rec", rec_vertices, rec_faces), ("gt", gt_vertices, gt_faces)):
+        pts, own = sample_mesh_surface(to_np(v), to_np(f), int(sample_nums), seed)
+        pts, vt = up(pts, torch.float32), up(v, torch.float32).reshape(-1, 3)
+        if name == "rec" and transform is not None:
+            m = torch.as_tensor(np.asarray(transform, dtype=np.float32))
+            pts, vt = so.transform_map(pts, m).contiguous(), so.transform_map(vt, m).contiguous()
+        sides[name] = (pts, up(own, torch.int32), mesh_ops.MeshDistance(vt, up(f, torch.int64).reshape(-1, 3).to(torch.int32)))
+    thr = torch.tensor(thres, dtype=torch.float64, device=dev)
+    (rp, ro, rmd), (gp, go, gmd) = sides["rec"], sides["gt"]
+    k = len(thres)
+    v = torch.cat([_surface_side(rp, ro, rmd, gmd, thr), _surface_side(gp, go, gmd, rmd, thr)]).cpu().tolist()   # the one host read
+    acc, comp = v[:3 + k], v[3 + k:]
+    Nr, Ng = int(rp.shape[0]), int(gp.shape[0])
+    res = {"accuracy": acc[0] / Nr * 100.0, "completion": comp[0] / Ng * 100.0}
+    Ps = {f"P (< {t})": acc[1 + j] / Nr * 100.0 for j, t in enumerate(thres)}
+    Rs = {f"R (< {t})": comp[1 + j] / Ng * 100.0 for j, t in enumerate(thres)}
+    Fs = {}
+    for t in thres:
+        P, R = Ps[f"P (< {t})"], Rs[f"R (< {t})"]
+        Fs[f"F1 (< {t})"] = 2 * P * R / (P + R) if P + R > 0 else math.nan
+    res.update(Ps)
+    res.update(Rs)
+    res.update(Fs)
+    for name, s in (("acc", acc), ("comp", comp)):
+        res["normal_consistency_" + name] = s[1 + k] / s[2 + k] if s[2 + k] else math.nan
+        res["normal_samples_" + name] = int(s[2 + k])
+    res["normal_consistency"] = 0.5 * (res["normal_consistency_acc"] + res["normal_consistency_comp"])
+    if reports is not None:
+        reports["gt"], reports["rec"] = gmd.report(), rmd.report()
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------------

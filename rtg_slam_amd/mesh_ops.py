@@ -10,16 +10,17 @@ so none of this.
     simplify_clusters         vertex clustering on a grid of `cell` metres: one vertex per occupied cell
     decimate                  quadric-error half-edge collapse to a target face count (csrc/mesh_decimate.hip): vertices are
                               removed, never moved, so corners stay sharp and the result stays manifold
+    MeshDistance              the exact distance from points to the nearest face, and that face (csrc/mesh_distance.hip)
 
 All take an indexed mesh on the device - vertices [V,3] float32, faces [F,3] int32, colours [V,3] float32 - from
 TsdfVolume.extract_mesh, SparseTsdfVolume.extract_mesh or another of these.  Every result is unique and independent of
-thread order: two runs are bit-equal, and tests/mesh_ops_reference.py (decimate: tests/mesh_decimate_reference.py) restates
-each in numpy, matched bit for bit.  The kernels do the float work and the per-element decisions; the scans and stable
+thread order: two runs are bit-equal, and tests/mesh_ops_reference.py (decimate: tests/mesh_decimate_reference.py, MeshDistance:
+tests/mesh_distance_reference.py) restates each in numpy, matched bit for bit.  The kernels do the float work and the per-element decisions; the scans and stable
 sorts between them are torch's.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -31,6 +32,14 @@ DECIMATE_MIN_VALENCE = 4             # RTGS_MESH_DECIMATE_MIN_VALENCE
 DECIMATE_MAX_VALENCE = 32            # RTGS_MESH_DECIMATE_MAX_VALENCE
 DECIMATE_MAX_ROUNDS = 1000           # RTGS_MESH_DECIMATE_MAX_ROUNDS
 _DECIMATE_HASH = 2654435761          # h(u) = u * this mod 2^32: the tie-break between equal costs
+DISTANCE_BLOCK = 4                   # RTGS_MESH_DISTANCE_BLOCK
+DISTANCE_SUPER = 4                   # RTGS_MESH_DISTANCE_SUPER
+DISTANCE_MAX_DIM = 65536             # RTGS_MESH_DISTANCE_MAX_DIM: cells per axis
+DISTANCE_MAX_COORD = float(2 ** 20)  # the largest |coordinate| of a vertex pair_d2 is finite for
+DISTANCE_LARGE_MAX = 64              # cell boxes of more cells go to the wave path of csrc/mesh_distance.hip
+DISTANCE_CELL_EDGES = 2.0            # the default cell in mean edge lengths ("mesh distance", has the measurement)
+DISTANCE_MIN_CELL_SHARE = 512        # ... but not below the mesh's extent / this
+DISTANCE_SORT = True                 # sort the queries by cell first (same section: 6 to 14 times faster)
 
 
 def _p(t):
@@ -398,3 +407,164 @@ def clean_mesh(vertices, faces, colors, *, min_component_faces: int = 0, simplif
         stats = {**stats, **{"decimate_" + k: v for k, v in dstats.items()}}
     nrm = vertex_normals(vertices, faces) if normals else None
     return vertices, faces, colors, nrm, stats
+
+
+class MeshDistance:
+    """The exact distance from points to the surface of an indexed triangle mesh (include/rtgs_slam.h, "mesh distance"):
+
+        md = MeshDistance(vertices, faces)
+        d2, face = md.query(points)                      # [N] float32 squared distances, [N] int32 nearest faces
+        d2, face, normals = md.query(points, normals=True)
+
+    d2[i] is the minimum over ALL faces of the float32 point-to-triangle chain pair_d2, face[i] the lowest face index that
+    attains it, (inf, -1) for a point with a non-finite coordinate: bit for bit the brute force of
+    tests/mesh_distance_reference.py, whatever `cell` is.  The index behind it is a uniform grid of `cell` metres over the
+    mesh's box (default: DISTANCE_CELL_EDGES mean edge lengths, at least the extent / DISTANCE_MIN_CELL_SHARE) with the
+    faces of every cell, and two levels of 4^3 blocks above it; it is built here, once, and refused with a ValueError that names the
+    size when an axis would take more than DISTANCE_MAX_DIM cells, the grid 2^31 or more, or the cell table and the entries
+    more than max_bytes.  The face indices are checked against V and F == 0 raises ValueError, here, once.  `sort`: take the
+    queries in the order of their cells (a torch sort; the results land at the points' own rows); `large_max`: the largest
+    cell box one thread registers.  Both change the time only."""
+
+    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor, cell: Optional[float] = None, max_bytes: int = 4 << 30,
+                 large_max: Optional[int] = None, sort: Optional[bool] = None):
+        self.vertices, self.faces, _, V, F = _check(vertices, faces)
+        if F == 0:
+            raise ValueError("rtg_slam_amd.mesh_ops: MeshDistance needs at least one face")
+        if F >= 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.mesh_ops: {F} faces do not fit the int32 face index")
+        dev = self.device = self.vertices.device
+        self.sort = DISTANCE_SORT if sort is None else bool(sort)
+        self.large_max = DISTANCE_LARGE_MAX if large_max is None else int(large_max)
+        if not 0 <= self.large_max < 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.mesh_ops: large_max must lie in 0..2^31 - 1, got {large_max}")
+        # one host read: the box, the largest |coordinate|, the mean edge length
+        used = self.vertices[self.faces.reshape(-1).long()].reshape(F, 3, 3)
+        edge = (used - used.roll(-1, 1)).double().norm(dim=2).mean()
+        box = torch.cat([used.amin((0, 1)).double(), used.amax((0, 1)).double(), used.abs().amax().double().reshape(1),
+                         edge.reshape(1)]).cpu().numpy()
+        lo, hi, vmax, mean_edge = box[:3], box[3:6], float(box[6]), float(box[7])
+        if not vmax <= DISTANCE_MAX_COORD:                                        # NaN fails too
+            raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance needs finite vertices with |coordinate| <= 2^20, found {vmax}")
+        extent = float((hi - lo).max())
+        if cell is None:
+            cell = max(DISTANCE_CELL_EDGES * mean_edge, extent / DISTANCE_MIN_CELL_SHARE)
+            cell = cell if cell > 0 else 1.0                                      # a mesh that is one point
+        cell = float(np.float32(cell))
+        if not 0 < cell < float("inf"):
+            raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance needs a finite cell > 0, got {cell}")
+        origin = (lo - 0.75 * cell).astype(np.float32)                            # the kernels need half a cell of room
+        dims = np.floor((hi - origin.astype(np.float64)) / cell).astype(np.int64) + 2
+        size = f"{int(dims[0])} x {int(dims[1])} x {int(dims[2])} cells of {cell:g} m"
+        if (dims > DISTANCE_MAX_DIM).any():
+            raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance would need {size}, more than {DISTANCE_MAX_DIM} on an axis; use a larger cell")
+        if not ((lo - origin >= 0.5 * cell).all() and ((hi - origin) / cell + 0.5 <= dims).all()):
+            raise ValueError(f"rtg_slam_amd.mesh_ops: a cell of {cell:g} m is below what float32 resolves at coordinates of {vmax:g}")
+        cells = int(dims[0]) * int(dims[1]) * int(dims[2])
+        bdims = (dims + DISTANCE_BLOCK - 1) // DISTANCE_BLOCK
+        nblocks = int(np.prod(bdims)) + int(np.prod((bdims + DISTANCE_SUPER - 1) // DISTANCE_SUPER))      # and the super blocks
+        table = 4 * (cells + 1) + nblocks
+        if cells >= 2 ** 31:
+            raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance would need {size} = {cells} cells, the limit is 2^31 - 1; use a larger cell")
+        if table > max_bytes:
+            raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance would need {size}: a cell table of {table} bytes "
+                             f"({table / 2 ** 30:.2f} GiB), more than max_bytes = {int(max_bytes)}; use a larger cell")
+        self.cell, self.dims, self.vmax = cell, tuple(int(d) for d in dims), float(np.float32(vmax))
+        self._origin = (C.c_float * 3)(*origin.tolist())
+        self._dims = (C.c_int32 * 3)(*self.dims)
+        self.origin = tuple(float(x) for x in origin)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            counts = torch.zeros(cells, dtype=torch.int32, device=dev)
+            self._queue = torch.zeros((lib.rtgs_mesh_distance_queue_bytes(F) + 3) // 4, dtype=torch.int32, device=dev)
+            _lib.check(lib.rtgs_mesh_distance_count(_p(self.vertices), V, _p(self.faces), F, self._origin, cell, self._dims, self.vmax,
+                                                    self.large_max, _p(counts), _p(self._queue), _stream(dev)), "rtgs_mesh_distance_count")
+            incl = torch.cumsum(counts, 0, dtype=torch.int64)
+            entries = int(incl[-1])                                               # the host read of the build
+            total = table + 4 * entries
+            if entries >= 2 ** 31 or total > max_bytes:
+                raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance would need {size} with {entries} entries: {total} bytes "
+                                 f"({total / 2 ** 30:.2f} GiB), more than max_bytes = {int(max_bytes)} (or 2^31 entries); use a larger cell")
+            self._start = torch.zeros(cells + 1, dtype=torch.int32, device=dev)
+            self._start[1:] = incl
+            del incl
+            counts.zero_()                                                        # the cursors of the fill
+            self._entries = torch.zeros(max(entries, 1), dtype=torch.int32, device=dev)       # every slot is a valid face index
+            self._occupied = torch.empty(nblocks, dtype=torch.uint8, device=dev)
+            _lib.check(lib.rtgs_mesh_distance_fill(_p(self.vertices), V, _p(self.faces), F, self._origin, cell, self._dims, self.vmax,
+                                                   self.large_max, _p(self._start), _p(counts), _p(self._entries), _p(self._queue),
+                                                   _stream(dev)), "rtgs_mesh_distance_fill")
+            _lib.check(lib.rtgs_mesh_distance_blocks(_p(self._start), self._origin, cell, self._dims, _p(self._occupied), _stream(dev)),
+                       "rtgs_mesh_distance_blocks")
+            b.record()
+        self._build = (a, b)
+        self.entries, self.bytes = entries, total
+        self.queries = 0
+        self._events: List = []
+        self._seconds = 0.0
+
+    def _points(self, points):
+        if not torch.is_tensor(points) or not points.is_cuda:
+            raise RuntimeError("rtg_slam_amd.mesh_ops: tensors must live on a HIP device; this build has no CPU path.")
+        if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+            raise ValueError("rtg_slam_amd.mesh_ops: points must be [N,3] float32")
+        if points.device != self.device:
+            raise ValueError("rtg_slam_amd.mesh_ops: the points and the mesh live on different devices")
+        return points.detach().contiguous()
+
+    def query(self, points: torch.Tensor, normals: bool = False):
+        """-> (d2 [N] float32, face [N] int32), with normals=True also the unit normals [N,3] float32 of the hit faces
+        (face_normals): new tensors, no synchronisation.  points [N,3] float32 on the mesh's device, anywhere in space."""
+        points = self._points(points)
+        dev, lib = self.device, _lib.load()
+        N, V, F = int(points.shape[0]), int(self.vertices.shape[0]), int(self.faces.shape[0])
+        d2 = torch.empty(N, dtype=torch.float32, device=dev)
+        face = torch.empty(N, dtype=torch.int32, device=dev)
+        if N:
+            with torch.cuda.device(dev):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                order = None
+                if self.sort:
+                    keys = torch.empty(N, dtype=torch.int64, device=dev)
+                    _lib.check(lib.rtgs_mesh_distance_keys(_p(points), N, self._origin, self.cell, self._dims, _p(keys), _stream(dev)),
+                               "rtgs_mesh_distance_keys")
+                    order = torch.sort(keys).indices.contiguous()
+                _lib.check(lib.rtgs_mesh_distance_query(_p(points), N, _p(order), _p(self.vertices), V, _p(self.faces), F, self._origin,
+                                                        self.cell, self._dims, self.vmax, _p(self._start), _p(self._entries),
+                                                        _p(self._occupied), _p(d2), _p(face), _stream(dev)), "rtgs_mesh_distance_query")
+                b.record()
+            self._events.append((a, b))
+            self.queries += 1
+        if not normals:
+            return d2, face
+        return d2, face, self.face_normals(face)
+
+    def face_normals(self, face: torch.Tensor) -> torch.Tensor:
+        """-> [N,3] float32: the unit normal (b - a) x (c - a) / l of face[i] ([N] int32 on the device), float32 in
+        vertex_normals' order; (0, 0, 0) for a face without area and for face[i] < 0."""
+        if not torch.is_tensor(face) or not face.is_cuda:
+            raise RuntimeError("rtg_slam_amd.mesh_ops: tensors must live on a HIP device; this build has no CPU path.")
+        if face.dim() != 1 or face.dtype != torch.int32 or face.device != self.device:
+            raise ValueError("rtg_slam_amd.mesh_ops: face must be [N] int32 on the mesh's device")
+        face = face.detach().contiguous()
+        N = int(face.shape[0])
+        out = torch.empty(N, 3, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().rtgs_mesh_distance_normals(_p(self.vertices), int(self.vertices.shape[0]), _p(self.faces),
+                                                              int(self.faces.shape[0]), _p(face), N, _p(out), _stream(self.device)),
+                       "rtgs_mesh_distance_normals")
+        return out
+
+    def report(self) -> Dict:
+        """The grid and the device time of the build and of the queries so far (events; synchronises)."""
+        for a, b in self._events:
+            b.synchronize()
+            self._seconds += a.elapsed_time(b) * 1e-3
+        self._events = []
+        self._build[1].synchronize()
+        return {"cell": self.cell, "dims": list(self.dims), "cells": self.dims[0] * self.dims[1] * self.dims[2], "entries": self.entries,
+                "bytes": self.bytes, "large_faces": int(self._queue[0]), "large_max": self.large_max, "sort": self.sort,
+                "build_s": self._build[0].elapsed_time(self._build[1]) * 1e-3, "queries": self.queries, "query_s": self._seconds}

@@ -22,9 +22,17 @@
     sampled on the decimated mesh to the ORIGINAL mesh's vertices (evaluation's nearest-neighbour kernels; the original's
     vertices lie at most a cell's diagonal apart, so this is the deviation from the original surface up to that), and beside
     it the same figures, and the time, for simplify_clusters at the cell (a multiple of a quarter voxel) whose face count
-    comes nearest.
+    comes nearest;
+  * the distance leg (key "distance"; alone with --distance): mesh_ops.MeshDistance on the same two meshes - the build (count, scan,
+    fill, blocks and its one host read, by the events of MeshDistance.report()) and the query of 1 M points (a) sampled on the mesh
+    itself, (b) sampled on its decimation to 25 %, (c) uniform in the padded box - the far case -, each at 1, 2 and 4 mean
+    edge lengths as the cell, with and without the query sort, and beside them knn_query_built of the same points against the
+    mesh's vertices, the thing it replaces; then the quality columns of the decimation table with this ruler, two-sided: the
+    result's samples to the original SURFACE and the original's samples to the result's surface, mean and maximum, for
+    decimate to 25 % and 10 % and the simplify_clusters rows beside them.  A query that takes long is timed with fewer calls
+    per block (reps_per_block says how many).
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
-blocks are reported.  python tools/mesh_check.py [--sparse-only | --cleanup | --decimate] [OUT] [reps = 10] [blocks = 5]"""
+blocks are reported.  python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -227,8 +235,99 @@ def decimate_leg(dev, cam, frames, lo, hi, blocks):
     return res
 
 
+def _adaptive_ms(fn, reps, blocks):
+    """blocks_ms, with fewer calls per block when one call is slow: about half a second of calls per block."""
+    fn(0)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn(0)
+    b.record()
+    b.synchronize()
+    first = a.elapsed_time(b)
+    reps = max(1, min(reps, int(500.0 / max(first, 1e-3))))
+    return blocks_ms(fn, reps, blocks if first < 1000.0 else 2, warmup=0)
+
+
+def _surface_deviation(md, pts):
+    d = md.query(pts)[0].double().sqrt()
+    return {"mean_m": float(d.mean()), "max_m": float(d.max())}
+
+
+def distance_leg(dev, cam, frames, lo, hi, reps, blocks):
+    from rtg_slam_amd import evaluation as ev, slam_ops as so
+    res = {"timing": "device events; the build is MeshDistance's own pair of events around count, scan, fill and blocks (one host "
+                     "read inside), the median of `blocks` builds after one; a query is one whole md.query call of 1 M points "
+                     "(with sort: the key kernel and torch's sort included), reps calls per block, fewer when a call is slow",
+           "points": {"self": "1 M samples of the mesh itself", "decimated": "1 M samples of its decimation to 25 %",
+                      "far": "1 M points uniform in the padded box"}}
+    n = 1_000_000
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        _fuse_all(vol, frames, cam)
+        v, f, c = vol.extract_mesh()
+        origin = vol.lo
+        del vol
+        torch.cuda.empty_cache()
+        V, F = int(v.shape[0]), int(f.shape[0])
+        tri = v[f.reshape(-1).long()].reshape(F, 3, 3)
+        mean_edge = float((tri - tri.roll(-1, 1)).double().norm(dim=2).mean())
+        del tri
+        entry = {"V": V, "F": F, "mean_edge_m": mean_edge}
+        dv, df, dc, _ = mesh_ops.decimate(v, f, c, int(0.25 * F))
+        gen = torch.Generator().manual_seed(0)
+        box_lo, box_hi = torch.tensor(lo), torch.tensor(hi)
+        sets = {"self": ev.sample_mesh_points(v, f, n, 0, dev).contiguous(), "decimated": ev.sample_mesh_points(dv, df, n, 0, dev).contiguous(),
+                "far": (box_lo + (box_hi - box_lo) * torch.rand(n, 3, generator=gen)).to(dev).contiguous()}
+        index = so.knn_build_ref(v.contiguous())
+        entry["knn_query_built_vertices"] = {k: _adaptive_ms(lambda i, p=p: so.knn_query_built(index, V, p), reps, blocks) for k, p in sets.items()}
+        for mult in (1, 2, 4):
+            e = {"cell": mult * mean_edge}
+            try:
+                builds = [mesh_ops.MeshDistance(v, f, cell=mult * mean_edge).report()["build_s"] for _ in range(blocks + 1)][1:]
+            except ValueError as err:
+                e["refused"] = str(err)
+                entry[f"cell_{mult}_edges"] = e
+                continue
+            print(f"distance: voxel {voxel:g}, cell {mult} edges: built", file=sys.stderr, flush=True)
+            e["build"] = {"median_ms": round(1e3 * float(np.median(builds)), 4), "min_ms": round(1e3 * min(builds), 4),
+                          "max_ms": round(1e3 * max(builds), 4), "blocks": blocks}
+            for sort in (False, True):
+                md = mesh_ops.MeshDistance(v, f, cell=mult * mean_edge, sort=sort)
+                if not sort:
+                    e.update({k: md.report()[k] for k in ("dims", "cells", "entries", "bytes", "large_faces")})
+                e["query_sorted" if sort else "query"] = {k: _adaptive_ms(lambda i, p=p: md.query(p), reps, blocks) for k, p in sets.items()}
+                del md
+            entry[f"cell_{mult}_edges"] = e
+        print(f"distance: voxel {voxel:g}: queries timed", file=sys.stderr, flush=True)
+        # the decimation table's quality columns with this ruler, two-sided
+        md = mesh_ops.MeshDistance(v, f)
+        entry["default_cell"] = md.report()["cell"]
+        entry["original_to_itself"] = _surface_deviation(md, sets["self"])
+        cells = {}
+        for i in range(36):
+            cell = voxel * (1.25 + 0.25 * i)
+            cells[cell] = int(mesh_ops.simplify_clusters(v, f, c, cell, origin)[1].shape[0])
+        for share in (0.25, 0.10):
+            ov, of, oc, _ = mesh_ops.decimate(v, f, c, int(share * F))
+            cell = min(cells, key=lambda k: abs(cells[k] - int(of.shape[0])))
+            sv, sf, sc = mesh_ops.simplify_clusters(v, f, c, cell, origin)
+            row = {}
+            for name, (rv, rf) in (("decimate", (ov, of)), ("simplify_clusters", (sv, sf))):
+                row[name] = {"F_after": int(rf.shape[0]),
+                             "result_to_original": _surface_deviation(md, ev.sample_mesh_points(rv, rf, n, 0, dev).contiguous()),
+                             "original_to_result": _surface_deviation(mesh_ops.MeshDistance(rv, rf), sets["self"])}
+            row["simplify_clusters"]["cell"] = cell
+            entry[f"to_{int(100 * share)}_percent"] = row
+            del ov, of, oc, sv, sf, sc
+        res[f"room_voxel_{voxel:g}"] = entry
+        del v, f, c, dv, df, dc, md, index, sets
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate")]
+    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance")]
     sparse_only = "--sparse-only" in sys.argv[1:]
     cleanup_only = "--cleanup" in sys.argv[1:]
     out_path = argv[0] if len(argv) > 0 else None
@@ -245,6 +344,9 @@ def main():
     frame_bytes = cam.H * cam.W * 16
     half = (2.5, 1.5, 3.0)
     lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
+    if "--distance" in sys.argv[1:]:
+        res["distance"] = distance_leg(dev, cam, frames, lo, hi, reps, blocks)
+        return _finish(res, out_path)
     if "--decimate" in sys.argv[1:]:
         res["decimate"] = decimate_leg(dev, cam, frames, lo, hi, blocks)
         return _finish(res, out_path)
