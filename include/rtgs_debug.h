@@ -71,6 +71,16 @@ void rtgs_raster_set_bwd_walk_ctx(rtgs_ctx* ctx, int mode);
  * (bin_place_kernel) instead of count + scan + scatter.  Outputs are bit-identical either way (the tile sort's order is
  * total); the switch exists for A-B runs and tests. */
 void rtgs_raster_set_onepass_ctx(rtgs_ctx* ctx, int on);
+/* Near-slice forward: the blend's workgroup sorts its tile's list itself (default on, RTGS_FWD_SORT=0 at load time turns it
+ * off: the sort launches in front of the blend, as before).  Lists of up to 1 024 entries are sorted in the blend's LDS
+ * (bitonic up to 256, LSD radix above); lists of 1 025 .. 3 072 entries keep one sort launch ahead of the blend; longer ones
+ * leave their tile to pass 2 either way.  The order is total, so the lists - and every output - are the same either way; the
+ * switch exists for A-B runs and tests, and forgets the speculative plan.
+ * rtgs_raster_fused_sort_stats_ctx: out18 = six classes x (tiles, shortest list, longest list) of the last near-slice blend that
+ * ran fused WITH work counters set (rtgs_raster_set_counters_ctx; the product kernel keeps no such words) - empty, single,
+ * bitonic, fused radix, separate launch, left to pass 2.  Waits for the device. */
+void rtgs_raster_set_fused_sort_ctx(rtgs_ctx* ctx, int on);
+int rtgs_raster_fused_sort_stats_ctx(rtgs_ctx* ctx, int64_t* out18);
 /* Timing decompositions of the entry-per-lane backward walk (tools only): bits 0..2 switch parts of the kernel OFF (1 walk,
  * 2 depth partials, 4 stores) - results are then wrong by construction, so the bits are never read from the environment and a
  * tool that sets them clears them again.  PROCESS-WIDE. */

@@ -3,6 +3,7 @@
 #include "../../include/rtgs_raster.h"
 #include "../../include/rtgs_debug.h"
 #include "raster_common.h"
+#include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -24,7 +25,8 @@ void set_bwd_debug(int bits);
 void set_bwd_stamps(void* dev);
 void launch_blend_fwd(const RasterParams&, const uint2*, const uint32_t*, const Splat*, float*, float*, int32_t*,
                       int32_t*, float*, float*, float*, uint32_t*, unsigned long long*, SlicePass, uint32_t*, uint32_t*, uint32_t*, int, uint32_t*,
-                      TileCache, uint32_t, hipStream_t);
+                      TileCache, uint32_t, hipStream_t, FusedSort fs = FusedSort{nullptr, nullptr, nullptr, nullptr, nullptr});
+bool blend_fwd_fuses_sort();
 void launch_blend_bwd(const RasterParams&, const uint2*, const uint32_t*, const Splat*, const float*, const float*,
                       const uint32_t*, const int32_t*, const float*, const float*, const uint32_t*, uint32_t*,
                       const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, int, uint32_t, uint32_t, hipStream_t);
@@ -67,6 +69,8 @@ void launch_slice_hist(int, const uint8_t*, const uint32_t*, const int32_t*, uin
 void launch_bin_tilesort(int, uint32_t, const uint2*, const unsigned long long*, uint32_t*, const uint32_t*, hipStream_t,
                          const uint32_t* seg_count = nullptr, uint32_t seg = 0, uint2* ranges_out = nullptr,
                          const BinFinish* finish = nullptr);
+void launch_bin_tilesort_long(int, const uint2*, const unsigned long long*, uint32_t*, const uint32_t*, hipStream_t,
+                              const uint32_t*, uint32_t);
 void launch_bin_place(const RasterParams&, const Splat*, const int32_t*, const int32_t*, uint32_t*, unsigned long long*, uint32_t,
                       uint32_t*, SliceSel, SliceList, size_t, hipStream_t);
 
@@ -87,6 +91,12 @@ struct rtgs_ctx {
   unsigned long long* counters = nullptr;
   uint32_t last_listed = 0;         // Gaussians the last verified speculative forward listed for binning
   bool onepass = true;              // one-pass placement into per-tile segments where the layout provides them
+  // Near slice: blend_fwd sorts each tile's list itself (lists of up to FSORT_CAP entries; RTGS_FWD_SORT=0: the sort
+  // launches in front of it, as before).  With work counters set, the blend also leaves one word per tile - the class
+  // its list took and its length - in `fsort_cls` (rtgs_raster_fused_sort_stats_ctx reduces them).
+  bool fused_sort = true;
+  uint32_t* fsort_cls = nullptr;    // device, [fsort_cap] words; 0xffffffff = the tile's workgroup did not get that far
+  int32_t fsort_cap = 0, fsort_tiles = 0;
   bool prof = false;                // optional per-stage HIP-event timing (bench.py's roofline leg)
   bool force_sort_path = false;     // testing aid: take the global radix-sort binning path
   int bwd_walk = 0;                 // 0 / 3 = MFMA walk (default); 1 = strip walk everywhere; 2 = row-granular walk everywhere; 4 = per-tile choice between those two
@@ -176,6 +186,7 @@ static rtgs_ctx* default_ctx() {
     if (const char* e = getenv("RTGS_NEAR_SLICE_BUDGET")) { const int b = atoi(e); if (b > 0) n->slice_budget = b; }
     if (const char* e = getenv("RTGS_SPECULATE")) n->speculation = atoi(e) != 0;
     if (const char* e = getenv("RTGS_BIN_ONEPASS")) n->onepass = atoi(e) != 0;
+    if (const char* e = getenv("RTGS_FWD_SORT")) n->fused_sort = atoi(e) != 0;
     if (const char* e = getenv("RTGS_PLAIN_ONEPASS")) n->plain_onepass = atoi(e) != 0;
     if (const char* e = getenv("RTGS_BWD_WALK")) { const int m = atoi(e); n->bwd_walk = (m >= 1 && m <= 4) ? m : 0; }
     if (const char* e = getenv("RTGS_CULL_CACHE")) n->cull.enabled = atoi(e) != 0;
@@ -396,7 +407,7 @@ const char* rtgs_version(void) { return "rtgs-hip 0.2.0 (gfx950)"; }
 
 rtgs_ctx* rtgs_ctx_create(void) {
   rtgs_ctx* c = new (std::nothrow) rtgs_ctx();
-  if (c) { c->slice_mode = default_ctx()->slice_mode; c->slice_budget = default_ctx()->slice_budget; c->bwd_walk = default_ctx()->bwd_walk; c->onepass = default_ctx()->onepass; c->speculation = default_ctx()->speculation; c->plain_onepass = default_ctx()->plain_onepass; c->cull.enabled = default_ctx()->cull.enabled; c->cull.check = default_ctx()->cull.check; }
+  if (c) { c->slice_mode = default_ctx()->slice_mode; c->slice_budget = default_ctx()->slice_budget; c->bwd_walk = default_ctx()->bwd_walk; c->onepass = default_ctx()->onepass; c->fused_sort = default_ctx()->fused_sort; c->speculation = default_ctx()->speculation; c->plain_onepass = default_ctx()->plain_onepass; c->cull.enabled = default_ctx()->cull.enabled; c->cull.check = default_ctx()->cull.check; }
   return c;
 }
 void rtgs_ctx_destroy(rtgs_ctx* c) {
@@ -405,6 +416,7 @@ void rtgs_ctx_destroy(rtgs_ctx* c) {
   if (c->info_host) (void)hipHostFree(c->info_host);
   if (c->cull.scratch) (void)hipFree(c->cull.scratch);
   if (c->cull.mismatches) (void)hipFree(c->cull.mismatches);
+  if (c->fsort_cls) (void)hipFree(c->fsort_cls);
   delete c;
 }
 
@@ -508,6 +520,33 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
   uint32_t longest = 0;
   // one-pass placement of the near slice's instances into per-tile segments (RTGS_BIN_ONEPASS=0: count / scan / scatter)
   const uint32_t seg1 = c->onepass ? (uint32_t)G.slice_seg : 0u;
+  // The near slice's tile lists, after their placement into bucket1: sorted by the sort launches into list1, or - fused -
+  // by the blend's own workgroups (fs1 tells it where the keys are); then only the size class that does not fit the
+  // blend's LDS keeps its launch.  (That launch is unconditional: a slice whose longest list fits the blend still pays it.)
+  FusedSort fs1{nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto sort_slice_lists = [&]() -> int {
+    const unsigned long long* bucket1 = (const unsigned long long*)(geom + G.bucket1);
+    const uint32_t* cnt = seg1 ? tile_count1 : nullptr;
+    if (!(c->fused_sort && blend_fwd_fuses_sort())) {
+      launch_bin_tilesort(ntiles, (uint32_t)SLICE_MAX_LIST, ranges1, bucket1, list1, nullptr, st, cnt, seg1, seg1 ? ranges1 : nullptr);
+      return RTGS_OK;
+    }
+    launch_bin_tilesort_long(ntiles, ranges1, bucket1, list1, nullptr, st, cnt, seg1);
+    uint32_t* cls = nullptr;
+    if (c->counters) {
+      if (c->fsort_cap < ntiles) {
+        if (c->fsort_cls) (void)hipFree(c->fsort_cls);
+        c->fsort_cls = nullptr; c->fsort_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->fsort_cls, (size_t)ntiles * sizeof(uint32_t)));
+        c->fsort_cap = ntiles;
+      }
+      HIP_TRY(hipMemsetAsync(c->fsort_cls, 0xff, (size_t)ntiles * sizeof(uint32_t), st));
+      c->fsort_tiles = ntiles;
+      cls = c->fsort_cls;
+    }
+    fs1 = FusedSort{bucket1, cnt, seg1 ? ranges1 : nullptr, list1, cls};
+    return RTGS_OK;
+  };
   // gradient slots of the backward (BwdInfo): gbase = exclusive scan of the rect areas, into `offsets`
   const bool want_bwd = !(flags & RTGS_FWD_NO_BACKWARD);
   uint32_t slots = 0;
@@ -655,8 +694,7 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
         if (seg1) {       // one pass: no count, no scan (tile_count1 was cleared by the cull pass; the sort writes ranges1)
           launch_bin_place(p, splats, radii, tile_mask, tile_count1, (unsigned long long*)(geom + G.bucket1), seg1, nullptr,
                            sel1, work, G.slice_max_list, st);
-          launch_bin_tilesort(ntiles, (uint32_t)SLICE_MAX_LIST, ranges1, (const unsigned long long*)(geom + G.bucket1), list1,
-                              nullptr, st, tile_count1, seg1, ranges1);
+          if ((rc = sort_slice_lists()) != RTGS_OK) return rc;
         } else {
         if (launch_bin_count(p, splats, radii, tile_mask, tile_count1, (uint16_t*)(geom + G.block_counts1), sel1, work,
                              G.slice_max_list, st) != 0)
@@ -666,13 +704,12 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
         launch_bin_scatter(p, splats, radii, tile_mask, (const uint16_t*)(geom + G.block_counts1),
                            (uint32_t*)(geom + G.cursor1), (unsigned long long*)(geom + G.bucket1), sel1, work,
                            G.slice_max_list, st);
-        launch_bin_tilesort(ntiles, (uint32_t)SLICE_MAX_LIST, ranges1, (const unsigned long long*)(geom + G.bucket1), list1,
-                            nullptr, st);
+        if ((rc = sort_slice_lists()) != RTGS_OK) return rc;
         }
         prof_mark(c, EV_SL_BIN, st);
         const SlicePass pass1{1, tile_mask, mask2, ranges1_bwd, ranges};
         launch_blend_fwd(p, ranges1, list1, splats, out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T,
-                         n_contrib, c->counters, pass1, tile_mode, depth_pos, tile_last, fwd_walk, aux_zero, tcache, seg1, st);
+                         n_contrib, c->counters, pass1, tile_mode, depth_pos, tile_last, fwd_walk, aux_zero, tcache, seg1, st, fs1);
         prof_mark(c, EV_SL_BLEND, st);      // the bracket holds the blend alone (bench.py's roofline divides by it)
         launch_slice_publish(ntiles, tile_mask, mask2, info + 2, slice_ctr, info_host, c->seq, fail, st, seg1 ? tile_count1 : nullptr);
         prof_mark(c, EV_BLEND0, st); prof_mark(c, EV_BLEND, st);
@@ -830,8 +867,7 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
       if (seg1) {
         launch_bin_place(p, splats, radii, tile_mask, tile_count1, (unsigned long long*)(geom + G.bucket1), seg1, nullptr,
                          sel1, work, G.slice_max_list, st);
-        launch_bin_tilesort(ntiles, (uint32_t)SLICE_MAX_LIST, ranges1, (const unsigned long long*)(geom + G.bucket1), list1,
-                            nullptr, st, tile_count1, seg1, ranges1);
+        if ((rc = sort_slice_lists()) != RTGS_OK) return rc;
       } else {
       if (launch_bin_count(p, splats, radii, tile_mask, tile_count1, (uint16_t*)(geom + G.block_counts1), sel1, work,
                            G.slice_max_list, st) != 0)
@@ -841,15 +877,14 @@ int rtgs_raster_forward_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_
       launch_bin_scatter(p, splats, radii, tile_mask, (const uint16_t*)(geom + G.block_counts1),
                          (uint32_t*)(geom + G.cursor1), (unsigned long long*)(geom + G.bucket1), sel1, work,
                          G.slice_max_list, st);
-      launch_bin_tilesort(ntiles, (uint32_t)SLICE_MAX_LIST, ranges1, (const unsigned long long*)(geom + G.bucket1), list1,
-                          nullptr, st);
+      if ((rc = sort_slice_lists()) != RTGS_OK) return rc;
       }
       DBG(s, st);
       prof_mark(c, EV_SL_BIN, st);
       if (++c->seq == 0u) c->seq = 1u;
       const SlicePass pass1{1, tile_mask, mask2, ranges1_bwd, ranges};
       launch_blend_fwd(p, ranges1, list1, splats, out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T,
-                       n_contrib, c->counters, pass1, tile_mode, depth_pos, tile_last, fwd_walk, aux_zero, tcache, seg1, st);
+                       n_contrib, c->counters, pass1, tile_mode, depth_pos, tile_last, fwd_walk, aux_zero, tcache, seg1, st, fs1);
       prof_mark(c, EV_SL_BLEND, st);
       launch_slice_publish(ntiles, tile_mask, mask2, info + 2, slice_ctr, info_host, c->seq, nullptr, st, seg1 ? tile_count1 : nullptr);
       DBG(s, st);
@@ -1228,6 +1263,26 @@ void rtgs_raster_set_bwd_debug(int bits) { rtgs::set_bwd_debug(bits); }
 void rtgs_raster_set_bwd_stamps(void* dev) { rtgs::set_bwd_stamps(dev); }
 void rtgs_raster_set_fwd_stamps(void* dev) { rtgs::set_fwd_stamps(dev); }
 void rtgs_raster_set_onepass_ctx(rtgs_ctx* c, int on) { use(c)->onepass = on != 0; use(c)->plan.valid = false; }
+void rtgs_raster_set_fused_sort_ctx(rtgs_ctx* c, int on) { use(c)->fused_sort = on != 0; use(c)->plan.valid = false; }
+int rtgs_raster_fused_sort_stats_ctx(rtgs_ctx* ctx, int64_t* out18) {
+  rtgs_ctx* c = use(ctx);
+  if (!out18) return RTGS_E_INVALID;
+  for (int k = 0; k < 3 * FSORT_CLASSES; ++k) out18[k] = 0;
+  if (!c->fsort_cls || c->fsort_tiles <= 0) return RTGS_OK;
+  std::vector<uint32_t> w((size_t)c->fsort_tiles);
+  HIP_TRY(hipMemcpy(w.data(), c->fsort_cls, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));   // waits for the device
+  for (uint32_t v : w) {
+    if (v == 0xffffffffu) continue;
+    const int cls = (int)(v >> 28);
+    const int64_t len = (int64_t)(v & 0x0fffffffu);
+    if (cls >= FSORT_CLASSES) continue;
+    int64_t* o = out18 + 3 * cls;
+    o[1] = o[0] == 0 ? len : (len < o[1] ? len : o[1]);
+    o[2] = len > o[2] ? len : o[2];
+    ++o[0];
+  }
+  return RTGS_OK;
+}
 void rtgs_raster_set_bwd_walk_ctx(rtgs_ctx* c, int mode) { use(c)->bwd_walk = (mode >= 1 && mode <= 4) ? mode : 0; }
 void rtgs_raster_set_aux_zero_ctx(rtgs_ctx* ctx, void* eight_words) { use(ctx)->aux_zero = (uint32_t*)eight_words; }
 int rtgs_raster_last_buffers_ctx(rtgs_ctx* ctx, void** out3) {

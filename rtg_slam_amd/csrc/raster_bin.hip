@@ -20,6 +20,7 @@
 // blend_fwd, so removing it changes no output.  The test is the minimum of the conic form over
 // the tile's pixel-centre box against 2 ln(255 o), with a safety margin far above float rounding.
 #include "raster_common.h"
+#include "raster_tilesort.h"
 #include <mutex>
 
 namespace rtgs {
@@ -447,31 +448,11 @@ __global__ void __launch_bounds__(THREADS) bin_tilesort_kernel(const uint2* __re
   if (n < lo || n >= hi) return;
   const int tid = threadIdx.x;
   if (n == 1) { if (tid == 0) point_list[r.x] = (uint32_t)bucket[r.x]; return; }
-  int n2 = 2;
-  while (n2 < n) n2 <<= 1;
-  for (int i = tid; i < n2; i += THREADS) s_key[i] = (i < n) ? bucket[r.x + i] : ~0ull;
-  __syncthreads();
-  for (int k = 2; k <= n2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += THREADS) {
-        const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1));     // index with bit j clear
-        const int b = a | j;
-        const unsigned long long ka = s_key[a], kb = s_key[b];
-        const bool up = (a & k) == 0;
-        if ((ka > kb) == up) { s_key[a] = kb; s_key[b] = ka; }
-      }
-      __syncthreads();
-    }
-  }
+  tile_sort_bitonic<THREADS>(s_key, bucket + r.x, n);
   for (int i = tid; i < n; i += THREADS) point_list[r.x + i] = (uint32_t)s_key[i];
 }
 
-// ---------------------------------------------------------------------------------------------
-// LDS radix sort of one tile bucket: LSD over the bytes of the depth bits that actually vary inside
-// the tile (usually 3 of 4), stable within a pass (wave-ordered segments, ballot ranks), then a
-// parallel fix-up that orders runs of bit-equal depths by Gaussian id.  ~6 LDS operations per key and pass instead of the
-// ~1.5 x 78 stages of the bitonic network.
-// ---------------------------------------------------------------------------------------------
+// the LDS radix sort of raster_tilesort.h, one size class [lo, hi) per launch; `cap` = keys the launch's LDS holds (>= hi - 1)
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) bin_tilesort_radix_kernel(const uint2* __restrict__ ranges,
                                                                      const unsigned long long* __restrict__ bucket,
@@ -489,97 +470,8 @@ __global__ void __launch_bounds__(THREADS) bin_tilesort_radix_kernel(const uint2
   const uint2 r = tile_range(ranges, ts, false);
   const int n = (int)(r.y - r.x);
   if (n < lo || n >= hi) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid == 0) s_or = 0;
-  __syncthreads();
-  const uint32_t z0 = (uint32_t)(bucket[r.x] >> 32);
-  uint32_t vary = 0;
-  for (int i = tid; i < n; i += THREADS) {
-    const unsigned long long k = bucket[r.x + i];
-    kA[i] = k;
-    vary |= (uint32_t)(k >> 32) ^ z0;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) vary |= (uint32_t)__shfl_xor((int)vary, off);
-  if (lane == 0 && vary) atomicOr(&s_or, vary);
-  __syncthreads();
-  const uint32_t vbits = s_or;
-  const int seg = ((n + NW - 1) / NW + 63) & ~63;        // keys per wave, multiple of 64
-  const int wlo = min(n, w * seg), whi = min(n, wlo + seg);
-  for (int pass = 0; pass < 4; ++pass) {
-    if (((vbits >> (8 * pass)) & 0xffu) == 0) continue;   // this byte is constant inside the tile
-    const int shift = 32 + 8 * pass;
-    for (int i = tid; i < NW * 256; i += THREADS) s_cnt[i] = 0;
-    __syncthreads();
-    for (int i = wlo + lane; i < whi; i += 64) atomicAdd(&s_cnt[w * 256 + (int)((kA[i] >> shift) & 0xff)], 1u);
-    __syncthreads();
-    if (tid < 256) {                                      // per digit: exclusive prefix over waves + digit total
-      uint32_t run = 0;
-#pragma unroll
-      for (int ww = 0; ww < NW; ++ww) { const uint32_t c = s_cnt[ww * 256 + tid]; s_cnt[ww * 256 + tid] = run; run += c; }
-      s_tot[tid] = run;
-    }
-    __syncthreads();
-    if (tid < 64) {                                       // exclusive scan of the 256 digit totals by one wave
-      uint32_t v0 = s_tot[4 * tid], v1 = s_tot[4 * tid + 1], v2 = s_tot[4 * tid + 2], v3 = s_tot[4 * tid + 3];
-      const uint32_t mine = v0 + v1 + v2 + v3;
-      uint32_t inc = mine;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off);
-        if (tid >= off) inc += o;
-      }
-      const uint32_t ex = inc - mine;
-      s_tot[4 * tid] = ex; s_tot[4 * tid + 1] = ex + v0; s_tot[4 * tid + 2] = ex + v0 + v1; s_tot[4 * tid + 3] = ex + v0 + v1 + v2;
-    }
-    __syncthreads();
-    for (int i0 = wlo; i0 < whi; i0 += 64) {
-      const int i = i0 + lane;
-      const bool act = i < whi;
-      const unsigned long long k = act ? kA[i] : 0ull;
-      const int d = (int)((k >> shift) & 0xff);
-      unsigned long long same = __builtin_amdgcn_ballot_w64(act);
-#pragma unroll
-      for (int bit = 0; bit < 8; ++bit) {
-        const unsigned long long m = __builtin_amdgcn_ballot_w64((d >> bit) & 1);
-        same &= ((d >> bit) & 1) ? m : ~m;
-      }
-      if (act) {
-        const unsigned long long below = same & ((1ull << lane) - 1ull);
-        const uint32_t base = s_cnt[w * 256 + d] + s_tot[d];
-        kB[base + (uint32_t)__popcll(below)] = k;
-        if ((same >> lane) == 1ull) s_cnt[w * 256 + d] += (uint32_t)__popcll(same);   // highest lane of the group
-      }
-    }
-    __syncthreads();
-    unsigned long long* tmp = kA; kA = kB; kB = tmp;
-  }
-  // Runs of bit-equal depth (the bucket was filled by atomics, so equal depths arrive in arbitrary order): order them
-  // by Gaussian id.  Usually there is none.  Otherwise every key finds its run with two binary searches over the
-  // depth-sorted array and its rank inside the run by counting the smaller ids (broadcast LDS reads) - O(run) per key
-  // and fully parallel, whatever the run length (a wall seen head-on puts hundreds of bit-equal depths into one tile).
-  bool tie = false;
-  for (int i = tid + 1; i < n; i += THREADS) tie |= (uint32_t)(kA[i] >> 32) == (uint32_t)(kA[i - 1] >> 32);
-  if (__syncthreads_or(tie)) {
-    for (int i = tid; i < n; i += THREADS) {
-      const unsigned long long key = kA[i];
-      const uint32_t z = (uint32_t)(key >> 32);
-      int lo = 0, hi = i;                       // first index with depth == z
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if ((uint32_t)(kA[mid] >> 32) < z) lo = mid + 1; else hi = mid; }
-      const int first = lo;
-      lo = i; hi = n;                           // one past the last index with depth == z
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if ((uint32_t)(kA[mid] >> 32) <= z) lo = mid + 1; else hi = mid; }
-      int rank = first;
-      if (lo - first > 1)
-        for (int j = first; j < lo; ++j) rank += (kA[j] < key) ? 1 : 0;
-      else
-        rank = i;
-      kB[rank] = key;
-    }
-    __syncthreads();
-    unsigned long long* tmp = kA; kA = kB; kB = tmp;
-  }
-  for (int i = tid; i < n; i += THREADS) point_list[r.x + i] = (uint32_t)kA[i];
+  const unsigned long long* sorted = tile_sort_radix<THREADS>(kA, kB, s_cnt, s_tot, &s_or, bucket + r.x, n);
+  for (int i = threadIdx.x; i < n; i += THREADS) point_list[r.x + i] = (uint32_t)sorted[i];
 }
 
 // ------------------------------------------------------------------------------ launchers
@@ -944,6 +836,16 @@ void launch_bin_tilesort(int ntiles, uint32_t longest, const uint2* ranges, cons
     hipLaunchKernelGGL(bin_tilesort_kernel<1024>, dim3(ntiles), dim3(1024), 16384 * 8, st, ranges, bucket, point_list,
                        8193, 16385, spec_fail, ts, nofin);
   }
+}
+
+// The near slice with the sort fused into blend_fwd (raster_fwd.hip: FSORT): lists of up to FSORT_CAP entries are sorted
+// by the blend's own workgroup; only the class above it - (1024, SLICE_MAX_LIST], whose keys do not fit the blend's LDS -
+// keeps its launch, ahead of the blend.
+void launch_bin_tilesort_long(int ntiles, const uint2* ranges, const unsigned long long* bucket, uint32_t* point_list,
+                              const uint32_t* spec_fail, hipStream_t st, const uint32_t* seg_count, uint32_t seg) {
+  static_assert(SLICE_MAX_LIST == 3072 && FSORT_CAP == 1024, "the one class between the fused sort and pass 2");
+  launch_radix<512>(ntiles, ranges, bucket, point_list, FSORT_CAP + 1, SLICE_MAX_LIST + 1, SLICE_MAX_LIST, spec_fail,
+                    TileSeg{seg_count, seg, nullptr}, st);
 }
 
 }  // namespace rtgs

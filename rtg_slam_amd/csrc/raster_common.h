@@ -130,6 +130,20 @@ struct SlicePass {
   uint2* ranges_bwd;             // mode 1: range of a finished tile, (0,0) otherwise - what blend_bwd walks
   uint2* ranges_main;            // mode 1: the main pass's ranges, written empty (pass 2 overwrites them if it runs)
 };
+// The near-slice blend that sorts its tile's list itself (blend_fwd_kernel<.., FSORT>; bucket == nullptr: lists arrive
+// sorted in point_list).  Lists of up to FSORT_CAP entries are sorted in the blend's LDS - bitonic up to FSORT_BITONIC,
+// the LDS radix above - and written to point_list for the backward; longer ones (up to SLICE_MAX_LIST) were sorted by a
+// launch ahead of the blend.
+constexpr int FSORT_BITONIC = 256;
+constexpr int FSORT_CAP = 1024;
+struct FusedSort {
+  const unsigned long long* bucket;   // unsorted keys (depth bits << 32 | id), laid out like point_list
+  const uint32_t* count;              // per-tile segments (one-pass placement): entries of tile t, at t * seg; nullptr: `ranges`
+  uint2* ranges_out;                  // segments: where the tile's range goes for the backward
+  uint32_t* list_out;                 // point_list, for writing: the sorted ids (the backward and later batches read them)
+  uint32_t* tile_class;               // accounting variant only: per tile (class << 28 | list length), see FSORT_CLASSES
+};
+enum { FSORT_EMPTY = 0, FSORT_SINGLE, FSORT_BITONIC_CLS, FSORT_RADIX, FSORT_LAUNCH, FSORT_PASS2, FSORT_CLASSES };
 // Shading work list of the two-pass forward (preprocess_fwd_kernel<2>, bin_count / bin_scatter in slice mode):
 // the near slice's Gaussian ids, appended in arbitrary order by slice_compact_kernel.
 struct SliceList {

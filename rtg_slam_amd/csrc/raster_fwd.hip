@@ -5,6 +5,7 @@
 // own CUDA sources are an un-vendored submodule (/root/reference/.gitmodules:1-4), its call
 // contract is /root/reference/SLAM/render.py:68-128.
 #include "raster_common.h"
+#include "raster_tilesort.h"
 #include <stdlib.h>
 
 namespace rtgs {
@@ -346,7 +347,7 @@ constexpr int FWD_CHUNKS = FWD_BATCH / 32;      // 32-entry words of a block's s
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-template <int OCC, bool STAMP, bool COUNT, bool ASMW>
+template <int OCC, bool STAMP, bool COUNT, bool ASMW, bool FSORT>
 __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
     RasterParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const Splat* __restrict__ splats, float* __restrict__ out_color, float* __restrict__ out_depth,
@@ -354,14 +355,24 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
     float* __restrict__ out_dw, float* __restrict__ out_T, uint32_t* __restrict__ n_contrib,
     unsigned long long* __restrict__ counters, SlicePass sp, uint32_t* __restrict__ tile_mode,
     uint32_t* __restrict__ depth_pos, uint32_t* __restrict__ tile_last, int walk, uint32_t* __restrict__ aux_zero,
-    TileCache tc, unsigned long long* __restrict__ stamps, uint32_t seg) {
-  __shared__ float4 s_rec[FWD_BATCH * 4];     // u v ca cb | cc o r g | b - - id | nx ny nz pd: the walk reads the first three
+    TileCache tc, unsigned long long* __restrict__ stamps, uint32_t seg, FusedSort fs) {
+  // ONE raw LDS arena.  The walk's view of it: s_rec 16 KB | s_z 1 KB | s_live 512 B, and (FSORT) the tile's sorted ids
+  // behind them, 4 KB.  The sorting prologue's view of the same bytes, BEFORE anything is staged: the bitonic network's
+  // keys in [0, 2 KB), or the radix's kA 8 KB | kB 8 KB | digit counters of the four waves 4 KB | digit totals 1 KB | one
+  // word.  22 016 B with the sort, 17 920 B without: six workgroups per CU fit the 160 KB either way.
+  constexpr int A_Z = FWD_BATCH * 64, A_LIVE = A_Z + FWD_BATCH * 4, A_IDS = A_LIVE + 16 * FWD_CHUNKS * 4;
+  constexpr int A_BYTES = FSORT ? A_IDS + FSORT_CAP * 4 : A_IDS;
+  static_assert(2 * FSORT_CAP * 8 + (BLOCK / 64 + 1) * 256 * 4 + 4 <= A_IDS + FSORT_CAP * 4, "the radix's LDS fits the arena");
+  static_assert(2 * FSORT_CAP * 8 <= A_IDS, "the sorted keys end in front of the id area they are copied to");
+  __shared__ __attribute__((aligned(16))) unsigned char s_arena[A_BYTES];
+  float4* const s_rec = reinterpret_cast<float4*>(s_arena);     // u v ca cb | cc o r g | b - - id | nx ny nz pd: the walk reads the first three
   // (entry-major, 64 B per entry.  Four planes of FWD_BATCH float4 - the four rows of a wave read four DIFFERENT entries per
   // step, and entry-major two of them collide on their banks whenever their indices agree mod 4 - were measured in round 6:
   // 82.1 / 131.3 us against 80.9 / 131.0.  The walk is not bound by LDS bank conflicts.)
 #define RI(e, j) ((e) * 4 + (j))
-  __shared__ float s_z[FWD_BATCH];            // centre depth (opaque-surface test only)
-  __shared__ uint32_t s_live[16][FWD_CHUNKS]; // per 4x4 block: the staged entries that reach it
+  float* const s_z = reinterpret_cast<float*>(s_arena + A_Z);      // centre depth (opaque-surface test only)
+  uint32_t (*const s_live)[FWD_CHUNKS] = reinterpret_cast<uint32_t (*)[FWD_CHUNKS]>(s_arena + A_LIVE);   // per 4x4 block: the staged entries that reach it
+  [[maybe_unused]] uint32_t* const s_ids = reinterpret_cast<uint32_t*>(s_arena + A_IDS);   // FSORT: the list, sorted (<= FSORT_CAP ids)
 
   unsigned long long st_wall = 0, st_cyc = 0, st_range = 0, st_first = 0, st_walk = 0, st_steps = 0, st_batches = 0;
   if constexpr (STAMP) { st_wall = wall_clock64(); st_cyc = __builtin_readcyclecounter(); }
@@ -374,12 +385,18 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   // and the id hop were 5.4 us of a 27-us tile).  `z` is a zero the compiler cannot see.
   int z = 0;
   asm volatile("" : "+v"(z));
-  const uint2 range_v = ranges[tile + z];
+  // (FSORT on per-tile segments: nobody has written the range yet - it follows from the tile's count)
+  uint2 range_v;
+  if (FSORT && fs.count) { const uint32_t x0 = (uint32_t)tile * seg; range_v = make_uint2(x0, x0 + fs.count[tile + z]); }
+  else range_v = ranges[tile + z];
   const uint32_t fail_v = p.spec_fail ? p.spec_fail[z] : 0u;
   const int32_t m2_v = sp.mode == 2 ? sp.mask2[tile + z] : 1;
   const int32_t on_v = sp.mode == 1 ? sp.user_mask[tile + z] : 1;
   uint32_t id_first = 0u;
-  if (seg != 0u) id_first = point_list[(size_t)tile * seg + (size_t)tid];     // (inside the tile's segment whatever its count)
+  // (FSORT: the unsorted key of segment position tid instead - what the one-key-per-thread sort starts from)
+  [[maybe_unused]] unsigned long long key_first = ~0ull;
+  if (FSORT && fs.count) key_first = fs.bucket[(size_t)tile * seg + (size_t)tid];
+  if (!FSORT && seg != 0u) id_first = point_list[(size_t)tile * seg + (size_t)tid];     // (inside the tile's segment whatever its count)
   // eight words a later kernel of the caller's step accumulates into (the loss sums of rtgs_slam_map_step): cleared here,
   // stream-ordered before that kernel, instead of by a memset launch of their own
   if (aux_zero && blockIdx.x == 0 && blockIdx.y == 0 && tid < 8) aux_zero[tid] = 0u;
@@ -397,6 +414,47 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   int n = (int)(range.y - range.x);
   if (sp.mode == 1 && n > SLICE_MAX_LIST) n = 0;       // near-slice list too long to have been sorted: leave the tile to pass 2
   if constexpr (STAMP) { st_range = __builtin_readcyclecounter() - st_cyc; }
+
+  // ---- FSORT: the tile's list is sorted HERE, in the arena nothing has been staged into yet, instead of by the three sort
+  // launches in front of the blend (raster_bin.hip; same device functions, keys are unique: the same list).  Five other
+  // workgroups of the CU are in their walks meanwhile.  The ids go to point_list for the backward, and into LDS behind
+  // the staging area, where the batches of THIS kernel take them from (the first batch of a bitonic-sorted list: from the
+  // sorting thread's register): no global read-back of what the workgroup wrote, so no ordering question.
+  // Lists above FSORT_CAP were sorted by a launch ahead of this kernel; those above SLICE_MAX_LIST are left to pass 2 (n = 0).
+  [[maybe_unused]] uint32_t id_mine = 0u;      // FSORT, lists of up to FSORT_BITONIC entries: the id of list position tid
+  if constexpr (FSORT) {
+    if (tid == 0) {
+      if (fs.ranges_out) fs.ranges_out[tile] = range;      // segments: what the first sort launch wrote for the backward
+      if (COUNT && fs.tile_class) {
+        const uint32_t len = range.y - range.x;
+        const uint32_t cls = len > (uint32_t)SLICE_MAX_LIST ? FSORT_PASS2 : len > (uint32_t)FSORT_CAP ? FSORT_LAUNCH :
+                             len > (uint32_t)FSORT_BITONIC ? FSORT_RADIX : len > 1u ? FSORT_BITONIC_CLS : len == 1u ? FSORT_SINGLE : FSORT_EMPTY;
+        fs.tile_class[tile] = (cls << 28) | min(len, 0x0fffffffu);
+      }
+    }
+    if (n >= 1 && n <= FSORT_CAP) {
+      const unsigned long long* const src = fs.bucket + range.x;
+      unsigned long long* const kA = reinterpret_cast<unsigned long long*>(s_arena);
+      if (n == 1) {
+        // no sort: thread 0 holds the only key (and stages it, as position 0 of the first batch)
+        if (tid == 0) { id_mine = (uint32_t)(fs.count ? key_first : src[0]); fs.list_out[range.x] = id_mine; }
+      } else if (n <= FSORT_BITONIC) {
+        // one key per thread: thread t ends with the id of list position t - the first batch stages it from the register;
+        // later batches read s_ids behind the barriers of the batch loop.  (The sort returns behind its last barrier.)
+        int n2 = 2;
+        while (n2 < n) n2 <<= 1;
+        const unsigned long long key = tid < n ? (fs.count ? key_first : src[tid]) : ~0ull;
+        id_mine = (uint32_t)tile_sort_bitonic_reg<BLOCK>(kA, key, n2);
+        if (tid < n) { s_ids[tid] = id_mine; fs.list_out[range.x + tid] = id_mine; }
+      } else {
+        uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_arena + 2 * FSORT_CAP * 8);
+        const unsigned long long* const sorted =
+            tile_sort_radix<BLOCK>(kA, kA + FSORT_CAP, s_cnt, s_cnt + (BLOCK / 64) * 256, s_cnt + (BLOCK / 64 + 1) * 256, src, n);
+        for (int i = tid; i < n; i += BLOCK) { const uint32_t id = (uint32_t)sorted[i]; s_ids[i] = id; fs.list_out[range.x + i] = id; }
+        __syncthreads();      // the ids are in place, and nobody reads a key any more: the arena is the walk's from here
+      }
+    }
+  }
 
   bool done = !inside;
   unsigned long long Dm = __builtin_amdgcn_ballot_w64(!inside);     // ASMW: the wave's stopped pixels as a mask in SGPRs
@@ -420,7 +478,9 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
     {
       uint32_t reach = 0;
       if (tid < m) {
-        const uint32_t id = (seg != 0u && base == 0) ? id_first : point_list[range.x + base + tid];
+        uint32_t id;
+        if constexpr (FSORT) id = (n <= FSORT_BITONIC && base == 0) ? id_mine : n <= FSORT_CAP ? s_ids[base + tid] : point_list[range.x + base + tid];
+        else id = (seg != 0u && base == 0) ? id_first : point_list[range.x + base + tid];
         const float4* src = reinterpret_cast<const float4*>(splats + id);
         const float4 q0 = src[0];
         s_rec[RI(tid, 0)] = q0;
@@ -975,15 +1035,20 @@ void launch_blend_fwd(const RasterParams& p, const uint2* ranges, const uint32_t
                       float* out_color, float* out_depth, int32_t* out_cidx, int32_t* out_didx, float* out_cw,
                       float* out_dw, float* out_T, uint32_t* n_contrib, unsigned long long* counters,
                       SlicePass sp, uint32_t* tile_mode, uint32_t* depth_pos, uint32_t* tile_last, int walk, uint32_t* aux_zero,
-                      TileCache tc, uint32_t seg, hipStream_t st) {
-#define RTGS_FWD1(OCC, STAMP, COUNT, ASMW) hipLaunchKernelGGL((blend_fwd_kernel<OCC, STAMP, COUNT, ASMW>), dim3(p.gx, p.gy), dim3(BLOCK), 0, st, p, ranges, point_list, splats, \
+                      TileCache tc, uint32_t seg, hipStream_t st, FusedSort fs) {
+#define RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, FS) hipLaunchKernelGGL((blend_fwd_kernel<OCC, STAMP, COUNT, ASMW, FS>), dim3(p.gx, p.gy), dim3(BLOCK), 0, st, p, ranges, point_list, splats, \
                        out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T, n_contrib, counters, sp, tile_mode, \
-                       depth_pos, tile_last, walk, aux_zero, tc, g_fwd_stamps, seg)
-  if (g_f1_asm == 0) RTGS_FWD1(6, false, true, false);      // the compiler's walk loop (A-B, tests): RTGS_F1_ASM=0
+                       depth_pos, tile_last, walk, aux_zero, tc, g_fwd_stamps, seg, fs)
+  // the sorting prologue is a template parameter: the main pass, forwards without a slice and RTGS_F1_ASM=0 run the kernel without it
+#define RTGS_FWD1(OCC, STAMP, COUNT, ASMW) do { if (fs.bucket) RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, true); else RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, false); } while (0)
+  if (fs.bucket && (g_f1_asm == 0 || sp.mode != 1)) abort();      // the caller asks blend_fwd_fuses_sort() first
+  if (g_f1_asm == 0) RTGS_FWD1F(6, false, true, false, false);      // the compiler's walk loop (A-B, tests): RTGS_F1_ASM=0
   else if (counters) RTGS_FWD1(6, false, true, true);        // work counters asked for (bench.py's roofline, tests): the accounting variant
   else if (g_fwd_stamps) RTGS_FWD1(6, true, false, true);
   else if (g_f1_occ == 5) RTGS_FWD1(5, false, false, true); else RTGS_FWD1(6, false, false, true);   // (7 / 8 waves: 79.6 / 79.0 us against 80.3 in round 5; the walk's named registers need 80 VGPRs)
 #undef RTGS_FWD1
+#undef RTGS_FWD1F
 }
+bool blend_fwd_fuses_sort() { return g_f1_asm != 0; }
 
 }  // namespace rtgs

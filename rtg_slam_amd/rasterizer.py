@@ -80,6 +80,17 @@ class RasterContext:
         """One-pass binning into per-tile segments (default on); off = count + scan + scatter.  Bit-identical outputs."""
         _lib.load().rtgs_raster_set_onepass_ctx(self.ptr, int(bool(enable)))
 
+    def set_fused_sort(self, enable: bool):
+        """Near slice: blend_fwd sorts each tile's list itself (default on); off = the sort launches.  Same lists, same outputs."""
+        _lib.load().rtgs_raster_set_fused_sort_ctx(self.ptr, int(bool(enable)))
+
+    def fused_sort_stats(self):
+        """Per list-length class of the last fused near-slice blend that ran with work counters set: tiles, shortest, longest."""
+        out = (C.c_int64 * 18)()
+        _lib.check(_lib.load().rtgs_raster_fused_sort_stats_ctx(self.ptr, out), "rtgs_raster_fused_sort_stats")
+        names = ("empty", "single", "bitonic", "radix", "launch", "pass2")
+        return {n: dict(tiles=int(out[3 * k]), shortest=int(out[3 * k + 1]), longest=int(out[3 * k + 2])) for k, n in enumerate(names)}
+
     def set_speculation(self, enable: bool):
         """Speculative sizing of the forward inside the one-call map step (RTGS_FWD_SPECULATE); default on."""
         _lib.load().rtgs_raster_set_speculation_ctx(self.ptr, int(bool(enable)))
