@@ -573,6 +573,39 @@ int rtgs_mesh_distance_keys(const float* points, int64_t N, const float* origin_
 int rtgs_mesh_distance_normals(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face, int64_t N,
                                float* normals, void* stream);
 
+/* ---- mesh registration: the point-to-plane normal equations of points against the faces a mesh distance query gave them, summed
+ * in a fixed order (no counterpart in the reference; csrc/mesh_register.hip).  tests/mesh_register_reference.py restates it in
+ * numpy; the kernels match it bit for bit.
+ *
+ * points [N][3] float32, face [N] int32 and d2 [N] float32 as rtgs_mesh_distance_query wrote them for these points, src_normals
+ * [N][3] float32 or NULL, vertices / V / faces / F the query's mesh (the CALLER guarantees 0 <= faces[.] < V), center_host 3 floats
+ * on the HOST.  Correspondence i TAKES PART when all of
+ *   0 <= face[i] < F;
+ *   d2[i] <= max_d2, compared in float32 (equality keeps it, a NaN drops it);
+ *   n != (0, 0, 0), n the unit normal of face[i] exactly as rtgs_mesh_distance_normals forms it (one shared device function);
+ *   with src_normals: |(s.x n.x + s.y n.y) + s.z n.z| >= min_cos, s = src_normals[i], every step one rounded float32 operation.
+ * Its terms are float64, every step one rounded operation on the float32 inputs widened: a = the face's first corner,
+ *   q = p - center,  e = p - a,  r = (n.x e.x + n.y e.y) + n.z e.z,
+ *   J = (q.y n.z - q.z n.y,  q.z n.x - q.x n.z,  q.x n.y - q.y n.x,  n.x, n.y, n.z),
+ *   t[0..20] = J[i] J[j] for i <= j, row-major;  t[21..26] = J[i] r;  t[27] = r r;  t[28] = d2[i];  t[29] = 1.
+ * A correspondence that does not take part has t = +0.  out [30] float64 on the device = the sum of t over i in THIS order, which
+ * depends on N alone (not on the grid, the number of CUs or any arrival order; there are no float atomics):
+ *   chunk  point i belongs to chunk i / C, C = RTGS_MESH_REGISTER_CHUNK = 1024.  Slot s (0..255) of a chunk starts at +0 and adds
+ *          the points C chunk + s, + 256, + 512, + 768 (those below N) in that order.
+ *   tree   256 slots -> one value: slots 64 w .. 64 w + 63 are wave w; inside a wave x[l] = x[l] + x[l + o] for l < o, with
+ *          o = 32, 16, 8, 4, 2, 1 in turn, leaves the wave's value in x[0]; the four waves give (w0 + w1) + (w2 + w3).
+ *   total  a second launch of one workgroup: slot s starts at +0 and adds the chunk values s, s + 256, s + 512, ... in that
+ *          order, then the same tree.
+ * N == 0 writes 30 zeros.  scratch: rtgs_mesh_register_scratch_bytes(N) bytes (the chunk values; 0 for N <= 0), the caller's,
+ * 8-byte aligned, reusable by the next call.  Two launches on `stream`, no host read.
+ * Return 0, -1 on a bad argument (N < 0 or >= 2^31, V or F <= 0, a null pointer that is needed), -2 on a launch failure. */
+#define RTGS_MESH_REGISTER_CHUNK 1024
+#define RTGS_MESH_REGISTER_OUT 30
+size_t rtgs_mesh_register_scratch_bytes(int64_t N);
+int rtgs_mesh_register_accumulate(const float* points, const int32_t* face, const float* d2, const float* src_normals, int64_t N,
+                                  const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float* center_host,
+                                  float max_d2, float min_cos, void* scratch, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,10 @@ rendered depth, not the sensor's.  `metric --mesh-depth` renders save_model/mesh
 `mesh --cull-unseen` removes the surface no fused view could see before the mesh is written.
 `metric --mesh --surface-distance` scores save_model/mesh_tsdf.ply against the GT mesh's SURFACE by exact point-to-triangle
 distances (evaluation.eval_mesh_surface), with the normal consistency, and writes eval_metric/surface_distance_frame_F_iter_I.json.
+`metric --align [--align-max-distance 0.10] [--align-iterations 30]` registers the scored geometry rigidly to the full GT surface
+(evaluation.align_to_gt: point-to-plane ICP on exact nearest faces), scores it again under that transform and writes the transform,
+the registration report and the unaligned and aligned figures to eval_metric/aligned_frame_F_iter_I.json: the transform measures
+the tracker's drift, the aligned figures the shape.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -357,6 +361,9 @@ def cmd_metric(opts) -> int:
     if opts.surface_distance and not opts.mesh:
         log("--surface-distance needs --mesh")
         return 2
+    if opts.align and (not opts.align_max_distance > 0 or opts.align_iterations < 1):
+        log("--align-max-distance must be > 0 (metres) and --align-iterations >= 1")
+        return 2
     if opts.cull_depth == "mesh" and not opts.cull_gt:
         log("--cull-depth mesh needs --cull-gt")
         return 2
@@ -376,6 +383,9 @@ def cmd_metric(opts) -> int:
         return 2
     if opts.surface_distance and not (info.mesh_path and os.path.isfile(info.mesh_path)):
         log(f"--surface-distance: there is no GT mesh to measure against ({info.mesh_path or 'this dataset type has none'})")
+        return 2
+    if opts.align and not (info.mesh_path and os.path.isfile(info.mesh_path)):
+        log(f"--align: there is no GT mesh to align to ({info.mesh_path or 'this dataset type has none'})")
         return 2
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
     log(f"evaluating at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
@@ -438,7 +448,6 @@ def cmd_metric(opts) -> int:
         log(f"mesh depth: L1 {100 * md.get('mesh_depth_l1', float('nan')):.3f} cm over {md.get('mesh_valid_ratio', float('nan')):.4f} "
             f"of the pixels, {len(rows)} frames -> {md_path}")
     if opts.surface_distance:                # the reconstructed mesh against the GT surface (the culled one with --cull-gt)
-        import time
         gv, gf = gt_cull.mesh() if gt_cull is not None else iof.load_mesh_ply(info.mesh_path)
         mv, mf = iof.load_mesh_ply(mesh_path)
         reports = {}
@@ -456,6 +465,51 @@ def cmd_metric(opts) -> int:
             json.dump(sd, fo, indent=1, default=float)
         log(f"surface distance: accuracy {sd['accuracy']:.4f} cm, completion {sd['completion']:.4f} cm, F1 {sd['F1 (< 0.03)']:.3f}, "
             f"normal consistency {sd['normal_consistency']:.4f} -> {sd_path}")
+    if opts.align:                           # register the scored geometry to the FULL GT surface, then score it again
+        from . import mesh_ops
+        gv, gf = iof.load_mesh_ply(info.mesh_path)
+        with torch.no_grad():
+            src = mapper.opt.gaussian_data("all")["xyz"].detach() if rec_points is None else rec_points
+        normals, kw = None, {}
+        if mesh_path is not None:            # the samples' own face normals: the draw of sample_mesh_points, again
+            mv, mf = iof.load_mesh_ply(mesh_path)
+            _, own = iof.sample_mesh_surface(mv, mf, 1_000_000, 0)
+            dv = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt).contiguous()
+            normals = mesh_ops.face_unit_normals(dv(mv, torch.float32).reshape(-1, 3), dv(mf, torch.int64).reshape(-1, 3).to(torch.int32),
+                                                 dv(own, torch.int32))
+            kw["min_cos"] = 0.5
+        reports = {}
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        T_total, reg = evaluation.align_to_gt(src, gv, gf, transform=transform, source_normals=normals, reports=reports,
+                                              max_distance=opts.align_max_distance, max_iterations=opts.align_iterations, **kw)
+        seconds = time.perf_counter() - t0
+        T_align = T_total @ np.linalg.inv(np.asarray(transform, dtype=np.float64).reshape(4, 4))
+        same_gt = gt_points                  # the GT points the unaligned figures were scored against
+        if gt_cull is not None:
+            same_gt = evaluation.sample_mesh_points(*gt_cull.mesh(), 1_000_000, 0, device)
+        aligned = evaluation.eval_pcd(src, same_gt, [0.03], T_total, 1_000_000)
+        row = res["rows"][-1] if res["rows"] else {}
+        unaligned = {k: row[k] for k in aligned} if all(k in row for k in aligned) else \
+            evaluation.eval_pcd(src, same_gt, [0.03], transform, 1_000_000)
+        al = {"transform": T_align.tolist(), "transform_total": T_total.tolist(), "registration": reg, "unaligned": unaligned,
+              "aligned": aligned, "source": mesh_path if mesh_path is not None else pcd_path, "gt_mesh": info.mesh_path,
+              "gt_culled": gt_cull is not None, "max_distance": opts.align_max_distance, "max_iterations": opts.align_iterations,
+              "distance_gt": reports["gt"], "seconds": seconds}
+        if opts.surface_distance:            # sd: the unaligned surface figures, written above
+            sgv, sgf = gt_cull.mesh() if gt_cull is not None else (gv, gf)
+            al["surface_aligned"] = evaluation.eval_mesh_surface(mv, mf, sgv, sgf, dist_thres=[0.03], transform=T_total,
+                                                                 sample_nums=1_000_000, device=device)
+            al["surface_unaligned"] = {k: sd[k] for k in al["surface_aligned"]}
+        al_dir = os.path.join(args.save_path, "eval_metric")
+        os.makedirs(al_dir, exist_ok=True)
+        al_path = os.path.join(al_dir, f"aligned_frame_{mapper.time}_iter_{test_iter}.json")
+        with open(al_path, "w") as fo:
+            json.dump(al, fo, indent=1, default=float)
+        log(f"aligned: rotation {reg['rotation_deg']:.4f} deg, translation {100 * reg['translation_m']:.4f} cm, "
+            f"{reg['inlier_share']:.4f} inliers; accuracy {unaligned['accuracy']:.4f} -> {aligned['accuracy']:.4f} cm, completion "
+            f"{unaligned['completion']:.4f} -> {aligned['completion']:.4f} cm, F1 {unaligned['F1 (< 0.03)']:.3f} -> "
+            f"{aligned['F1 (< 0.03)']:.3f} -> {al_path}")
     out = os.path.join(args.save_path, f"statis_frame_{mapper.time}_iter_{test_iter}.csv")
     iof.save_metrics_csv(out, res["rows"])
     m = res["mean"]
@@ -509,6 +563,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "point-to-triangle distances - accuracy from 1 M samples of the mesh to the GT surface, completion from 1 M "
                         "samples of the GT mesh to the mesh's surface, and the normal consistency - and write "
                         "eval_metric/surface_distance_frame_F_iter_I.json; the statis csv is what it is without the flag")
+    m.add_argument("--align", action="store_true",
+                   help="after the evaluation, register the scored geometry (the mesh samples with --mesh, else pcd_densify.ply's "
+                        "points, else the Gaussian centres) rigidly to the FULL GT surface by point-to-plane ICP on exact nearest "
+                        "faces, score it again under that transform against the same GT points, and write the transform, the "
+                        "registration report and both sets of figures to eval_metric/aligned_frame_F_iter_I.json; every other "
+                        "file is what it is without the flag")
+    m.add_argument("--align-max-distance", type=float, default=0.10, metavar="D",
+                   help="with --align: correspondences farther than D metres from the GT surface take no part (default 0.10)")
+    m.add_argument("--align-iterations", type=int, default=30, metavar="K",
+                   help="with --align: at most K Gauss-Newton updates (default 30)")
     t = sub.add_parser("mesh", help="fuse the map into a TSDF volume and write save_model/mesh_tsdf.ply")
     t.add_argument("--config", required=True)
     t.add_argument("--load-frame", type=int, default=-1)

@@ -299,6 +299,10 @@ _SIGNATURES = {
                                            _P, _P]),
     "rtgs_mesh_distance_keys": (C.c_int, [_P, C.c_int64, _P, C.c_float, _P, _P, _P]),
     "rtgs_mesh_distance_normals": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    # mesh registration
+    "rtgs_mesh_register_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "rtgs_mesh_register_accumulate": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, C.c_float, _P, _P,
+                                                _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -44,6 +44,7 @@
 // Index range: the caller guarantees 0 <= faces[i] < V, finite vertices with |coordinate| <= 2^20, and that the grid holds the
 // mesh with half a cell to spare (mesh_ops.MeshDistance checks all three once).  Element indices are 64-bit.
 #include "../../include/rtgs_slam.h"
+#include "mesh_face_normal.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -407,17 +408,9 @@ __global__ void __launch_bounds__(NT) normals_kernel(const float* __restrict__ v
   const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
   if (i >= N) return;
   const int64_t f = face[i];
-  float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-  if (f >= 0 && f < F) {
-    const int64_t ia = faces[f * 3], ib = faces[f * 3 + 1], ic = faces[f * 3 + 2];
-    const float ax = vertices[ia * 3], ay = vertices[ia * 3 + 1], az = vertices[ia * 3 + 2];
-    const float e1x = vertices[ib * 3] - ax, e1y = vertices[ib * 3 + 1] - ay, e1z = vertices[ib * 3 + 2] - az;
-    const float e2x = vertices[ic * 3] - ax, e2y = vertices[ic * 3 + 1] - ay, e2z = vertices[ic * 3 + 2] - az;
-    const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
-    const float l = sqrtf((cx * cx + cy * cy) + cz * cz);
-    if (l > 0.0f && l < INFINITY) { nx = cx / l; ny = cy / l; nz = cz / l; }
-  }
-  normals[i * 3] = nx; normals[i * 3 + 1] = ny; normals[i * 3 + 2] = nz;
+  float a[3], n[3] = {0.0f, 0.0f, 0.0f};
+  if (f >= 0 && f < F) rtgs_face_unit_normal(vertices, faces, f, a, n);                    // mesh_face_normal.h
+  normals[i * 3] = n[0]; normals[i * 3 + 1] = n[1]; normals[i * 3 + 2] = n[2];
 }
 
 inline bool make_grid(const float* origin_host, float cell, const int32_t* dims_host, float vmax, Grid* g) {

@@ -12,6 +12,8 @@
     eval_mesh          (no counterpart)       eval_pcd of points sampled on a triangle mesh's surface (rtg_slam_amd.meshing)
     eval_mesh_surface  (no counterpart)       the same keys from samples of each mesh to the other's SURFACE (exact point-to-
                                               triangle distances, mesh_ops.MeshDistance), and the normal consistency
+    align_to_gt        (no counterpart)       the rigid transform that registers a reconstruction to the GT surface
+                                              (mesh_ops.register_to_mesh), to score shape apart from drift
     VisibilityCull     (no counterpart)       the part of the GT mesh the evaluated frames saw: per vertex, against the sensor
                                               depth, at the GT poses (include/rtgs_slam.h, "visibility")
     MeshRenderer       (no counterpart)       the depth and face maps of a triangle mesh at a pose (include/rtgs_slam.h, "mesh
@@ -251,6 +253,48 @@ def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres
     if reports is not None:
         reports["gt"], reports["rec"] = gmd.report(), rmd.report()
     return res
+
+
+def align_to_gt(rec_points, gt_vertices, gt_faces, transform=None, sample_nums: int = 1_000_000,
+                generator: Optional[torch.Generator] = None, source_normals=None, reports: Optional[Dict] = None, **kw):
+    """Register a reconstruction rigidly to the GT SURFACE (mesh_ops.register_to_mesh: point-to-plane ICP on exact nearest
+    faces) -> (T_total [4,4] float64, report), T_total = T_align @ transform: what eval_pcd and eval_mesh_surface take as
+    `transform` to score the aligned reconstruction.  rec_points [P,3] on the device are subsampled without replacement to
+    sample_nums as eval_pcd subsamples them (source_normals [P,3], the points' own unit normals, follow the draw), moved by
+    `transform` (4x4; the normals by its rotation) and registered from the identity; T_align is the rigid error the
+    registration found, the report is register_to_mesh's.  gt_vertices / gt_faces: arrays or device tensors.  **kw goes to
+    register_to_mesh (max_distance, max_iterations, min_cos, rank_tol).  `reports`, a dict, receives "gt": the GT's
+    MeshDistance.report()."""
+    from . import mesh_ops, slam_ops as so
+    dev = _dev(rec_points)
+    rec = rec_points.detach().float().reshape(-1, 3)
+    nrm = None
+    if source_normals is not None:
+        _dev(source_normals)
+        nrm = source_normals.detach().float().reshape(-1, 3)
+        if nrm.shape != rec.shape:
+            raise ValueError("rtg_slam_amd.evaluation: source_normals must hold one row per point")
+    if rec.shape[0] == 0:
+        raise ValueError("rtg_slam_amd.evaluation: align_to_gt needs a non-empty point set")
+    P = int(rec.shape[0])
+    if P > sample_nums:                                                # subsample()'s draw, shared by the points and the normals
+        pick = torch.randperm(P, generator=generator)[:int(sample_nums)].to(dev)
+        rec, nrm = rec[pick], None if nrm is None else nrm[pick]
+    base = np.eye(4) if transform is None else np.asarray(transform, dtype=np.float64).reshape(4, 4)
+    if transform is not None:
+        m = np.asarray(transform, dtype=np.float32).reshape(4, 4)
+        rec = so.transform_map(rec.contiguous(), torch.as_tensor(m))
+        if nrm is not None:
+            r = m.copy()
+            r[:3, 3] = 0.0
+            nrm = so.transform_map(nrm.contiguous(), torch.as_tensor(r))
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(to_np(a))).to(device=dev, dtype=dt).contiguous()
+    md = mesh_ops.MeshDistance(up(gt_vertices, torch.float32).reshape(-1, 3), up(gt_faces, torch.int64).reshape(-1, 3).to(torch.int32))
+    T, report = mesh_ops.register_to_mesh(rec.contiguous(), md, source_normals=None if nrm is None else nrm.contiguous(), **kw)
+    if reports is not None:
+        reports["gt"] = md.report()
+    return T @ base, report
 
 
 # ---------------------------------------------------------------------------------------------------------------------

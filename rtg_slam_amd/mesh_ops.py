@@ -11,6 +11,8 @@ so none of this.
     decimate                  quadric-error half-edge collapse to a target face count (csrc/mesh_decimate.hip): vertices are
                               removed, never moved, so corners stay sharp and the result stays manifold
     MeshDistance              the exact distance from points to the nearest face, and that face (csrc/mesh_distance.hip)
+    register_to_mesh          rigid point-to-plane ICP of points to a MeshDistance's surface (csrc/mesh_register.hip sums the
+                              normal equations in a fixed order; tests/mesh_register_reference.py is the definition)
 
 All take an indexed mesh on the device - vertices [V,3] float32, faces [F,3] int32, colours [V,3] float32 - from
 TsdfVolume.extract_mesh, SparseTsdfVolume.extract_mesh or another of these.  Every result is unique and independent of
@@ -40,6 +42,9 @@ DISTANCE_LARGE_MAX = 64              # cell boxes of more cells go to the wave p
 DISTANCE_CELL_EDGES = 2.0            # the default cell in mean edge lengths ("mesh distance", has the measurement)
 DISTANCE_MIN_CELL_SHARE = 512        # ... but not below the mesh's extent / this
 DISTANCE_SORT = True                 # sort the queries by cell first (same section: 6 to 14 times faster)
+REGISTER_OUT = 30                    # RTGS_MESH_REGISTER_OUT: 21 of J J^T, 6 of J r, r r, d2, the count
+REGISTER_MIN_INLIERS = 6             # fewer correspondences do not determine a rigid motion
+REGISTER_STOP = 1e-6                 # radians and metres: an update below both ends register_to_mesh
 
 
 def _p(t):
@@ -444,6 +449,7 @@ class MeshDistance:
         box = torch.cat([used.amin((0, 1)).double(), used.amax((0, 1)).double(), used.abs().amax().double().reshape(1),
                          edge.reshape(1)]).cpu().numpy()
         lo, hi, vmax, mean_edge = box[:3], box[3:6], float(box[6]), float(box[7])
+        self.box = (lo.copy(), hi.copy())                                         # of the vertices the faces use, float64
         if not vmax <= DISTANCE_MAX_COORD:                                        # NaN fails too
             raise ValueError(f"rtg_slam_amd.mesh_ops: MeshDistance needs finite vertices with |coordinate| <= 2^20, found {vmax}")
         extent = float((hi - lo).max())
@@ -568,3 +574,171 @@ class MeshDistance:
         return {"cell": self.cell, "dims": list(self.dims), "cells": self.dims[0] * self.dims[1] * self.dims[2], "entries": self.entries,
                 "bytes": self.bytes, "large_faces": int(self._queue[0]), "large_max": self.large_max, "sort": self.sort,
                 "build_s": self._build[0].elapsed_time(self._build[1]) * 1e-3, "queries": self.queries, "query_s": self._seconds}
+
+
+def face_unit_normals(vertices: torch.Tensor, faces: torch.Tensor, face: torch.Tensor) -> torch.Tensor:
+    """MeshDistance.face_normals without the index: -> [N,3] float32, the unit normal of face[i] ([N] int32 on the device) of the
+    mesh, (0, 0, 0) for a face without area and for face[i] < 0 (rtgs_mesh_distance_normals)."""
+    vertices, faces, _, V, F = _check(vertices, faces)
+    if F == 0:
+        raise ValueError("rtg_slam_amd.mesh_ops: face_unit_normals needs at least one face")
+    if not torch.is_tensor(face) or not face.is_cuda:
+        raise RuntimeError("rtg_slam_amd.mesh_ops: tensors must live on a HIP device; this build has no CPU path.")
+    if face.dim() != 1 or face.dtype != torch.int32 or face.device != vertices.device:
+        raise ValueError("rtg_slam_amd.mesh_ops: face must be [N] int32 on the mesh's device")
+    face = face.detach().contiguous()
+    N = int(face.shape[0])
+    out = torch.empty(N, 3, dtype=torch.float32, device=vertices.device)
+    with torch.cuda.device(vertices.device):
+        _lib.check(_lib.load().rtgs_mesh_distance_normals(_p(vertices), V, _p(faces), F, _p(face), N, _p(out), _stream(vertices.device)),
+                   "rtgs_mesh_distance_normals")
+    return out
+
+
+def register_accumulate(points: torch.Tensor, face: torch.Tensor, d2: torch.Tensor, target: MeshDistance, center, max_d2: float,
+                        source_normals: Optional[torch.Tensor] = None, min_cos: float = 0.0) -> torch.Tensor:
+    """rtgs_mesh_register_accumulate -> out [30] float64 on the device, no synchronisation: the point-to-plane normal equations
+    of points [N,3] float32 against the faces target.query gave them (face [N] int32, d2 [N] float32), summed in the fixed order
+    of include/rtgs_slam.h, "mesh registration".  center: 3 numbers, rounded to float32; max_d2 and min_cos likewise."""
+    points = target._points(points)
+    N, dev = int(points.shape[0]), target.device
+    for name, t, shape, dt in (("face", face, (N,), torch.int32), ("d2", d2, (N,), torch.float32),
+                               ("source_normals", source_normals, (N, 3), torch.float32)):
+        if t is None and name == "source_normals":
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("rtg_slam_amd.mesh_ops: tensors must live on a HIP device; this build has no CPU path.")
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
+            raise ValueError(f"rtg_slam_amd.mesh_ops: {name} must be {list(shape)} {str(dt).split('.')[-1]} on the mesh's device")
+    if N >= 2 ** 31:
+        raise ValueError(f"rtg_slam_amd.mesh_ops: {N} points are more than the 2^31 - 1 one accumulation takes")
+    face, d2 = face.detach().contiguous(), d2.detach().contiguous()
+    sn = None if source_normals is None else source_normals.detach().contiguous()
+    c = (C.c_float * 3)(*[float(np.float32(x)) for x in center])
+    lib = _lib.load()
+    scratch = torch.empty(max(lib.rtgs_mesh_register_scratch_bytes(N) // 8, 1), dtype=torch.float64, device=dev)
+    out = torch.empty(REGISTER_OUT, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rtgs_mesh_register_accumulate(_p(points), _p(face), _p(d2), _p(sn), N, _p(target.vertices),
+                                                     int(target.vertices.shape[0]), _p(target.faces), int(target.faces.shape[0]), c,
+                                                     float(np.float32(max_d2)), float(np.float32(min_cos)), _p(scratch), _p(out),
+                                                     _stream(dev)), "rtgs_mesh_register_accumulate")
+    return out
+
+
+def _rodrigues(w):
+    theta = np.sqrt(np.dot(w, w))
+    if not theta > 0:
+        return np.eye(3)
+    k = w / theta
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(theta) * K + (1.0 - np.cos(theta)) * (K @ K)
+
+
+def _register_solve(out, rank_tol):
+    """The 30 sums -> (x, rank): A x = -b on the eigen-directions of A with lambda > rank_tol lambda_max."""
+    A = np.zeros((6, 6), np.float64)
+    A[np.triu_indices(6)] = out[:21]
+    A = A + np.triu(A, 1).T
+    b = np.asarray(out[21:27], dtype=np.float64)
+    lam, vec = np.linalg.eigh(A)
+    x, rank = np.zeros(6, np.float64), 0
+    for j in range(6):
+        if lam[j] > rank_tol * lam[5]:
+            x = x - vec[:, j] * (np.dot(vec[:, j], b) / lam[j])
+            rank += 1
+    return x, rank
+
+
+def register_to_mesh(points: torch.Tensor, target: MeshDistance, *, max_distance: float = 0.10, max_iterations: int = 30,
+                     source_normals: Optional[torch.Tensor] = None, min_cos: float = 0.0, init=None,
+                     rank_tol: float = 1e-8) -> Tuple[np.ndarray, Dict]:
+    """Rigid point-to-plane ICP of points [N,3] float32 (on the target's device) to the surface of `target` -> (T [4,4] float64
+    on the host with T p near the surface, report).  T starts at `init` (4x4) or the identity and stays float64 on the host.
+    Every iteration moves the ORIGINAL points by float32(T) (slam_ops.transform_map; source_normals [N,3] float32, if given,
+    by its rotation), queries their nearest faces, sums the normal equations of the correspondences that take part
+    (register_accumulate: d2 <= float32(max_distance)^2, a face with area, |n_source . n_face| >= min_cos) about the centre c
+    of the target's vertex box, reads the 30 sums - the iteration's one host read - and solves A x = -b through
+    numpy.linalg.eigh without the eigen-directions with lambda <= rank_tol lambda_max: what the geometry does not constrain
+    stays put.  x = (w, v) is applied as T <- Trans(c) [R(w) | v] Trans(-c) T, R the Rodrigues rotation.  It stops after an
+    update with |w| <= 1e-6 rad and |v| <= 1e-6 m ("converged"), after max_iterations updates ("max iterations"), or, without
+    an update, when fewer than 6 correspondences take part ("too few inliers").
+    report: iterations (updates applied), converged, reason, inliers (per accumulation), inlier_share (the last / N),
+    rms_plane_before / _after and rms_distance_before / _after (metres, of the first and the last accumulation: the plane
+    residuals r and the query's distances over the inliers), rank (of the last solve), rotation_deg and translation_m (of
+    T inverse(init): its angle, and how far it moves c), query_s and accumulate_s (device events, summed over the
+    accumulations).  tests/mesh_register_reference.py is the definition: every device step is matched bit for bit and the host
+    steps are the same float64 numpy operations."""
+    from . import slam_ops as so
+    if not isinstance(target, MeshDistance):
+        raise ValueError("rtg_slam_amd.mesh_ops: register_to_mesh needs a MeshDistance as its target")
+    points = target._points(points)
+    N, dev = int(points.shape[0]), target.device
+    if source_normals is not None:
+        if not torch.is_tensor(source_normals) or not source_normals.is_cuda:
+            raise RuntimeError("rtg_slam_amd.mesh_ops: tensors must live on a HIP device; this build has no CPU path.")
+        if tuple(source_normals.shape) != (N, 3) or source_normals.dtype != torch.float32 or source_normals.device != dev:
+            raise ValueError("rtg_slam_amd.mesh_ops: source_normals must be [N,3] float32, one row per point, on the mesh's device")
+        source_normals = source_normals.detach().contiguous()
+    max_iterations = int(max_iterations)
+    if not float(max_distance) > 0 or max_iterations < 1:
+        raise ValueError(f"rtg_slam_amd.mesh_ops: register_to_mesh needs max_distance > 0 and max_iterations >= 1, got "
+                         f"{max_distance} and {max_iterations}")
+    T0 = np.eye(4) if init is None else np.array(init, dtype=np.float64)
+    if T0.shape != (4, 4) or not np.isfinite(T0).all():
+        raise ValueError("rtg_slam_amd.mesh_ops: init must be a finite 4x4 matrix")
+    md = np.float32(max_distance)
+    max_d2 = md * md                                                              # float32
+    center = ((target.box[0] + target.box[1]) * 0.5).astype(np.float32)
+    c = center.astype(np.float64)
+    T = T0.copy()
+    rep: Dict = {"iterations": 0, "converged": False, "reason": "max iterations", "inliers": [], "rank": 0}
+    events: List = []
+    first = last = None
+    while True:
+        T32 = T.astype(np.float32)
+        with torch.cuda.device(dev):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            moved = so.transform_map(points, torch.from_numpy(T32))
+            normals = None
+            if source_normals is not None:
+                R32 = T32.copy()
+                R32[:3, 3] = 0.0
+                normals = so.transform_map(source_normals, torch.from_numpy(R32))
+            e[0].record()
+            d2, face = target.query(moved)
+            e[1].record()
+            sums = register_accumulate(moved, face, d2, target, center, max_d2, normals, min_cos)
+            e[2].record()
+        events.append(e)
+        out = sums.cpu().numpy()                                                  # the iteration's host read
+        count = int(out[29])
+        rep["inliers"].append(count)
+        last = out
+        first = out if first is None else first
+        if count < REGISTER_MIN_INLIERS:
+            rep["reason"] = "too few inliers"
+            break
+        x, rep["rank"] = _register_solve(out, rank_tol)
+        D = np.eye(4)
+        D[:3, :3] = _rodrigues(x[:3])
+        D[:3, 3] = (c + x[3:]) - D[:3, :3] @ c
+        T = D @ T
+        rep["iterations"] += 1
+        if np.sqrt(np.dot(x[:3], x[:3])) <= REGISTER_STOP and np.sqrt(np.dot(x[3:], x[3:])) <= REGISTER_STOP:
+            rep["converged"], rep["reason"] = True, "converged"
+            break
+        if rep["iterations"] >= max_iterations:
+            break
+    for name, o in (("before", first), ("after", last)):
+        n = o[29]
+        rep["rms_plane_" + name] = float(np.sqrt(o[27] / n)) if n else float("nan")
+        rep["rms_distance_" + name] = float(np.sqrt(o[28] / n)) if n else float("nan")
+    rep["inlier_share"] = rep["inliers"][-1] / N if N else 0.0
+    total = T @ np.linalg.inv(T0)
+    rep["rotation_deg"] = float(np.degrees(np.arccos(np.clip(0.5 * (np.trace(total[:3, :3]) - 1.0), -1.0, 1.0))))
+    rep["translation_m"] = float(np.linalg.norm(total[:3, :3] @ c + total[:3, 3] - c))
+    events[-1][2].synchronize()
+    rep["query_s"] = sum(e[0].elapsed_time(e[1]) for e in events) * 1e-3
+    rep["accumulate_s"] = sum(e[1].elapsed_time(e[2]) for e in events) * 1e-3
+    return T, rep

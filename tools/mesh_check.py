@@ -30,9 +30,14 @@
     mesh's vertices, the thing it replaces; then the quality columns of the decimation table with this ruler, two-sided: the
     result's samples to the original SURFACE and the original's samples to the result's surface, mean and maximum, for
     decimate to 25 % and 10 % and the simplify_clusters rows beside them.  A query that takes long is timed with fewer calls
-    per block (reps_per_block says how many).
+    per block (reps_per_block says how many);
+  * the registration leg (key "register"; alone with --register): mesh_ops.register_to_mesh of 1 M samples of the same two
+    meshes, moved by a known 1 degree rotation and 2 cm translation, back onto them - the whole call, its queries and its
+    accumulations per iteration, the iteration count, what is left of the known displacement, and rtgs_mesh_register_accumulate
+    alone.
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
-blocks are reported.  python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance] [OUT] [reps = 10] [blocks = 5]"""
+blocks are reported.
+python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance | --register] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -326,8 +331,60 @@ def distance_leg(dev, cam, frames, lo, hi, reps, blocks):
     return res
 
 
+def register_leg(dev, cam, frames, lo, hi, reps, blocks):
+    from rtg_slam_amd import evaluation as ev
+    res = {"timing": "one whole mesh_ops.register_to_mesh call of 1 M points per block after one warm-up call: device events around "
+                     "the call (every iteration's transform, query, accumulation, host read and solve), and the report's own "
+                     "events around the queries and the accumulations, divided by the accumulations; accumulate_alone: "
+                     "register_accumulate of the same points on a query's result, reps calls per block",
+           "known": "the samples are moved by the inverse of a 1 degree rotation about (0.4, -0.7, 0.59) and a 2 cm translation"}
+    n = 1_000_000
+    axis = np.array([0.4, -0.7, 0.59]) / np.linalg.norm([0.4, -0.7, 0.59])
+    known = np.eye(4)
+    known[:3, :3] = mesh_ops._rodrigues(axis * np.deg2rad(1.0))
+    known[:3, 3] = 0.02 * np.array([0.6, -0.5, 0.62]) / np.linalg.norm([0.6, -0.5, 0.62])
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        _fuse_all(vol, frames, cam)
+        v, f, _ = vol.extract_mesh()
+        del vol
+        torch.cuda.empty_cache()
+        md = mesh_ops.MeshDistance(v, f)
+        true = ev.sample_mesh_points(v, f, n, 0, dev).double()
+        inv = torch.from_numpy(np.linalg.inv(known)).to(dev)
+        src = (true @ inv[:3, :3].T + inv[:3, 3]).float().contiguous()
+        entry = {"V": int(v.shape[0]), "F": int(f.shape[0]), "points": n, "cell": md.report()["cell"]}
+        calls = []
+        for k in range(blocks + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            T, rep = mesh_ops.register_to_mesh(src, md)
+            b.record()
+            b.synchronize()
+            passes = len(rep["inliers"])
+            calls.append({"call_ms": a.elapsed_time(b), "query_ms_per_pass": 1e3 * rep["query_s"] / passes,
+                          "accumulate_ms_per_pass": 1e3 * rep["accumulate_s"] / passes})
+        calls = calls[1:]
+        for key in ("call_ms", "query_ms_per_pass", "accumulate_ms_per_pass"):
+            entry[key] = _summary([c[key] for c in calls], 1)
+        Tt = torch.from_numpy(T).to(dev)
+        entry["residual_displacement_m"] = float(((src.double() @ Tt[:3, :3].T + Tt[:3, 3]) - true).norm(dim=1).max())
+        entry["report"] = {k: rep[k] for k in ("iterations", "converged", "reason", "inliers", "inlier_share", "rank", "rotation_deg",
+                                               "translation_m", "rms_plane_before", "rms_plane_after", "rms_distance_before",
+                                               "rms_distance_after")}
+        d2, face = md.query(src)
+        center = (md.box[0] + md.box[1]) * 0.5
+        entry["accumulate_alone"] = blocks_ms(lambda i: mesh_ops.register_accumulate(src, face, d2, md, center, 0.01), reps, blocks)
+        entry["accumulate_alone"]["bytes_per_point"] = "12 point + 4 face + 4 d2 read, 12 face indices and 36 corner gathered"
+        res[f"room_voxel_{voxel:g}"] = entry
+        print(f"register: voxel {voxel:g} done", file=sys.stderr, flush=True)
+        del v, f, md, src, true, d2, face
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance")]
+    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance", "--register")]
     sparse_only = "--sparse-only" in sys.argv[1:]
     cleanup_only = "--cleanup" in sys.argv[1:]
     out_path = argv[0] if len(argv) > 0 else None
@@ -346,6 +403,9 @@ def main():
     lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
     if "--distance" in sys.argv[1:]:
         res["distance"] = distance_leg(dev, cam, frames, lo, hi, reps, blocks)
+        return _finish(res, out_path)
+    if "--register" in sys.argv[1:]:
+        res["register"] = register_leg(dev, cam, frames, lo, hi, reps, blocks)
         return _finish(res, out_path)
     if "--decimate" in sys.argv[1:]:
         res["decimate"] = decimate_leg(dev, cam, frames, lo, hi, blocks)
