@@ -550,6 +550,11 @@ int rtgs_mesh_render(const float* vertices, int64_t V, const int32_t* faces, int
  *   [ceil(bz/S)][ceil(by/S)][ceil(bx/S)], S = RTGS_MESH_DISTANCE_SUPER, 1 where a block of it is occupied.
  * rtgs_mesh_distance_query   points [N][3] float32 (anywhere), order: NULL, or a permutation of 0..N-1 (int64) in which the threads
  *   take the points; d2 [N] float32 and face [N] int32 are written at the points' own rows.  One launch, no host read.
+ * rtgs_mesh_distance_query_bounded  "the nearest face within max_d2, or nothing": row i is the row of rtgs_mesh_distance_query when
+ *   its d2[i] <= max_d2 (float32; equality keeps the row, a NaN drops it) and (+inf, -1) otherwise, so also for a non-finite
+ *   point.  max_d2 = +inf is the unbounded result, max_d2 = 0 keeps only exact zeros; max_d2 < 0 or NaN returns -1.  A kernel of
+ *   its own: the walk starts under the bound, so a point far from every face ends after the first rings of super blocks.
+ *   tests/mesh_distance_bounded_reference.py (nearest_within) is the definition.
  * rtgs_mesh_distance_keys    keys [N] int64: the point's cell, clamped into the grid, block-major (0 for a non-finite point).
  * rtgs_mesh_distance_normals normals [N][3] float32: n = (b - a) x (c - a) of face[i] as rtgs_mesh_vertex_normals forms it,
  *   divided by l = sqrt((x x + y y) + z z) when l > 0; (0, 0, 0) otherwise and for face[i] < 0.
@@ -568,6 +573,10 @@ int rtgs_mesh_distance_blocks(const int32_t* start, const float* origin_host, fl
 int rtgs_mesh_distance_query(const float* points, int64_t N, const int64_t* order, const float* vertices, int64_t V, const int32_t* faces,
                              int64_t F, const float* origin_host, float cell, const int32_t* dims_host, float vmax, const int32_t* start,
                              const int32_t* entries, const uint8_t* occupied, float* d2, int32_t* face, void* stream);
+int rtgs_mesh_distance_query_bounded(const float* points, int64_t N, const int64_t* order, const float* vertices, int64_t V,
+                                     const int32_t* faces, int64_t F, const float* origin_host, float cell, const int32_t* dims_host, float vmax,
+                                     const int32_t* start, const int32_t* entries, const uint8_t* occupied, float max_d2, float* d2,
+                                     int32_t* face, void* stream);
 int rtgs_mesh_distance_keys(const float* points, int64_t N, const float* origin_host, float cell, const int32_t* dims_host, int64_t* keys,
                             void* stream);
 int rtgs_mesh_distance_normals(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face, int64_t N,

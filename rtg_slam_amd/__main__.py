@@ -25,6 +25,7 @@ rendered depth, not the sensor's.  `metric --mesh-depth` renders save_model/mesh
 `mesh --cull-unseen` removes the surface no fused view could see before the mesh is written.
 `metric --mesh --surface-distance` scores save_model/mesh_tsdf.ply against the GT mesh's SURFACE by exact point-to-triangle
 distances (evaluation.eval_mesh_surface), with the normal consistency, and writes eval_metric/surface_distance_frame_F_iter_I.json.
+`--surface-max-distance D` truncates it: only the nearest face within D metres is asked for, a distance beyond D counts as D.
 `metric --align [--align-max-distance 0.10] [--align-iterations 30]` registers the scored geometry rigidly to the full GT surface
 (evaluation.align_to_gt: point-to-plane ICP on exact nearest faces), scores it again under that transform and writes the transform,
 the registration report and the unaligned and aligned figures to eval_metric/aligned_frame_F_iter_I.json: the transform measures
@@ -361,6 +362,13 @@ def cmd_metric(opts) -> int:
     if opts.surface_distance and not opts.mesh:
         log("--surface-distance needs --mesh")
         return 2
+    if opts.surface_max_distance is not None:
+        if not opts.surface_distance:
+            log("--surface-max-distance needs --surface-distance")
+            return 2
+        if not (0.03 < opts.surface_max_distance < float("inf")):        # NaN too
+            log("--surface-max-distance must be a finite number of metres above the F-score threshold 0.03")
+            return 2
     if opts.align and (not opts.align_max_distance > 0 or opts.align_iterations < 1):
         log("--align-max-distance must be > 0 (metres) and --align-iterations >= 1")
         return 2
@@ -453,8 +461,9 @@ def cmd_metric(opts) -> int:
         reports = {}
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
+        trunc = {} if opts.surface_max_distance is None else {"max_distance": opts.surface_max_distance}
         sd = evaluation.eval_mesh_surface(mv, mf, gv, gf, dist_thres=[0.03], transform=transform, sample_nums=1_000_000,
-                                          device=device, reports=reports)
+                                          device=device, reports=reports, **trunc)
         sd.update(V=int(mv.shape[0]), F=int(mf.shape[0]), V_gt=int(gv.shape[0]), F_gt=int(gf.shape[0]), mesh=mesh_path,
                   gt_mesh=info.mesh_path, gt_culled=gt_cull is not None, distance_gt=reports["gt"], distance_rec=reports["rec"],
                   seconds=time.perf_counter() - t0)
@@ -465,6 +474,8 @@ def cmd_metric(opts) -> int:
             json.dump(sd, fo, indent=1, default=float)
         log(f"surface distance: accuracy {sd['accuracy']:.4f} cm, completion {sd['completion']:.4f} cm, F1 {sd['F1 (< 0.03)']:.3f}, "
             f"normal consistency {sd['normal_consistency']:.4f} -> {sd_path}")
+        if trunc:
+            log(f"surface distance truncated at {sd['max_distance']:g} m: {sd['beyond_acc']} / {sd['beyond_comp']} samples beyond")
     if opts.align:                           # register the scored geometry to the FULL GT surface, then score it again
         from . import mesh_ops
         gv, gf = iof.load_mesh_ply(info.mesh_path)
@@ -499,7 +510,7 @@ def cmd_metric(opts) -> int:
         if opts.surface_distance:            # sd: the unaligned surface figures, written above
             sgv, sgf = gt_cull.mesh() if gt_cull is not None else (gv, gf)
             al["surface_aligned"] = evaluation.eval_mesh_surface(mv, mf, sgv, sgf, dist_thres=[0.03], transform=T_total,
-                                                                 sample_nums=1_000_000, device=device)
+                                                                 sample_nums=1_000_000, device=device, **trunc)
             al["surface_unaligned"] = {k: sd[k] for k in al["surface_aligned"]}
         al_dir = os.path.join(args.save_path, "eval_metric")
         os.makedirs(al_dir, exist_ok=True)
@@ -563,6 +574,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "point-to-triangle distances - accuracy from 1 M samples of the mesh to the GT surface, completion from 1 M "
                         "samples of the GT mesh to the mesh's surface, and the normal consistency - and write "
                         "eval_metric/surface_distance_frame_F_iter_I.json; the statis csv is what it is without the flag")
+    m.add_argument("--surface-max-distance", type=float, default=None, metavar="D",
+                   help="with --surface-distance: ask only for the nearest face within D metres (D > 0.03) - bounded time against "
+                        "an un-culled GT; a distance beyond D counts as D in accuracy and completion, P / R / F1 are unchanged, and "
+                        "the JSON gains max_distance, beyond_acc and beyond_comp (the samples beyond D)")
     m.add_argument("--align", action="store_true",
                    help="after the evaluation, register the scored geometry (the mesh samples with --mesh, else pcd_densify.ply's "
                         "points, else the Gaussian centres) rigidly to the FULL GT surface by point-to-plane ICP on exact nearest "

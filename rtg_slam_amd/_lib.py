@@ -297,6 +297,8 @@ _SIGNATURES = {
     "rtgs_mesh_distance_blocks": (C.c_int, [_P, _P, C.c_float, _P, _P, _P]),
     "rtgs_mesh_distance_query": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, _P, _P, _P,
                                            _P, _P]),
+    "rtgs_mesh_distance_query_bounded": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, _P,
+                                                   _P, C.c_float, _P, _P, _P]),
     "rtgs_mesh_distance_keys": (C.c_int, [_P, C.c_int64, _P, C.c_float, _P, _P, _P]),
     "rtgs_mesh_distance_normals": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     # mesh registration

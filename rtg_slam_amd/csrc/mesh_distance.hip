@@ -21,7 +21,7 @@
 // query      one thread per point (through `order` when the caller sorted the points by cell): Chebyshev rings of super blocks
 //            around the point's clamped cell, empty ones skipped, then per super block, per block and per cell a lower bound of
 //            the distance from the integer cell offsets; pair_d2 for the entries of the cells that pass.  See "Why the walk
-//            may stop".
+//            may stop".  query_bounded is the same walk under a caller's radius (step 5), a kernel of its own.
 // keys       the clamped cell of every point as one int64, for the caller's sort.
 // normals    the unit normal of face[i].
 //
@@ -40,6 +40,15 @@
 //  4 thr = (sqrt(best) + eta) (1 + 2^-20), thr2 = thr thr (1 + 2^-20) are rounded up past their exact values.  A ring, super block, block or
 //    cell is skipped only when lb2 > thr2: then D > sqrt(best) + eta, and by 1 the face's pair_d2 is > best.  A face whose
 //    pair_d2 is <= best is therefore never skipped: the bits and the lowest-index tie rule of the brute force are kept.
+//  5 The bounded query (rtgs_mesh_distance_query_bounded: "the nearest face within max_d2, or nothing") is the same walk with
+//    two changes: thr2 starts at cap_thr2, from cap_thr = (sqrt(max_d2) + eta) (1 + 2^-20), cap_thr2 = cap_thr cap_thr
+//    (1 + 2^-20), and a candidate is offered only when pair_d2 <= max_d2.  The chain of 4 is monotone in best, so every later
+//    thr2 is <= cap_thr2.  A face with pair_d2 <= max_d2 has by 1 a true distance D <= sqrt(max_d2) + eta, and by 3 every cell
+//    it is registered in has lb2 <= D^2 <= cap_thr2: the cap does not skip it, and a later thr2 comes from a best <= max_d2, to
+//    which 4 applies unchanged.  All faces with pair_d2 <= max_d2 therefore compete exactly as in the unbounded walk, lowest
+//    index first among equals; the faces beyond cannot win and need not be seen.  A point metres from any surface finds every
+//    bound of ring 0 and ring 1 above the cap and is done.  The unbounded query is its own instantiation (BOUNDED = false:
+//    no cap, no test), not the bounded one with max_d2 = inf.
 //
 // Index range: the caller guarantees 0 <= faces[i] < V, finite vertices with |coordinate| <= 2^20, and that the grid holds the
 // mesh with half a cell to spare (mesh_ops.MeshDistance checks all three once).  Element indices are 64-bit.
@@ -284,10 +293,12 @@ __host__ __device__ __forceinline__ void offer(Best* b, float d, uint32_t f) {
   }
 }
 
+// BOUNDED: only candidates with pair_d2 <= max_d2 are offered (step 5); max_d2 is not read otherwise
+template <bool BOUNDED>
 __host__ __device__ __forceinline__ void walk_block(const Grid& g, int BX, int BY, int BZ, int c0x, int c0y, int c0z, float px, float py, float pz,
                                            const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                            const int32_t* __restrict__ start, const int32_t* __restrict__ entries,
-                                           const uint8_t* __restrict__ occupied, Best* best) {
+                                           const uint8_t* __restrict__ occupied, float max_d2, Best* best) {
   if (!occupied[((int64_t)BZ * g.by + BY) * g.bx + BX]) return;
   const int X = BX * BLOCK, Y = BY * BLOCK, Z = BZ * BLOCK;
   {
@@ -310,7 +321,8 @@ __host__ __device__ __forceinline__ void walk_block(const Grid& g, int BX, int B
         for (int32_t j = s; j < e; ++j) {
           const uint32_t f = (uint32_t)entries[j];
           if (f == best->face) continue;                                                   // the same face from another cell
-          offer(best, pair_d2(px, py, pz, vertices, faces, (int64_t)f), f);
+          const float d = pair_d2(px, py, pz, vertices, faces, (int64_t)f);
+          if (!BOUNDED || d <= max_d2) offer(best, d, f);                                  // a NaN is not offered
         }
       }
     }
@@ -318,10 +330,11 @@ __host__ __device__ __forceinline__ void walk_block(const Grid& g, int BX, int B
 }
 
 // the blocks of one occupied super block that the bound lets through
+template <bool BOUNDED>
 __host__ __device__ __forceinline__ void walk_super(const Grid& g, int SX, int SY, int SZ, int c0x, int c0y, int c0z, float px, float py, float pz,
                                                     const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                                     const int32_t* __restrict__ start, const int32_t* __restrict__ entries,
-                                                    const uint8_t* __restrict__ occupied, Best* best) {
+                                                    const uint8_t* __restrict__ occupied, float max_d2, Best* best) {
   const int64_t nb = (int64_t)g.bx * g.by * g.bz;
   if (!occupied[nb + ((int64_t)SZ * g.sy + SY) * g.sx + SX]) return;
   constexpr int EDGE = BLOCK * SUPER;                                                      // cells
@@ -334,13 +347,16 @@ __host__ __device__ __forceinline__ void walk_super(const Grid& g, int SX, int S
   for (int BZ = SZ * SUPER; BZ < z1; ++BZ)
     for (int BY = SY * SUPER; BY < y1; ++BY)
       for (int BX = SX * SUPER; BX < x1; ++BX)
-        walk_block(g, BX, BY, BZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, best);
+        walk_block<BOUNDED>(g, BX, BY, BZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, max_d2, best);
 }
 
-// the whole query of one point -> (d2, face); (inf, all ones) for a point with a non-finite coordinate
+// the whole query of one point -> (d2, face); (inf, all ones) for a point with a non-finite coordinate and, BOUNDED, for one
+// without a face within max_d2.  max_root = sqrtf(max_d2), taken once by the host: both are the same for every point.
+template <bool BOUNDED>
 __host__ __device__ __forceinline__ Best query_point(float px, float py, float pz, const Grid& g, const float* __restrict__ vertices,
                                                      const int32_t* __restrict__ faces, const int32_t* __restrict__ start,
-                                                     const int32_t* __restrict__ entries, const uint8_t* __restrict__ occupied) {
+                                                     const int32_t* __restrict__ entries, const uint8_t* __restrict__ occupied,
+                                                     float max_d2, float max_root) {
   Best best;
   best.d2 = INFINITY;
   best.thr2 = INFINITY;
@@ -348,6 +364,10 @@ __host__ __device__ __forceinline__ Best query_point(float px, float py, float p
   best.face = 0xffffffffu;
   if (!(fabsf(px) < INFINITY && fabsf(py) < INFINITY && fabsf(pz) < INFINITY)) return best;  // NaN too
   best.eta = ETA * (fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) + 4.0f * g.vmax);
+  if (BOUNDED) {                                                                           // step 5: the point's own cap
+    const float cap_thr = (max_root + best.eta) * UP;
+    best.thr2 = (cap_thr * cap_thr) * UP;
+  }
   const int c0x = cell_of(px, g.ox, g.inv_h, g.nx, 0.0f), c0y = cell_of(py, g.oy, g.inv_h, g.ny, 0.0f),
             c0z = cell_of(pz, g.oz, g.inv_h, g.nz, 0.0f);
   constexpr int EDGE = BLOCK * SUPER;
@@ -365,10 +385,10 @@ __host__ __device__ __forceinline__ Best query_point(float px, float py, float p
       for (int SY = y0; SY <= y1; ++SY) {
         if (iabs(SZ - Cz) == K || iabs(SY - Cy) == K) {
           for (int SX = x0; SX <= x1; ++SX)
-            walk_super(g, SX, SY, SZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, &best);
+            walk_super<BOUNDED>(g, SX, SY, SZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, max_d2, &best);
         } else {                                                                           // K > 0: only the two ends of the row
-          if (Cx - K >= 0) walk_super(g, Cx - K, SY, SZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, &best);
-          if (Cx + K < g.sx) walk_super(g, Cx + K, SY, SZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, &best);
+          if (Cx - K >= 0) walk_super<BOUNDED>(g, Cx - K, SY, SZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, max_d2, &best);
+          if (Cx + K < g.sx) walk_super<BOUNDED>(g, Cx + K, SY, SZ, c0x, c0y, c0z, px, py, pz, vertices, faces, start, entries, occupied, max_d2, &best);
         }
       }
   }
@@ -384,9 +404,26 @@ __global__ void __launch_bounds__(NT) query_kernel(const float* __restrict__ poi
   if (k >= N) return;
   const int64_t i = order ? order[k] : k;
   if (i < 0 || i >= N) return;                                                             // a permutation: never
-  const Best best = query_point(points[i * 3], points[i * 3 + 1], points[i * 3 + 2], g, vertices, faces, start, entries, occupied);
+  const Best best = query_point<false>(points[i * 3], points[i * 3 + 1], points[i * 3 + 2], g, vertices, faces, start, entries, occupied,
+                                       0.0f, 0.0f);
   out_d2[i] = best.d2;
   out_face[i] = (int32_t)best.face;                                                        // all ones -> -1
+}
+
+// the bounded form: max_d2 and max_root are kernel arguments, the same for the whole launch; the cap they give is per point
+__global__ void __launch_bounds__(NT) query_bounded_kernel(const float* __restrict__ points, int64_t N, const int64_t* __restrict__ order,
+                                                           const float* __restrict__ vertices, const int32_t* __restrict__ faces, Grid g,
+                                                           const int32_t* __restrict__ start, const int32_t* __restrict__ entries,
+                                                           const uint8_t* __restrict__ occupied, float max_d2, float max_root,
+                                                           float* __restrict__ out_d2, int32_t* __restrict__ out_face) {
+  const int64_t k = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (k >= N) return;
+  const int64_t i = order ? order[k] : k;
+  if (i < 0 || i >= N) return;                                                             // a permutation: never
+  const Best best = query_point<true>(points[i * 3], points[i * 3 + 1], points[i * 3 + 2], g, vertices, faces, start, entries, occupied,
+                                      max_d2, max_root);
+  out_d2[i] = best.d2;
+  out_face[i] = (int32_t)best.face;                                                        // all ones -> -1: nothing within the bound
 }
 
 __global__ void __launch_bounds__(NT) keys_kernel(const float* __restrict__ points, int64_t N, Grid g, int64_t* __restrict__ keys) {
@@ -499,6 +536,23 @@ int rtgs_mesh_distance_query(const float* points, int64_t N, const int64_t* orde
   if (!grid_for(N, &blocks)) return -1;
   hipLaunchKernelGGL(query_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, points, N, order, vertices, faces, g, start, entries,
                      occupied, d2, face);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_mesh_distance_query_bounded(const float* points, int64_t N, const int64_t* order, const float* vertices, int64_t V,
+                                     const int32_t* faces, int64_t F, const float* origin_host, float cell, const int32_t* dims_host, float vmax,
+                                     const int32_t* start, const int32_t* entries, const uint8_t* occupied, float max_d2, float* d2,
+                                     int32_t* face, void* stream) {
+  Grid g;
+  if (N < 0 || V <= 0 || F <= 0 || F >= 0x80000000LL || !vertices || !faces || !start || !entries || !occupied) return -1;
+  if (!(max_d2 >= 0.0f)) return -1;                                                        // NaN too
+  if (!make_grid(origin_host, cell, dims_host, vmax, &g)) return -1;
+  if (N == 0) return 0;
+  if (!points || !d2 || !face) return -1;
+  unsigned blocks;
+  if (!grid_for(N, &blocks)) return -1;
+  hipLaunchKernelGGL(query_bounded_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, points, N, order, vertices, faces, g, start,
+                     entries, occupied, max_d2, sqrtf(max_d2), d2, face);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

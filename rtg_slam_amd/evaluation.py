@@ -187,19 +187,29 @@ def eval_mesh(vertices, faces, gt_points, dist_thres: Sequence[float] = (0.03,),
     return eval_pcd(sample_mesh_points(vertices, faces, sample_nums, seed, dev), gt_points, dist_thres, transform, sample_nums)
 
 
-def _surface_side(samples, own_face, own: "MeshDistance", target: "MeshDistance", thr):
+def _surface_side(samples, own_face, own: "MeshDistance", target: "MeshDistance", thr, max_distance=None):
     """One direction of eval_mesh_surface -> float64 [3 + k] on the device: nn_stats of the samples' distances to the target's
-    surface, then the sum of |n_own . n_hit| and the number of samples it runs over."""
-    d2, face, n_hit = target.query(samples, normals=True)
+    surface, then the sum of |n_own . n_hit| and the number of samples it runs over.  With max_distance a 4 + k th value
+    follows: the rows beyond the bound, whose distance counts as the bound and whose zero normal counts them out."""
+    d2, face, n_hit = target.query(samples, normals=True, max_distance=max_distance)
+    beyond = None
+    if max_distance is not None:
+        md = np.float32(max_distance)
+        beyond = face < 0
+        d2 = torch.where(beyond, torch.full_like(d2, float(md * md)), d2)       # float32 max_d2, as the query formed it
     n_own = own.face_normals(own_face)
     dot = ((n_own[:, 0] * n_hit[:, 0] + n_own[:, 1] * n_hit[:, 1]) + n_own[:, 2] * n_hit[:, 2]).abs()      # float32, step by step
     ok = (n_own != 0).any(1) & (n_hit != 0).any(1)                   # a degenerate face has the normal (0, 0, 0)
     nc = torch.stack([torch.where(ok, dot, torch.zeros_like(dot)).sum(dtype=torch.float64), ok.sum().to(torch.float64)])
-    return torch.cat([nn_stats(d2[:, None].expand(-1, 3), thr), nc])
+    out = [nn_stats(d2[:, None].expand(-1, 3), thr), nc]
+    if beyond is not None:
+        out.append(beyond.sum().to(torch.float64).reshape(1))
+    return torch.cat(out)
 
 
 def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres: Sequence[float] = (0.03,), transform=None,
-                      sample_nums: int = 1_000_000, seed: int = 0, device=None, reports: Optional[Dict] = None) -> Dict[str, float]:
+                      sample_nums: int = 1_000_000, seed: int = 0, device=None, reports: Optional[Dict] = None,
+                      max_distance: Optional[float] = None) -> Dict[str, float]:
     """The reconstruction metrics of a triangle mesh against a GT mesh with the SURFACE on the far side of every distance
     (mesh_ops.MeshDistance), so that no figure carries the sample spacing of the other mesh: accuracy and precision from
     sample_nums points drawn on the reconstruction (sample_mesh_surface, `seed`, as eval_mesh draws them; moved by `transform`
@@ -210,6 +220,10 @@ def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres
                                          float64; samples whose own or hit face has no area are counted out
         normal_samples_acc / _comp       the samples they run over
         normal_consistency               the mean of the two.
+    max_distance = D (metres, > every threshold; a ValueError otherwise) truncates: both directions ask only for the nearest face
+    within D (MeshDistance.query(max_distance=D): bounded time against an un-culled GT), a distance beyond D counts as D in
+    accuracy and completion, and the normal consistency runs over the samples within D.  P, R and F1 are exactly those of the
+    call without it.  The result then also holds max_distance, beyond_acc and beyond_comp, the samples beyond the bound.
     Meshes are arrays or device tensors.  `reports`, a dict, receives "gt" and "rec": the two MeshDistance.report()s."""
     from . import mesh_ops, slam_ops as so
     from .io_formats import sample_mesh_surface
@@ -220,6 +234,8 @@ def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres
     thres = [float(t) for t in dist_thres]
     if len(thres) > MAX_THRESHOLDS:
         raise ValueError(f"rtg_slam_amd.evaluation: at most {MAX_THRESHOLDS} thresholds")
+    if max_distance is not None and not (thres and float(max_distance) > max(thres) and math.isfinite(float(max_distance))):
+        raise ValueError(f"rtg_slam_amd.evaluation: max_distance must be finite and above every threshold {thres}, got {max_distance}")
     to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(to_np(a))).to(device=dev, dtype=dt).contiguous()
     sides = {}
@@ -233,8 +249,10 @@ def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres
     thr = torch.tensor(thres, dtype=torch.float64, device=dev)
     (rp, ro, rmd), (gp, go, gmd) = sides["rec"], sides["gt"]
     k = len(thres)
-    v = torch.cat([_surface_side(rp, ro, rmd, gmd, thr), _surface_side(gp, go, gmd, rmd, thr)]).cpu().tolist()   # the one host read
-    acc, comp = v[:3 + k], v[3 + k:]
+    w = 3 + k + (max_distance is not None)
+    v = torch.cat([_surface_side(rp, ro, rmd, gmd, thr, max_distance),
+                   _surface_side(gp, go, gmd, rmd, thr, max_distance)]).cpu().tolist()                         # the one host read
+    acc, comp = v[:w], v[w:]
     Nr, Ng = int(rp.shape[0]), int(gp.shape[0])
     res = {"accuracy": acc[0] / Nr * 100.0, "completion": comp[0] / Ng * 100.0}
     Ps = {f"P (< {t})": acc[1 + j] / Nr * 100.0 for j, t in enumerate(thres)}
@@ -250,6 +268,8 @@ def eval_mesh_surface(rec_vertices, rec_faces, gt_vertices, gt_faces, dist_thres
         res["normal_consistency_" + name] = s[1 + k] / s[2 + k] if s[2 + k] else math.nan
         res["normal_samples_" + name] = int(s[2 + k])
     res["normal_consistency"] = 0.5 * (res["normal_consistency_acc"] + res["normal_consistency_comp"])
+    if max_distance is not None:
+        res.update(max_distance=float(max_distance), beyond_acc=int(acc[3 + k]), beyond_comp=int(comp[3 + k]))
     if reports is not None:
         reports["gt"], reports["rec"] = gmd.report(), rmd.report()
     return res
@@ -263,7 +283,7 @@ def align_to_gt(rec_points, gt_vertices, gt_faces, transform=None, sample_nums: 
     sample_nums as eval_pcd subsamples them (source_normals [P,3], the points' own unit normals, follow the draw), moved by
     `transform` (4x4; the normals by its rotation) and registered from the identity; T_align is the rigid error the
     registration found, the report is register_to_mesh's.  gt_vertices / gt_faces: arrays or device tensors.  **kw goes to
-    register_to_mesh (max_distance, max_iterations, min_cos, rank_tol).  `reports`, a dict, receives "gt": the GT's
+    register_to_mesh (max_distance, max_iterations, min_cos, rank_tol, bounded_query).  `reports`, a dict, receives "gt": the GT's
     MeshDistance.report()."""
     from . import mesh_ops, slam_ops as so
     dev = _dev(rec_points)

@@ -420,6 +420,7 @@ class MeshDistance:
         md = MeshDistance(vertices, faces)
         d2, face = md.query(points)                      # [N] float32 squared distances, [N] int32 nearest faces
         d2, face, normals = md.query(points, normals=True)
+        d2, face = md.query(points, max_distance=0.1)    # the nearest face within 10 cm, or (inf, -1)
 
     d2[i] is the minimum over ALL faces of the float32 point-to-triangle chain pair_d2, face[i] the lowest face index that
     attains it, (inf, -1) for a point with a non-finite coordinate: bit for bit the brute force of
@@ -520,10 +521,21 @@ class MeshDistance:
             raise ValueError("rtg_slam_amd.mesh_ops: the points and the mesh live on different devices")
         return points.detach().contiguous()
 
-    def query(self, points: torch.Tensor, normals: bool = False):
+    def query(self, points: torch.Tensor, normals: bool = False, max_distance: Optional[float] = None):
         """-> (d2 [N] float32, face [N] int32), with normals=True also the unit normals [N,3] float32 of the hit faces
-        (face_normals): new tensors, no synchronisation.  points [N,3] float32 on the mesh's device, anywhere in space."""
+        (face_normals): new tensors, no synchronisation.  points [N,3] float32 on the mesh's device, anywhere in space.
+        max_distance (metres, > 0): "the nearest face within it, or nothing" - a row stays what it is without the bound when
+        its d2 <= max_d2 = float32(max_distance)^2 rounded to float32 (equality keeps it) and is (inf, -1), with the normal
+        (0, 0, 0), otherwise (rtgs_mesh_distance_query_bounded; tests/mesh_distance_bounded_reference.py).  A point far from
+        every face then costs a look at the super blocks around it, not its exact nearest face."""
         points = self._points(points)
+        max_d2 = None
+        if max_distance is not None:
+            md = np.float32(max_distance)
+            if not md > 0:                                                        # NaN too
+                raise ValueError(f"rtg_slam_amd.mesh_ops: max_distance must be a number > 0 or None, got {max_distance}")
+            with np.errstate(over="ignore"):
+                max_d2 = float(md * md)                                           # float32; inf for a huge bound: unbounded
         dev, lib = self.device, _lib.load()
         N, V, F = int(points.shape[0]), int(self.vertices.shape[0]), int(self.faces.shape[0])
         d2 = torch.empty(N, dtype=torch.float32, device=dev)
@@ -538,9 +550,15 @@ class MeshDistance:
                     _lib.check(lib.rtgs_mesh_distance_keys(_p(points), N, self._origin, self.cell, self._dims, _p(keys), _stream(dev)),
                                "rtgs_mesh_distance_keys")
                     order = torch.sort(keys).indices.contiguous()
-                _lib.check(lib.rtgs_mesh_distance_query(_p(points), N, _p(order), _p(self.vertices), V, _p(self.faces), F, self._origin,
-                                                        self.cell, self._dims, self.vmax, _p(self._start), _p(self._entries),
-                                                        _p(self._occupied), _p(d2), _p(face), _stream(dev)), "rtgs_mesh_distance_query")
+                if max_d2 is None:
+                    _lib.check(lib.rtgs_mesh_distance_query(_p(points), N, _p(order), _p(self.vertices), V, _p(self.faces), F, self._origin,
+                                                            self.cell, self._dims, self.vmax, _p(self._start), _p(self._entries),
+                                                            _p(self._occupied), _p(d2), _p(face), _stream(dev)), "rtgs_mesh_distance_query")
+                else:
+                    _lib.check(lib.rtgs_mesh_distance_query_bounded(_p(points), N, _p(order), _p(self.vertices), V, _p(self.faces), F,
+                                                                    self._origin, self.cell, self._dims, self.vmax, _p(self._start),
+                                                                    _p(self._entries), _p(self._occupied), max_d2, _p(d2), _p(face),
+                                                                    _stream(dev)), "rtgs_mesh_distance_query_bounded")
                 b.record()
             self._events.append((a, b))
             self.queries += 1
@@ -652,7 +670,7 @@ def _register_solve(out, rank_tol):
 
 def register_to_mesh(points: torch.Tensor, target: MeshDistance, *, max_distance: float = 0.10, max_iterations: int = 30,
                      source_normals: Optional[torch.Tensor] = None, min_cos: float = 0.0, init=None,
-                     rank_tol: float = 1e-8) -> Tuple[np.ndarray, Dict]:
+                     rank_tol: float = 1e-8, bounded_query: bool = True) -> Tuple[np.ndarray, Dict]:
     """Rigid point-to-plane ICP of points [N,3] float32 (on the target's device) to the surface of `target` -> (T [4,4] float64
     on the host with T p near the surface, report).  T starts at `init` (4x4) or the identity and stays float64 on the host.
     Every iteration moves the ORIGINAL points by float32(T) (slam_ops.transform_map; source_normals [N,3] float32, if given,
@@ -660,7 +678,10 @@ def register_to_mesh(points: torch.Tensor, target: MeshDistance, *, max_distance
     (register_accumulate: d2 <= float32(max_distance)^2, a face with area, |n_source . n_face| >= min_cos) about the centre c
     of the target's vertex box, reads the 30 sums - the iteration's one host read - and solves A x = -b through
     numpy.linalg.eigh without the eigen-directions with lambda <= rank_tol lambda_max: what the geometry does not constrain
-    stays put.  x = (w, v) is applied as T <- Trans(c) [R(w) | v] Trans(-c) T, R the Rodrigues rotation.  It stops after an
+    stays put.  bounded_query: the iteration's query is target.query(moved, max_distance=max_distance) - the accumulation's
+    own float32 gate - so that only the inliers pay for their nearest face; the rows it drops are the rows the gate drops, so
+    T, the iterations and all 30 sums are bit for bit those of bounded_query=False.  x = (w, v) is applied as
+    T <- Trans(c) [R(w) | v] Trans(-c) T, R the Rodrigues rotation.  It stops after an
     update with |w| <= 1e-6 rad and |v| <= 1e-6 m ("converged"), after max_iterations updates ("max iterations"), or, without
     an update, when fewer than 6 correspondences take part ("too few inliers").
     report: iterations (updates applied), converged, reason, inliers (per accumulation), inlier_share (the last / N),
@@ -706,7 +727,7 @@ def register_to_mesh(points: torch.Tensor, target: MeshDistance, *, max_distance
                 R32[:3, 3] = 0.0
                 normals = so.transform_map(source_normals, torch.from_numpy(R32))
             e[0].record()
-            d2, face = target.query(moved)
+            d2, face = target.query(moved, max_distance=max_distance if bounded_query else None)
             e[1].record()
             sums = register_accumulate(moved, face, d2, target, center, max_d2, normals, min_cos)
             e[2].record()

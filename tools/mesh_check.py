@@ -34,10 +34,15 @@
   * the registration leg (key "register"; alone with --register): mesh_ops.register_to_mesh of 1 M samples of the same two
     meshes, moved by a known 1 degree rotation and 2 cm translation, back onto them - the whole call, its queries and its
     accumulations per iteration, the iteration count, what is left of the known displacement, and rtgs_mesh_register_accumulate
-    alone.
+    alone;
+  * the bounded leg (key "distance_bounded"; alone with --distance-bounded): MeshDistance.query(max_distance=D) against the
+    unbounded query on the same two meshes at the default cell, sorted, in alternating blocks - 1 M points (a) sampled on the
+    mesh itself, (b) uniform in the padded box, each unbounded and at D = 0.10 and 0.03 with the share of the rows within the
+    bound - and (c) register_to_mesh of --register's case with 10 % of the samples replaced by points uniform in the box,
+    bounded_query False and True: the whole call and the query per iteration, with the check that both return the same T.
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
 blocks are reported.
-python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance | --register] [OUT] [reps = 10] [blocks = 5]"""
+python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance | --register | --distance-bounded] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -383,8 +388,109 @@ def register_leg(dev, cam, frames, lo, hi, reps, blocks):
     return res
 
 
+def _adaptive_alternating_ms(fns, reps, blocks):
+    """alternating_blocks_ms with _adaptive_ms's calls per block: every form gets its own count from one timed call after a
+    warm-up call, and all forms run 2 blocks when one call of any takes more than a second."""
+    counts, slow = {}, False
+    for name, fn in fns.items():
+        fn(0)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn(0)
+        b.record()
+        b.synchronize()
+        first = a.elapsed_time(b)
+        counts[name] = max(1, min(reps, int(500.0 / max(first, 1e-3))))
+        slow = slow or first >= 1000.0
+    out = {name: [] for name in fns}
+    for _ in range(2 if slow else blocks):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(counts[name]):
+                fn(i)
+            b.record()
+            b.synchronize()
+            out[name].append(a.elapsed_time(b) / counts[name])
+    return {name: _summary(ms, counts[name]) for name, ms in out.items()}
+
+
+BOUNDS = (0.10, 0.03)
+
+
+def bounded_leg(dev, cam, frames, lo, hi, reps, blocks):
+    from rtg_slam_amd import evaluation as ev
+    res = {"timing": "device events around whole md.query calls of 1 M points (the key kernel and torch's sort included), default "
+                     "cell, sort on; the unbounded query and the bounded one at every D in alternating blocks, the calls per block "
+                     "set per form from one timed call (2 blocks when a call takes more than a second); register: one whole "
+                     "register_to_mesh call per block after a warm-up call, bounded_query False and True alternating",
+           "points": {"self": "1 M samples of the mesh itself", "far": "1 M points uniform in the padded box",
+                      "register": "--register's 1 M moved samples, every 10th replaced by a point uniform in the padded box"},
+           "max_distance_m": list(BOUNDS)}
+    n = 1_000_000
+    axis = np.array([0.4, -0.7, 0.59]) / np.linalg.norm([0.4, -0.7, 0.59])
+    known = np.eye(4)
+    known[:3, :3] = mesh_ops._rodrigues(axis * np.deg2rad(1.0))
+    known[:3, 3] = 0.02 * np.array([0.6, -0.5, 0.62]) / np.linalg.norm([0.6, -0.5, 0.62])
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        _fuse_all(vol, frames, cam)
+        v, f, _ = vol.extract_mesh()
+        del vol
+        torch.cuda.empty_cache()
+        md = mesh_ops.MeshDistance(v, f, sort=True)
+        entry = {"V": int(v.shape[0]), "F": int(f.shape[0]), "cell": md.report()["cell"]}
+        gen = torch.Generator().manual_seed(0)
+        box_lo, box_hi = torch.tensor(lo), torch.tensor(hi)
+        uniform = (box_lo + (box_hi - box_lo) * torch.rand(n, 3, generator=gen)).to(dev).contiguous()
+        own = ev.sample_mesh_points(v, f, n, 0, dev).contiguous()
+        for name, p in (("self", own), ("far", uniform)):
+            fns = {"unbounded": lambda i, p=p: md.query(p)}
+            for D in BOUNDS:
+                fns[f"bounded_{D:g}"] = lambda i, p=p, D=D: md.query(p, max_distance=D)
+            row = _adaptive_alternating_ms(fns, reps, blocks)
+            d2u, fu = md.query(p)
+            for D in BOUNDS:
+                d2b, fb = md.query(p, max_distance=D)
+                kept = fb >= 0
+                row[f"bounded_{D:g}"]["share_within"] = float(kept.float().mean())
+                row[f"bounded_{D:g}"]["rows_within_equal_unbounded"] = bool(torch.equal(d2b[kept], d2u[kept]) and torch.equal(fb[kept], fu[kept])
+                                                                            and bool((d2u[~kept] > np.float32(D) * np.float32(D)).all()))
+            entry[name] = row
+            print(f"distance-bounded: voxel {voxel:g}, {name}: timed", file=sys.stderr, flush=True)
+        inv = torch.from_numpy(np.linalg.inv(known)).to(dev)
+        src = (own.double() @ inv[:3, :3].T + inv[:3, 3]).float().contiguous()
+        src[::10] = uniform[::10]
+        calls = {False: [], True: []}
+        last = {}
+        for k in range(blocks + 1):
+            for bounded in (False, True):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                T, rep = mesh_ops.register_to_mesh(src, md, bounded_query=bounded)
+                b.record()
+                b.synchronize()
+                passes = len(rep["inliers"])
+                calls[bounded].append({"call_ms": a.elapsed_time(b), "query_ms_per_pass": 1e3 * rep["query_s"] / passes,
+                                       "accumulate_ms_per_pass": 1e3 * rep["accumulate_s"] / passes})
+                last[bounded] = (T, rep)
+        reg = {"points": n, "max_distance": 0.10}
+        for bounded in (False, True):
+            reg["bounded_query" if bounded else "unbounded_query"] = {
+                key: _summary([c[key] for c in calls[bounded][1:]], 1) for key in ("call_ms", "query_ms_per_pass", "accumulate_ms_per_pass")}
+        reg["same_T_and_inliers"] = bool(np.array_equal(last[False][0], last[True][0]) and last[False][1]["inliers"] == last[True][1]["inliers"])
+        reg["report"] = {k: last[True][1][k] for k in ("iterations", "converged", "reason", "inliers", "inlier_share")}
+        entry["register"] = reg
+        res[f"room_voxel_{voxel:g}"] = entry
+        print(f"distance-bounded: voxel {voxel:g} done", file=sys.stderr, flush=True)
+        del v, f, md, own, uniform, src
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance", "--register")]
+    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance", "--register", "--distance-bounded")]
     sparse_only = "--sparse-only" in sys.argv[1:]
     cleanup_only = "--cleanup" in sys.argv[1:]
     out_path = argv[0] if len(argv) > 0 else None
@@ -403,6 +509,9 @@ def main():
     lo, hi = [-h - 0.1 for h in half], [h + 0.1 for h in half]
     if "--distance" in sys.argv[1:]:
         res["distance"] = distance_leg(dev, cam, frames, lo, hi, reps, blocks)
+        return _finish(res, out_path)
+    if "--distance-bounded" in sys.argv[1:]:
+        res["distance_bounded"] = bounded_leg(dev, cam, frames, lo, hi, reps, blocks)
         return _finish(res, out_path)
     if "--register" in sys.argv[1:]:
         res["register"] = register_leg(dev, cam, frames, lo, hi, reps, blocks)
