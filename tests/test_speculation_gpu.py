@@ -82,6 +82,77 @@ def test_speculative_steps_equal_plain_steps(kind):
     assert on[2]["speculative"] >= 5, on[2]        # the first call(s) build the history, the rest speculate
 
 
+class _NoGradCtx:
+    """Stands in for the autograd ctx of a forward nobody differentiates: keeps `num_rendered`, which no_grad throws away."""
+    needs_input_grad = (False,) * 10
+    save_for_backward = mark_non_differentiable = set_materialize_grads = staticmethod(lambda *a: None)
+
+
+def _bookkeeping(ctx, num_rendered):
+    st = ctx.last_stats()
+    return dict(stats={k: st[k] for k in (0, 2, 3, 5, 6, 7)}, slice=ctx.last_slice_stats(), num_rendered=int(num_rendered))
+
+
+@pytest.mark.parametrize("kind", ["plain", "declined", "slice"])
+def test_every_forward_path_leaves_the_same_statistics(kind):
+    """One scene and one view on the three host paths of the forward - classic (speculation off), speculative + verify, and
+    the `immediate` forward without a backward - leave the same `last_stats()` words 0, 2, 3, 5, 6 and 7 (instances, tiles,
+    geometry and image bytes, tile path, longest list), the same four `last_slice_stats()` words and the same
+    `num_rendered`.  Word 4, the binning bytes, is sized from the guess on the speculative paths and is left out.  The
+    steps run with a zero learning rate: the map every path renders is the same to the bit."""
+    dev = "cuda:0"
+    cam = MID
+    if kind == "plain":
+        g, _ = ru.make_scene(20_000, cam, seed=4)
+    elif kind == "declined":
+        g = synth.surface_gaussians(150_000, cam, seed=5)
+    else:
+        cam = synth.REPLICA
+        g, _ = ru.make_scene(1_200_000, cam, seed=2024)
+    pose = None if kind == "slice" else 1
+    ctx = rz.current_context()
+    opt = mo.ShardedMapOptimizer(mo.pack_from_activated({k: v.to(dev) for k, v in g.items()}), lr_col=mo.default_lr_columns() * 0.0)
+    gen = torch.Generator().manual_seed(3)
+    gt_c = torch.rand(3, cam.H, cam.W, generator=gen).to(dev)
+    gt_d = (1.0 + torch.rand(1, cam.H, cam.W, generator=gen)).to(dev)
+    _, s = ru.make_scene(8, cam, seed=1, pose_seed=pose)
+    rs = ru.hip_settings(s, dev)
+    opt.begin_local_optimization()
+    seen = {}
+    try:
+        for name, speculate, steps in (("classic", False, 3), ("speculative", True, 4)):
+            ctx.set_speculation(speculate)
+            for k in range(steps):
+                before = ctx.speculation_stats()
+                opt.step_slam(rs, gt_c, gt_d, None)
+            after = ctx.speculation_stats()
+            took = {k: after[k] - before[k] for k in after}       # the last step's
+            assert took["speculative"] == int(speculate) and took["failed"] == 0, (name, took)
+            seen[name] = _bookkeeping(ctx, opt.last_num_rendered)
+        if kind != "slice":
+            # forwards without a backward: the first one(s) learn the pass structure, then the call checks its own guess
+            gd = opt.gaussian_data()
+            gy, gx = (cam.H + 15) // 16, (cam.W + 15) // 16
+            ones = torch.ones(gy, gx, dtype=torch.int32, device=dev)
+            for k in range(3):
+                before = ctx.plain_stats()
+                nograd = _NoGradCtx()
+                with torch.no_grad():
+                    rz._RasterizeGaussians.forward(nograd, gd["xyz"], gd["opacity"], gd["shs"], gd["scales"], gd["rotations"],
+                                                   gd["normal"], ones, rs)
+            after = ctx.plain_stats()
+            assert {k: after[k] - before[k] for k in after} == dict(onepass=1, redone=0)
+            seen["immediate"] = _bookkeeping(ctx, nograd.num_rendered)
+    finally:
+        ctx.set_speculation(True)
+    print(kind, seen)
+    assert seen["classic"]["slice"]["used"] == (0 if kind == "plain" else 1), seen
+    if kind == "slice":
+        assert seen["classic"]["slice"]["tiles_left_to_pass2"] == 0 and seen["classic"]["stats"][7] == 0, seen
+    for name, got in seen.items():
+        assert got == seen["classic"], (name, seen)
+
+
 @pytest.mark.parametrize("onepass", [False, True])
 def test_a_failed_guess_changes_nothing_and_is_redone(onepass):
     cam = MID
