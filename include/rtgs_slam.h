@@ -615,6 +615,57 @@ int rtgs_mesh_register_accumulate(const float* points, const int32_t* face, cons
                                   const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float* center_host,
                                   float max_d2, float min_cos, void* scratch, double* out, void* stream);
 
+/* ---- mesh texture: a per-face texture atlas of an indexed triangle mesh, baked from colour views (no counterpart in the
+ * reference; csrc/mesh_texture.hip).  tests/mesh_texture_reference.py restates every step in numpy; the kernels match it bit for
+ * bit.  Float32 throughout, one correctly rounded operation per step, in the order written.  vertices [V][3] float32; faces [F][3]
+ * int32, the CALLER guarantees 0 <= faces[i] < V.  u.v = (ux vx + uy vy) + uz vz.
+ *
+ * rtgs_mesh_texture_levels.  A face gets a square block of s = 2^l texels a side, l in 1..max_level (max_level in
+ *   1..RTGS_MESH_TEXTURE_MAX_LEVEL): with L = max(max(|B - A|^2, |C - B|^2), |A - C|^2), d = q - p, |d|^2 = d.d, levels[f] is the
+ *   smallest l with t t >= L, t = (float)(s - 1) texel.  Without such an l: levels[f] = max_level, capped[f] = 1 (else 0).  A face
+ *   with a non-finite corner coordinate has level 1 and is not capped.  texel > 0 and finite.
+ * The CALLER lays the blocks out: faces sorted by level descending, stable in the face index (order [F] int32: the face of every
+ *   sorted slot); sorted_offset [F] int64 the exclusive prefix sum of 4^l over that order, T the sum; offset [F] int64 the same per
+ *   face.  A block's origin (x0, y0) is the Morton decode of its offset (even bits x0, odd bits y0); the atlas is Wt x Ht, both
+ *   <= RTGS_MESH_TEXTURE_MAX_SIDE: k the smallest integer with 4^k >= T, Wt = 2^k, Ht = 2^k when T > 2^(2k-1), else 2^(k-1).
+ * rtgs_mesh_texture_face_layout.  origin [F][2] int32 = (x0, y0); uv [F][3][2] float32 = the corners at texel centres,
+ *   ((x0 + 0.5) / Wt, (y0 + 0.5) / Ht), (((x0 + s) - 0.5) / Wt, .), (., ((y0 + s) - 0.5) / Ht); record [F][12] float32, 16-byte
+ *   aligned, what rtgs_mesh_texture_bake_view reads of a face: A, B - A, C - A (9 floats), then x0, y0 and l as int32 bits.
+ * rtgs_mesh_texture_texel_face.  texel_face [Ht][Wt] int32: with c the Morton code of (x, y), -1 when c >= T, else
+ *   order[the last slot whose sorted_offset <= c] (a binary search).  F >= 1.
+ * A texel's surface point: i = x - x0, j = y - y0; when i + j > s - 1, (i, j) <- (s - 1 - j, s - 1 - i) (the reflection across
+ *   the hypotenuse); a = (float)i / (float)(s - 1), b = (float)j / (float)(s - 1); P = (A + a (B - A)) + b (C - A) per component.
+ * rtgs_mesh_texture_bake_view.  record as rtgs_mesh_texture_face_layout wrote it, color [3][H][W] float32, depth [H][W] float32 (the depth map of THIS mesh at the view's pose),
+ *   w2c12_host as rtgs_visibility_add's, centre_host = the camera centre in the mesh's frame (3 floats on the HOST), acc
+ *   [Ht][Wt][4] float32, 16-byte aligned, ZEROED by the caller before the first view.  Per texel with texel_face >= 0:
+ *     1  xc, yc, zc and u, v of P: steps 1 and 3 of rtgs_visibility_add; fail unless zc > 0
+ *     2  x0 = floorf(u), y0 = floorf(v); fail unless 0 <= x0 <= W - 2 and 0 <= y0 <= H - 2 (the bilinear footprint)
+ *     3  d = depth[floorf(v + 0.5f)][floorf(u + 0.5f)]; fail unless d > 0; fail when zc - d > tolerance
+ *     4  n = (B - A) x (C - A), r = centre - P, cos2 = ((n.r) (n.r)) / ((n.n) (r.r)); fail unless cos2 >= min_cos2
+ *     5  w = cos2 / (zc zc); tx = u - x0, ty = v - y0; per channel top = c00 + tx (c10 - c00), bot = c01 + tx (c11 - c01),
+ *        val = top + ty (bot - top); acc.rgb = acc.rgb + w val, acc.w = acc.w + w
+ *   Every comparison is false for NaN.  acc[texel] has one owner: no atomics; views add up in the order of the calls.
+ * rtgs_mesh_texture_finish.  image [Ht][Wt][3] uint8, flags [Ht][Wt] uint8.  texel_face < 0: colour 0, flag 0.  acc.w > 0: colour
+ *   acc.rgb / acc.w, flag 2.  Otherwise flag 1 and the colour (cA + a (cB - cA)) + b (cC - cA) of the face's rows of colors [V][3]
+ *   float32, or 0.5 when colors is NULL.  A byte is floorf(c 255 + 0.5f) clamped by fminf(fmaxf(., 0), 255) (NaN gives 0).
+ * One launch each, no host read.  Return 0 (also, without a launch, for F == 0 in levels and face_layout), -1 on a bad argument,
+ * -2 on a launch failure. */
+#define RTGS_MESH_TEXTURE_MAX_LEVEL 6
+#define RTGS_MESH_TEXTURE_MAX_SIDE 16384
+int rtgs_mesh_texture_levels(const float* vertices, const int32_t* faces, int64_t F, float texel, int32_t max_level, int32_t* levels,
+                             int32_t* capped, void* stream);
+int rtgs_mesh_texture_face_layout(const float* vertices, const int32_t* faces, const int64_t* offset, const int32_t* levels, int64_t F,
+                                  int32_t Wt, int32_t Ht, int32_t* origin, float* uv, float* record, void* stream);
+int rtgs_mesh_texture_texel_face(const int64_t* sorted_offset, const int32_t* order, int64_t F, int64_t T, int32_t Wt, int32_t Ht,
+                                 int32_t* texel_face, void* stream);
+int rtgs_mesh_texture_bake_view(const int32_t* texel_face, int32_t Wt, int32_t Ht, const float* record, const float* color,
+                                const float* depth, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                const float* w2c12_host, const float* centre_host, float tolerance, float min_cos2, float* acc,
+                                void* stream);
+int rtgs_mesh_texture_finish(const int32_t* texel_face, int32_t Wt, int32_t Ht, const int32_t* faces, const int32_t* levels,
+                             const int32_t* origin, const float* colors, const float* acc, uint8_t* image, uint8_t* flags,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,9 @@ save_model/pcd_densify.ply exists, the reconstruction metrics are computed on th
 `mesh` selects the model file as `metric` does, fuses the map's rendered depth and colour (or, with --depth-source sensor, the
 dataset's own) over the trajectory into a TSDF volume and writes save_model/mesh_tsdf.ply and save_model/mesh_report.json
 (rtg_slam_amd.meshing); --volume sparse keeps planes only for the 8x8x8 bricks near the surface, for boxes whose dense planes
-would be refused.  `metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
+would be refused; --texture also bakes a texture atlas for the final mesh from the map rendered at the fused poses
+(meshing.texture_mesh) and writes save_model/mesh_textured.obj, mesh_textured.mtl and mesh_texture.png.
+`metric --mesh` computes the reconstruction metrics on 1 M points sampled from that mesh instead.
 `metric --cull-gt` scores them against the part of the GT mesh the evaluated frames saw (evaluation.VisibilityCull) and writes
 eval_metric/gt_mesh_culled.ply and eval_metric/gt_cull_report.json; --cull-depth mesh decides that against the GT mesh's own
 rendered depth, not the sensor's.  `metric --mesh-depth` renders save_model/mesh_tsdf.ply at every evaluated pose
@@ -37,6 +39,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import shutil
 import sys
@@ -192,6 +195,8 @@ def cmd_slam(opts) -> int:
 DENSIFY_PLY = "pcd_densify.ply"
 MESH_PLY = "mesh_tsdf.ply"
 MESH_REPORT = "mesh_report.json"
+MESH_TEXTURED_OBJ = "mesh_textured.obj"
+MESH_TEXTURE_PNG = "mesh_texture.png"
 GT_CULL_PLY = "gt_mesh_culled.ply"
 GT_CULL_REPORT = "gt_cull_report.json"
 MESH_DEPTH_REPORT = "mesh_depth_report.json"
@@ -285,6 +290,18 @@ def cmd_mesh(opts) -> int:
     if opts.decimate_max_error is not None and not (opts.decimate > 0 and opts.decimate_max_error > 0):
         log("--decimate-max-error must be > 0 and needs --decimate")
         return 2
+    texture_texel = 0.0
+    if opts.texture:
+        texture_texel = opts.voxel if opts.texture_texel is None else opts.texture_texel
+        if not (math.isfinite(texture_texel) and texture_texel > 0):
+            log(f"--texture-texel {texture_texel:g}: the texel must be finite and > 0")
+            return 2
+        if not 1 <= opts.texture_max_level <= meshing.TEXTURE_MAX_LEVEL:
+            log(f"--texture-max-level {opts.texture_max_level}: the level must lie in 1..{meshing.TEXTURE_MAX_LEVEL}")
+            return 2
+    elif opts.texture_texel is not None or opts.texture_max_level != meshing.TEXTURE_MAX_LEVEL:
+        log("--texture-texel and --texture-max-level need --texture")
+        return 2
     cleanup = opts.min_component_faces > 0 or opts.simplify > 0 or opts.normals or opts.decimate > 0
     log(f"meshing {select_ply} over {n_frames} frames ({opts.depth_source} depth, every {opts.every}, voxel {opts.voxel:g} m)")
     mapper = load_map(args, device, select_ply)
@@ -298,18 +315,29 @@ def cmd_mesh(opts) -> int:
     source = datasets.FrameSource(info, device, io_workers=opts.io_workers)
     log(f"fusing at {info.width}x{info.height} (resolution scale {info.resolution_scale:g})")
     t0 = time.perf_counter()
-    vertices, faces, colors, report, *normals = meshing.mesh_from_map(
-        mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
-        trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume,
-        min_component_faces=opts.min_component_faces, simplify_cell=opts.simplify, normals=opts.normals,
-        cull_unseen=opts.cull_unseen, cull_unseen_tolerance=opts.cull_unseen_tolerance, decimate=opts.decimate,
-        decimate_max_error=opts.decimate_max_error)
+    texture_options = {"texture_texel": texture_texel, "texture_max_level": opts.texture_max_level} if opts.texture else {}
+    try:
+        vertices, faces, colors, report, *normals = meshing.mesh_from_map(
+            mapper, info.camera(), poses, source, voxel=opts.voxel, depth_source=opts.depth_source, every=opts.every,
+            trunc=opts.trunc_voxels * opts.voxel, min_weight=opts.min_weight, args=args, device=device, volume=opts.volume,
+            min_component_faces=opts.min_component_faces, simplify_cell=opts.simplify, normals=opts.normals,
+            cull_unseen=opts.cull_unseen, cull_unseen_tolerance=opts.cull_unseen_tolerance, decimate=opts.decimate,
+            decimate_max_error=opts.decimate_max_error, **texture_options)
+    except ValueError as e:
+        if not (opts.texture and "atlas" in str(e)):
+            raise
+        log(f"--texture: {e}")
+        return 2
+    texture = normals.pop() if opts.texture else None
     report["total_s"] = time.perf_counter() - t0
     path = os.path.join(model_base, MESH_PLY)
     t0 = time.perf_counter()
     iof.save_mesh_ply(path, vertices, faces, colors, *normals)
     report["write_s"] = time.perf_counter() - t0
     report["model"] = select_ply
+    if texture is not None:
+        obj = os.path.join(model_base, MESH_TEXTURED_OBJ)
+        iof.save_textured_obj(obj, vertices, faces, texture["uv"], texture["image"], *normals, image_name=MESH_TEXTURE_PNG)
     with open(os.path.join(model_base, MESH_REPORT), "w") as f:
         json.dump(report, f, indent=1, default=float)
     log(f"mesh: {report['V']} vertices, {report['F']} faces from {report['frames_fused']} frames into a "
@@ -329,6 +357,10 @@ def cmd_mesh(opts) -> int:
             f"{', error <= %g m' % report['decimate_max_error'] if report['decimate_max_error'] is not None else ''}); "
             f"{report['decimate_collapses']} collapses in {report['decimate_rounds']} rounds, target "
             f"{'reached' if report['decimate_target_reached'] else 'NOT reached'}: {report['decimate_s']:.3f} s")
+    if texture is not None:
+        stats = texture["stats"]
+        log(f"texture: {stats['size'][0]} x {stats['size'][1]}, {100 * stats['fill']:.1f} % filled, {100 * stats['seen_share']:.1f} % of "
+            f"the assigned texels seen by {stats['views']} views -> {obj}")
     if opts.volume == "sparse":
         log(f"sparse volume: {report['bricks']} bricks, {100 * report['brick_share']:.2f} % of the grid's, "
             f"{report['pool_bytes'] / 2 ** 20:.1f} MiB of pool where the dense planes would take {report['dense_bytes'] / 2 ** 20:.1f} MiB")
@@ -617,6 +649,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "fused pose and its vertices are tested against that depth")
     t.add_argument("--cull-unseen-tolerance", type=float, default=None, metavar="T",
                    help="metres a vertex may lie behind the rendered depth and still count as seen (default: the voxel)")
+    t.add_argument("--texture", action="store_true",
+                   help="after everything else, bake a texture atlas for the final mesh from the map rendered at the fused poses and "
+                        "write save_model/mesh_textured.obj, mesh_textured.mtl and mesh_texture.png; mesh_tsdf.ply is unchanged")
+    t.add_argument("--texture-texel", type=float, default=None, metavar="T",
+                   help="with --texture: the edge of a texel on the surface in metres (default: the voxel)")
+    t.add_argument("--texture-max-level", type=int, default=6, metavar="L",
+                   help="with --texture: a face's block is at most 2^L texels wide, L in 1..6 (default 6)")
     t.add_argument("--device", default="cuda:0")
     t.add_argument("--io-workers", type=int, default=None)
     t.add_argument("--resolution-scale", type=float, default=None,

@@ -305,6 +305,13 @@ _SIGNATURES = {
     "rtgs_mesh_register_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "rtgs_mesh_register_accumulate": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_float, C.c_float, _P, _P,
                                                 _P]),
+    # mesh texture
+    "rtgs_mesh_texture_levels": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P, _P]),
+    "rtgs_mesh_texture_face_layout": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "rtgs_mesh_texture_texel_face": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    "rtgs_mesh_texture_bake_view": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                              C.c_float, C.c_float, _P, _P, C.c_float, C.c_float, _P, _P]),
+    "rtgs_mesh_texture_finish": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -384,6 +384,88 @@ def save_mesh_ply(path: str, vertices, faces, colors=None, normals=None) -> None
         out.write(ft.tobytes())
 
 
+def save_textured_obj(path: str, vertices, faces, uv, image, normals=None, image_name: Optional[str] = None) -> None:
+    """A textured triangle mesh as Wavefront OBJ: `path` (X.obj), X.mtl beside it and the texture as a PNG (image_name, in
+    the OBJ's directory; default X.png), written through PIL.  vertices [V,3], faces [F,3], uv [F,3,2] (three texture
+    coordinates per face, x right and y DOWN in 0..1, as meshing.texture_mesh gives them), image [Ht,Wt,3] uint8, normals [V,3]
+    or None.  The file holds `v` (and `vn`), three `vt` per face with v = 1 - y (OBJ's origin is the lower left corner), and
+    `f a/ta b/tb c/tc` (`a/ta/a` with normals), under `mtllib` and `usemtl`.  Floats are written so that load_textured_obj
+    returns equal arrays."""
+    from PIL import Image
+    to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    v = np.ascontiguousarray(to_np(vertices), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(to_np(faces)).astype(np.int64).reshape(-1, 3)
+    t = np.ascontiguousarray(to_np(uv), dtype=np.float32).reshape(-1, 3, 2)
+    img = np.ascontiguousarray(to_np(image))
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"save_textured_obj: face indices must lie in 0..{v.shape[0] - 1}")
+    if t.shape[0] != f.shape[0]:
+        raise ValueError(f"save_textured_obj: {t.shape[0]} rows of texture coordinates for {f.shape[0]} faces")
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("save_textured_obj: the image must be [Ht,Wt,3] uint8")
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    image_name = name + ".png" if image_name is None else image_name
+    lines = [f"mtllib {name}.mtl", "usemtl textured"]
+    lines += ["v %.9g %.9g %.9g" % tuple(r) for r in v.tolist()]
+    if normals is not None:
+        nrm = np.ascontiguousarray(to_np(normals), dtype=np.float32).reshape(-1, 3)
+        if nrm.shape[0] != v.shape[0]:
+            raise ValueError(f"save_textured_obj: {nrm.shape[0]} normals for {v.shape[0]} vertices")
+        lines += ["vn %.9g %.9g %.9g" % tuple(r) for r in nrm.tolist()]
+    t64 = t.astype(np.float64).reshape(-1, 2)
+    lines += [f"vt {x!r} {1.0 - y!r}" for x, y in t64.tolist()]                  # 1 - y is exact in float64 for a float32 y >= 2^-29
+    corner = "{0}/{1}/{0}" if normals is not None else "{0}/{1}"
+    for i, (a, b, c) in enumerate((f + 1).tolist()):
+        lines.append("f " + " ".join(corner.format(p, 3 * i + k + 1) for k, p in enumerate((a, b, c))))
+    with open(path, "w") as out:
+        out.write("\n".join(lines) + "\n")
+    with open(stem + ".mtl", "w") as out:
+        out.write(f"newmtl textured\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {image_name}\n")
+    Image.fromarray(img).save(os.path.join(os.path.dirname(path), image_name))
+
+
+def load_textured_obj(path: str):
+    """What save_textured_obj wrote -> (vertices float32 [V,3], faces int32 [F,3], uv float32 [F,3,2] with y down, image uint8
+    [Ht,Wt,3] from the material's map_Kd).  Triangles with `v/vt` or `v/vt/vn` corners only."""
+    from PIL import Image
+    v, vt, fv, ft, mtl = [], [], [], [], None
+    with open(path) as src:
+        for line in src:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "v":
+                v.append([float(x) for x in w[1:4]])
+            elif w[0] == "vt":
+                vt.append((float(w[1]), 1.0 - float(w[2])))
+            elif w[0] == "f":
+                if len(w) != 4:
+                    raise ValueError(f"{path}: only triangles are read, found a face of {len(w) - 1} corners")
+                c = [p.split("/") for p in w[1:]]
+                if any(len(p) < 2 or not p[1] for p in c):
+                    raise ValueError(f"{path}: a face corner without a texture coordinate")
+                fv.append([int(p[0]) - 1 for p in c])
+                ft.append([int(p[1]) - 1 for p in c])
+            elif w[0] == "mtllib":
+                mtl = line.split(None, 1)[1].strip()
+    if mtl is None:
+        raise ValueError(f"{path}: no mtllib")
+    base = os.path.dirname(path)
+    tex = None
+    with open(os.path.join(base, mtl)) as src:
+        for line in src:
+            if line.split()[:1] == ["map_Kd"]:
+                tex = line.split(None, 1)[1].strip()
+    if tex is None:
+        raise ValueError(f"{os.path.join(base, mtl)}: no map_Kd")
+    image = np.asarray(Image.open(os.path.join(base, tex)).convert("RGB"), dtype=np.uint8)
+    vt = np.asarray(vt, dtype=np.float64).reshape(-1, 2)
+    ft = np.asarray(ft, dtype=np.int64).reshape(-1, 3)
+    return (np.asarray(v, dtype=np.float32).reshape(-1, 3), np.asarray(fv, dtype=np.int32).reshape(-1, 3),
+            vt[ft].astype(np.float32).reshape(-1, 3, 2), image)
+
+
 def sample_mesh_surface(vertices, faces, n: int, seed: int = 0):
     """n points uniformly on the surface (trimesh.sample.sample_surface, which eval_pcd applies to the GT mesh): a face with
     probability proportional to its area, then a uniform point of it (barycentric u, v in the unit square, folded into the

@@ -5,9 +5,10 @@ depth rendered from the map (or the sensor's own), fused into a truncated signed
     TsdfVolume        a dense axis-aligned grid (tsdf, weight, rgb planes, float32, x fastest) with integrate / extract_mesh
     SparseTsdfVolume  the same virtual grid with planes only for the 8 x 8 x 8 bricks near an observed surface
     mesh_from_map     walk a trajectory, fuse every `every`-th frame's rendered or sensor depth and colour, extract the mesh
+    texture_mesh      a per-face texture atlas of a mesh baked from colour views (TextureBaker; csrc/mesh_texture.hip)
 
 The per-voxel rule and the extraction are restated in numpy in tests/tsdf_reference.py, the brick allocation in
-tests/tsdf_sparse_reference.py; the kernels match both bit for bit.
+tests/tsdf_sparse_reference.py, the texture bake in tests/mesh_texture_reference.py; the kernels match all three bit for bit.
 There is no CPU path."""
 from __future__ import annotations
 
@@ -440,12 +441,229 @@ def cull_unseen(vertices, faces, colors, cam, poses, tolerance: float, transform
 _cull_unseen = cull_unseen                        # mesh_from_map has a flag of that name
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# texture: a per-face atlas baked from colour views
+# ---------------------------------------------------------------------------------------------------------------------
+
+TEXTURE_MAX_LEVEL = 6                 # RTGS_MESH_TEXTURE_MAX_LEVEL: blocks of 2 .. 64 texels a side
+TEXTURE_MAX_SIDE = 16384              # RTGS_MESH_TEXTURE_MAX_SIDE
+
+
+def texture_atlas_size(T: int) -> Tuple[int, int]:
+    """(Wt, Ht) of an atlas of T block texels: k the smallest integer with 4^k >= T, Wt = 2^k, Ht = 2^k when T > 2^(2k-1), else
+    2^(k-1) (Morton codes below 2^(2k-1) have y < 2^(k-1)).  T = 0 gives (1, 1)."""
+    T = int(T)
+    if T <= 0:
+        return 1, 1
+    k = 0
+    while 4 ** k < T:
+        k += 1
+    return 1 << k, (1 << k) if 2 * T > 4 ** k else (1 << k) >> 1
+
+
+class TextureBaker:
+    """The texture atlas of a mesh and its bake (include/rtgs_slam.h, "mesh texture"; bit for bit
+    tests/mesh_texture_reference.py).  Every face owns a square block of 2^l texels a side, l in 1..max_level the smallest
+    level at which (2^l - 1) texels span its longest edge; the blocks are packed by Morton code in descending size, so they are
+    aligned, disjoint and gap-free; the upper half of a block mirrors the triangle across its hypotenuse.
+
+        baker = TextureBaker(vertices, faces, cam, texel=0.01, tolerance=0.02)
+        for colour, c2w in views: baker.add(colour, c2w)          # renders the mesh's depth at c2w, bakes the view
+        image, flags = baker.finish(colors)
+
+    levels, capped [F] int32, offset [F] int64, origin [F,2] int32, uv [F,3,2] float32, texel_face [Ht,Wt] int32 and acc
+    [Ht,Wt,4] float32 (w r, w g, w b, w) are device tensors; size = (Wt, Ht).  An atlas wider than 16384 raises ValueError.
+    With F = 0 there is nothing to bake: size is (1, 1) and finish gives one black texel.  There is no CPU path."""
+
+    def __init__(self, vertices, faces, cam, *, texel: float, tolerance: float, max_level: int = TEXTURE_MAX_LEVEL,
+                 min_cos: float = 0.2, transform=None, near: Optional[float] = None):
+        from . import evaluation
+        texel, tolerance, min_cos, max_level = float(texel), float(tolerance), float(min_cos), int(max_level)
+        if not (math.isfinite(texel) and texel > 0):
+            raise ValueError(f"rtg_slam_amd.meshing: the texel must be finite and > 0, got {texel:g}")
+        if not (math.isfinite(tolerance) and tolerance > 0):
+            raise ValueError(f"rtg_slam_amd.meshing: the texture tolerance must be finite and > 0, got {tolerance:g}")
+        if not 1 <= max_level <= TEXTURE_MAX_LEVEL:
+            raise ValueError(f"rtg_slam_amd.meshing: the texture's max_level must lie in 1..{TEXTURE_MAX_LEVEL}, got {max_level}")
+        if not 0 <= min_cos <= 1:
+            raise ValueError(f"rtg_slam_amd.meshing: min_cos must lie in 0..1, got {min_cos:g}")
+        kw = {} if near is None else {"near": near}
+        self.renderer = evaluation.MeshRenderer(vertices, faces, cam, transform=transform, **kw)
+        self.device = dev = self.renderer.device
+        self.vertices, self.faces, self.cam = self.renderer.vertices, self.renderer.faces, cam
+        self.texel = float(np.float32(texel))
+        self.tolerance = float(np.float32(tolerance))
+        self.max_level = max_level
+        self.min_cos2 = float(np.float32(min_cos) * np.float32(min_cos))
+        self.views = 0
+        self._events = []
+        self._seconds = 0.0
+        F = int(self.faces.shape[0])
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        with torch.cuda.device(dev):
+            t0.record()
+            self.levels, self.capped = self._levels(self.texel)
+            order = torch.sort(self.levels, descending=True, stable=True).indices
+            size = torch.ones(F, dtype=torch.int64, device=dev) << (2 * self.levels[order].to(torch.int64))
+            sorted_offset = torch.cumsum(size, 0) - size
+            self.T = int(size.sum()) if F else 0
+            Wt, Ht = texture_atlas_size(self.T)
+            if Wt > TEXTURE_MAX_SIDE:
+                raise ValueError(f"rtg_slam_amd.meshing: at a texel of {self.texel:g} m the blocks hold T = {self.T} texels, more than "
+                                 f"a {TEXTURE_MAX_SIDE} x {TEXTURE_MAX_SIDE} atlas; {self._smallest_texel()}")
+            self.size = (Wt, Ht)
+            self.offset = torch.empty(F, dtype=torch.int64, device=dev)
+            self.offset[order] = sorted_offset
+            self.origin = torch.empty(F, 2, dtype=torch.int32, device=dev)
+            self.uv = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+            self._record = torch.empty(F, 12, dtype=torch.float32, device=dev)       # per face: A, B - A, C - A, x0, y0, level
+            self.texel_face = torch.full((Ht, Wt), -1, dtype=torch.int32, device=dev)
+            self.acc = torch.zeros(Ht, Wt, 4, dtype=torch.float32, device=dev)
+            if F:
+                lib = _lib.load()
+                order32 = order.to(torch.int32).contiguous()
+                _lib.check(lib.rtgs_mesh_texture_face_layout(_p(self.vertices), _p(self.faces), _p(self.offset), _p(self.levels), F, Wt,
+                                                             Ht, _p(self.origin), _p(self.uv), _p(self._record), _stream(dev)),
+                           "rtgs_mesh_texture_face_layout")
+                _lib.check(lib.rtgs_mesh_texture_texel_face(_p(sorted_offset), _p(order32), F, self.T, Wt, Ht, _p(self.texel_face),
+                                                            _stream(dev)), "rtgs_mesh_texture_texel_face")
+            t1.record()
+        t1.synchronize()
+        self.layout_s = t0.elapsed_time(t1) * 1e-3
+
+    def _levels(self, texel: float):
+        F, dev = int(self.faces.shape[0]), self.device
+        levels = torch.empty(F, dtype=torch.int32, device=dev)
+        capped = torch.empty(F, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().rtgs_mesh_texture_levels(_p(self.vertices), _p(self.faces), F, texel, self.max_level, _p(levels),
+                                                            _p(capped), _stream(dev)), "rtgs_mesh_texture_levels")
+        return levels, capped
+
+    def _smallest_texel(self) -> str:
+        """The words of the refusal: the smallest texel whose blocks fit, by bisection on the levels kernel (T falls as the
+        texel grows), rounded up to three digits."""
+        def fits(t):
+            levels = self._levels(t)[0].to(torch.int64)
+            return texture_atlas_size(int((torch.ones_like(levels) << (2 * levels)).sum()))[0] <= TEXTURE_MAX_SIDE
+        lo = hi = self.texel
+        for _ in range(64):
+            hi *= 2
+            if fits(float(np.float32(hi))):
+                break
+            lo = hi
+        else:
+            return "no texel fits this many faces"
+        for _ in range(16):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (lo, mid) if fits(float(np.float32(mid))) else (mid, hi)
+        digits = 2 - int(math.floor(math.log10(hi)))
+        return f"the smallest texel that fits is {math.ceil(hi * 10 ** digits) / 10 ** digits:g} m"
+
+    def add(self, color: torch.Tensor, c2w) -> None:
+        """One view: color [3,H,W] float on the device at the camera's size, c2w its pose (`transform @ c2w` is the camera in
+        the mesh's frame).  The mesh's depth is rendered at that pose and the view is added to acc.  No synchronisation."""
+        c2w = _host_pose(c2w)
+        depth = self.renderer.render(c2w)[0] if int(self.faces.shape[0]) else None
+        self.bake(color, depth, c2w)
+
+    def bake(self, color: torch.Tensor, depth: Optional[torch.Tensor], c2w) -> None:
+        """add() with the depth map given: depth [H,W] float32 on the device, the mesh as c2w sees it (renderer.render)."""
+        if not torch.is_tensor(color) or not color.is_cuda or (depth is not None and not depth.is_cuda):
+            raise RuntimeError("rtg_slam_amd.meshing: tensors must live on a HIP device; this build has no CPU path.")
+        H, W = int(self.cam.H), int(self.cam.W)
+        if tuple(color.shape) != (3, H, W):
+            raise ValueError(f"rtg_slam_amd.meshing: a view's colour must be [3,{H},{W}], got {tuple(color.shape)}")
+        if color.device != self.device:
+            raise ValueError("rtg_slam_amd.meshing: the view and the mesh live on different devices")
+        c2w = _host_pose(c2w)
+        self.views += 1
+        if int(self.faces.shape[0]) == 0:
+            return
+        if tuple(depth.shape) != (H, W) or depth.dtype != torch.float32 or not depth.is_contiguous() or depth.device != self.device:
+            raise ValueError(f"rtg_slam_amd.meshing: a view's depth must be a contiguous [{H},{W}] float32 tensor on the mesh's device")
+        pose = self.renderer.transform @ c2w
+        w2c = np.linalg.inv(pose).astype(np.float32)
+        m = (C.c_float * 12)(*np.ascontiguousarray(w2c.reshape(-1)[:12]).tolist())
+        o = (C.c_float * 3)(*pose[:3, 3].astype(np.float32).tolist())
+        fx, fy, cx, cy = (float(np.float32(k)) for k in (self.cam.fx, self.cam.fy, self.cam.cx, self.cam.cy))
+        color = color.detach().to(torch.float32).contiguous()
+        Wt, Ht = self.size
+        with torch.cuda.device(self.device):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            rc = _lib.load().rtgs_mesh_texture_bake_view(_p(self.texel_face), Wt, Ht, _p(self._record), _p(color), _p(depth), H, W, fx,
+                                                         fy, cx, cy, m, o, self.tolerance, self.min_cos2, _p(self.acc),
+                                                         _stream(self.device))
+            b.record()
+        _lib.check(rc, "rtgs_mesh_texture_bake_view")
+        self._events.append((a, b))
+
+    @property
+    def bake_seconds(self) -> float:
+        """The device time of the bake launches so far (events, read here: synchronises on the last one)."""
+        for a, b in self._events:
+            b.synchronize()
+            self._seconds += a.elapsed_time(b) * 1e-3
+        self._events = []
+        return self._seconds
+
+    def finish(self, colors=None):
+        """-> (image [Ht,Wt,3] uint8, flags [Ht,Wt] uint8: 0 unassigned, 1 assigned but seen by no view, 2 seen).  A texel no
+        view saw takes the blend of its face's vertex colours (colors [V,3] in 0..1), 0.5 grey without them."""
+        Wt, Ht = self.size
+        dev = self.device
+        image = torch.zeros(Ht, Wt, 3, dtype=torch.uint8, device=dev)
+        flags = torch.zeros(Ht, Wt, dtype=torch.uint8, device=dev)
+        if int(self.faces.shape[0]) == 0:
+            return image, flags
+        if colors is not None:
+            if torch.is_tensor(colors) and not colors.is_cuda:
+                raise RuntimeError("rtg_slam_amd.meshing: tensors must live on a HIP device; this build has no CPU path.")
+            colors = torch.as_tensor(colors).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+            if colors.shape[0] != self.vertices.shape[0]:
+                raise ValueError(f"rtg_slam_amd.meshing: {colors.shape[0]} colours for {self.vertices.shape[0]} vertices")
+        with torch.cuda.device(dev):
+            rc = _lib.load().rtgs_mesh_texture_finish(_p(self.texel_face), Wt, Ht, _p(self.faces), _p(self.levels), _p(self.origin),
+                                                      C.c_void_p(0) if colors is None else _p(colors), _p(self.acc), _p(image),
+                                                      _p(flags), _stream(dev))
+        _lib.check(rc, "rtgs_mesh_texture_finish")
+        return image, flags
+
+
+def texture_mesh(vertices, faces, colors, cam, views, *, texel: float, tolerance: float, max_level: int = TEXTURE_MAX_LEVEL,
+                 min_cos: float = 0.2, transform=None, near: Optional[float] = None):
+    """Bake a texture for a mesh -> (image [Ht,Wt,3] uint8, uv [F,3,2] float32, stats), device tensors (TextureBaker has the
+    rules).  views: an iterable of (colour [3,H,W] float device tensor, c2w); they are baked in the order given, one launch
+    each after a render of the mesh's own depth, so the result is reproducible.  A texel takes part in a view when it is in
+    front of the camera, its bilinear footprint lies in the image, the mesh's depth at its pixel is valid and not more than
+    `tolerance` metres in front of it, and the squared cosine between its face and the ray is at least min_cos^2; the weight
+    is cos^2 / z^2.  uv holds three texture coordinates per face, x right and y DOWN, in 0..1 of the image.  stats: "size" (Wt,
+    Ht), "texels_assigned", "fill" (assigned / atlas), "texels_seen", "seen_share" (seen / assigned), "views", "faces_capped"
+    (faces longer than (2^max_level - 1) texels, stretched), "levels" (faces per level, index 0 = level 1), "layout_s",
+    "render_s" and "bake_s" (device time).  F = 0 gives a 1 x 1 black image."""
+    baker = TextureBaker(vertices, faces, cam, texel=texel, tolerance=tolerance, max_level=max_level, min_cos=min_cos,
+                         transform=transform, near=near)
+    for color, c2w in views:
+        baker.add(color, c2w)
+    image, flags = baker.finish(colors)
+    Wt, Ht = baker.size
+    assigned, seen = int((flags > 0).sum()), int((flags == 2).sum())
+    hist = torch.bincount(baker.levels.to(torch.int64), minlength=baker.max_level + 1)[1:baker.max_level + 1].tolist()
+    stats = {"size": [Wt, Ht], "texels_assigned": assigned, "fill": assigned / (Wt * Ht), "texels_seen": seen,
+             "seen_share": seen / assigned if assigned else 0.0, "views": baker.views, "faces_capped": int(baker.capped.sum()),
+             "levels": hist, "layout_s": baker.layout_s, "render_s": baker.renderer.seconds, "bake_s": baker.bake_seconds}
+    return image, baker.uv, stats
+
+
 def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *, voxel: float = 0.01, depth_source: str = "render",
                   every: int = 1, bounds=None, trunc: Optional[float] = None, max_weight: float = 64, min_weight: float = 1,
                   args=None, device=None, max_bytes: int = MAX_BYTES, volume: str = "dense", min_component_faces: int = 0,
                   simplify_cell: float = 0.0, normals: bool = False, cull_unseen: bool = False,
                   cull_unseen_tolerance: Optional[float] = None, decimate: float = 0.0,
-                  decimate_max_error: Optional[float] = None):
+                  decimate_max_error: Optional[float] = None, texture_texel: float = 0.0,
+                  texture_tolerance: Optional[float] = None, texture_max_level: int = TEXTURE_MAX_LEVEL):
     """Fuse a trajectory into a TsdfVolume (volume "dense") or a SparseTsdfVolume ("sparse") and extract its mesh ->
     (vertices, faces, colors, report).
 
@@ -474,7 +692,14 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
     cull_unseen=True removes, after the extraction and before the clean-up, the surface no fused view could see (cull_unseen
     below, at the fused poses, cull_unseen_tolerance metres, default the voxel): the report's V and F are the counts after it
     and it gains "cull_unseen" (the tolerance), "F_unseen_removed", "V_unseen_removed", "cull_render_s" and, as with the
-    clean-up, "V_raw" and "F_raw": the extracted counts."""
+    clean-up, "V_raw" and "F_raw": the extracted counts.
+
+    texture_texel > 0 (metres) textures the FINAL mesh - after the cull, the clean-up, the decimation and the normals - with
+    texture_mesh: the views are the map rendered again at the fused poses by the same evaluation renderer under no_grad (the
+    sensor's colour is not used; call texture_mesh with views of your own for that), texture_tolerance defaults to the voxel.
+    The result then gains a LAST element, the dict {"image", "uv", "stats"} of texture_mesh, and the report "texture_texel",
+    "texture_size", "texture_fill", "texture_seen_share", "texture_views", "texture_faces_capped" and "texture_s".  With
+    texture_texel = 0 the result and the report are what they are without the option."""
     from .mapping import Frame
     from .render import Renderer
     if volume not in ("dense", "sparse"):
@@ -494,6 +719,11 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         raise ValueError(f"rtg_slam_amd.meshing: decimate is the share of faces to keep, 0 (off) <= decimate < 1, got {decimate:g}")
     if decimate_max_error is not None and not (decimate > 0 and float(decimate_max_error) > 0):
         raise ValueError("rtg_slam_amd.meshing: decimate_max_error must be > 0 and needs decimate > 0")
+    texture_texel = float(texture_texel)
+    if not (math.isfinite(texture_texel) and texture_texel >= 0):
+        raise ValueError(f"rtg_slam_amd.meshing: texture_texel must be finite and >= 0 (0: off), got {texture_texel:g}")
+    if not 1 <= int(texture_max_level) <= TEXTURE_MAX_LEVEL:
+        raise ValueError(f"rtg_slam_amd.meshing: texture_max_level must lie in 1..{TEXTURE_MAX_LEVEL}, got {texture_max_level}")
     every = max(1, int(every))
     trunc = 4 * float(voxel) if trunc is None else float(trunc)
     if device is None:
@@ -550,6 +780,7 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
                        "cull_unseen": stats["tolerance"],
                        "F_unseen_removed": f_raw - int(faces.shape[0]), "V_unseen_removed": v_raw - int(vertices.shape[0]),
                        "cull_render_s": stats["render_s"]})
+    nrm = None
     if min_component_faces > 0 or simplify_cell > 0 or normals or decimate > 0:
         from . import mesh_ops
         t0 = time.perf_counter()
@@ -573,6 +804,28 @@ def mesh_from_map(mapper, cam, poses=None, stream: Optional[Iterable] = None, *,
         torch.cuda.synchronize(device)
         report.update({"V_raw": v_raw, "F_raw": f_raw, "V": int(vertices.shape[0]), "F": int(faces.shape[0]), **stats,
                        "simplify_cell": simplify_cell, "normals": normals, "cleanup_s": time.perf_counter() - t0, **extra})
-        if normals:
-            return vertices, faces, colors, report, nrm
-    return vertices, faces, colors, report
+    result = (vertices, faces, colors, report) + ((nrm,) if normals else ())
+    if texture_texel > 0:
+        t0 = time.perf_counter()
+        if renderer is None:
+            args = mapper.args if args is None else args
+            eval_args = SimpleNamespace(**vars(args))
+            eval_args.renderer_opaque_threshold = float(getattr(args, "renderer_opaque_threshold_eval", 0.5))
+            renderer = Renderer(eval_args)
+        params = {k: v.detach() for k, v in mapper.global_params.items()}
+
+        def views():
+            for i, c2w in enumerate(fused_poses):
+                with torch.no_grad():
+                    out = renderer.render(Frame(cam, c2w, device, uid=i), params)
+                yield out["render"], c2w
+
+        image, uv, stats = texture_mesh(vertices, faces, colors, cam, views(), texel=texture_texel,
+                                        tolerance=float(vol.voxel if texture_tolerance is None else texture_tolerance),
+                                        max_level=int(texture_max_level))
+        torch.cuda.synchronize(device)
+        report.update({"texture_texel": texture_texel, "texture_size": stats["size"], "texture_fill": stats["fill"],
+                       "texture_seen_share": stats["seen_share"], "texture_views": stats["views"],
+                       "texture_faces_capped": stats["faces_capped"], "texture_s": time.perf_counter() - t0})
+        result += ({"image": image, "uv": uv, "stats": stats},)
+    return result

@@ -39,10 +39,16 @@
     unbounded query on the same two meshes at the default cell, sorted, in alternating blocks - 1 M points (a) sampled on the
     mesh itself, (b) uniform in the padded box, each unbounded and at D = 0.10 and 0.03 with the share of the rows within the
     bound - and (c) register_to_mesh of --register's case with 10 % of the samples replaced by points uniform in the box,
-    bounded_query False and True: the whole call and the query per iteration, with the check that both return the same T.
+    bounded_query False and True: the whole call and the query per iteration, with the check that both return the same T;
+  * the texture leg (key "texture"; alone with --texture): meshing.TextureBaker on the same two meshes, each decimated to 10 %
+    of its faces, at a texel of half the voxel - the layout (levels, torch's sort and scan, face_layout, texel_face: the
+    baker's own events, one construction per block after a warm-up), rtgs_mesh_texture_bake_view per view at 1200 x 680 with
+    the depth maps rendered beforehand, the mesh render of the same views beside it, the finish, the atlas size, fill and seen
+    share after the frames, and the bytes a view moves (4 B per atlas texel for the face map, 32 B per contributing texel)
+    against the time.
 Timing: device events around `reps` launches, after warm-up, in `blocks` blocks; the median block and the spread of the
 blocks are reported.
-python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance | --register | --distance-bounded] [OUT] [reps = 10] [blocks = 5]"""
+python tools/mesh_check.py [--sparse-only | --cleanup | --decimate | --distance | --register | --distance-bounded | --texture] [OUT] [reps = 10] [blocks = 5]"""
 import json
 import os
 import sys
@@ -489,8 +495,58 @@ def bounded_leg(dev, cam, frames, lo, hi, reps, blocks):
     return res
 
 
+def texture_leg(dev, cam, frames, lo, hi, reps, blocks):
+    res = {"timing": "device events; layout: the baker's own events around levels + sort + scan + face_layout + texel_face, one "
+                     "construction per block after a warm-up; bake and render: `reps` launches per block over the frames in turn",
+           "bytes": "per view: 4 B per atlas texel (texel_face) + 32 B per contributing texel (16 B of acc read and written)"}
+    for voxel in (0.02, 0.01):
+        vol = meshing.TsdfVolume(lo, hi, voxel, device=dev)
+        _fuse_all(vol, frames, cam)
+        v, f, c = vol.extract_mesh()
+        del vol
+        torch.cuda.empty_cache()
+        F0 = int(f.shape[0])
+        v, f, c, dstats = mesh_ops.decimate(v, f, c, int(0.10 * F0))
+        texel = voxel / 2
+        make = lambda: meshing.TextureBaker(v, f, cam, texel=texel, tolerance=voxel)
+        try:
+            layout = [make().layout_s * 1e3 for _ in range(blocks + 1)][1:]
+        except ValueError as e:                                                # the atlas would pass 16384: say so, go on
+            res[f"room_voxel_{voxel:g}"] = {"F": int(f.shape[0]), "texel": texel, "refused": str(e)}
+            continue
+        baker = make()
+        Wt, Ht = baker.size
+        entry = {"F_extracted": F0, "V": int(v.shape[0]), "F": int(f.shape[0]), "decimate_target_reached": dstats["target_reached"],
+                 "texel": texel, "size": [Wt, Ht], "atlas_texels": Wt * Ht, "texels_assigned": baker.T, "fill": round(baker.T / (Wt * Ht), 4),
+                 "faces_capped": int(baker.capped.sum()),
+                 "levels": torch.bincount(baker.levels.to(torch.int64), minlength=7)[1:7].tolist(), "layout": _summary(layout, 1)}
+        depths = [baker.renderer.render(p)[0] for _, _, p in frames]
+        contributing = []
+        for (_, col, p), d in zip(frames, depths):
+            before = baker.acc[..., 3].clone()
+            baker.bake(col, d, p)
+            contributing.append(int((baker.acc[..., 3] != before).sum()))
+            del before
+        image, flags = baker.finish(c)
+        seen = int((flags == 2).sum())
+        moved = 4.0 * Wt * Ht + 32.0 * float(np.mean(contributing))
+        entry.update({"views": len(frames), "texels_seen": seen, "seen_share": round(seen / max(baker.T, 1), 4),
+                      "contributing_texels_per_view_mean": int(np.mean(contributing)), "bytes_moved_per_view_mean": int(moved)})
+        n = len(frames)
+        timed = alternating_blocks_ms({"bake_view": lambda i: baker.bake(frames[i % n][1], depths[i % n], frames[i % n][2]),
+                                       "mesh_render": lambda i: baker.renderer.render(frames[i % n][2])}, reps, blocks)
+        timed["bake_view"]["TB_per_s_of_moved_bytes_at_median"] = round(moved / (timed["bake_view"]["median_ms"] * 1e-3) / 1e12, 3)
+        entry.update(timed)
+        entry["finish"] = blocks_ms(lambda i: baker.finish(c), reps, blocks)
+        res[f"room_voxel_{voxel:g}"] = entry
+        del baker, depths, image, flags, v, f, c
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance", "--register", "--distance-bounded")]
+    argv = [a for a in sys.argv[1:] if a not in ("--sparse-only", "--cleanup", "--decimate", "--distance", "--register", "--distance-bounded",
+                                                 "--texture")]
     sparse_only = "--sparse-only" in sys.argv[1:]
     cleanup_only = "--cleanup" in sys.argv[1:]
     out_path = argv[0] if len(argv) > 0 else None
@@ -515,6 +571,9 @@ def main():
         return _finish(res, out_path)
     if "--register" in sys.argv[1:]:
         res["register"] = register_leg(dev, cam, frames, lo, hi, reps, blocks)
+        return _finish(res, out_path)
+    if "--texture" in sys.argv[1:]:
+        res["texture"] = texture_leg(dev, cam, frames, lo, hi, reps, blocks)
         return _finish(res, out_path)
     if "--decimate" in sys.argv[1:]:
         res["decimate"] = decimate_leg(dev, cam, frames, lo, hi, blocks)
