@@ -96,8 +96,10 @@ void rtgs_raster_set_fwd_stamps(void* dev);
 /* The same for the tracker's residual launches (tools/icp_stamps.py): `dev` = device uint64[RTGS_ICP_STAMP_LAUNCHES x
  * RTGS_ICP_STAMP_WGS workgroups x 4 waves x 8] or NULL.  Residual launch k after the call (rtgs_icp_track, rtgs_icp_step) takes
  * slot k % RTGS_ICP_STAMP_LAUNCHES and runs the stamped twin of the kernel.  Per wave: wall clock (100 MHz) at entry and exit,
- * shader cycles of the source loads | gathers | projection, gates and sums | partial publish + ticket | last arriver's
- * partial reads + float64 sum | its solve.  PROCESS-WIDE; each call restarts at slot 0. */
+ * shader cycles of the source loads | gathers | projection, gates and sums | the partial row's store | the head's reads of
+ * the previous launch's rows + float64 sum | its solve, both of the wave's own workgroup (head-solve chain, the default;
+ * zero in a track's first launch).  With RTGS_ICP_FLAG_LAST_ARRIVER: ... | partial publish + ticket | last arriver's partial
+ * reads + float64 sum | its solve.  PROCESS-WIDE; each call restarts at slot 0. */
 #define RTGS_ICP_STAMP_LAUNCHES 16
 #define RTGS_ICP_STAMP_WGS 256
 void rtgs_icp_set_stamps(void* dev);

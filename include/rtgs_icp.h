@@ -79,7 +79,8 @@ typedef struct rtgs_icp_level {
 } rtgs_icp_level;
 
 /* Runs the whole multi-level Gauss-Newton loop on the device, pose resident there, no host synchronisation:
- * one launch per Gauss-Newton iteration by default, or - flags & RTGS_ICP_FLAG_PERSISTENT - ONE persistent kernel (a
+ * one launch per Gauss-Newton iteration by default (launch k+1 sums launch k's partial rows, solves and steps the pose at
+ * its head; the point2plane launch does so for the last iteration and writes pose_inout), or - flags & RTGS_ICP_FLAG_PERSISTENT - ONE persistent kernel (a
  * workgroup per CU, a grid barrier per iteration, every workgroup takes the same step on its own copy of the pose).
  * Same arithmetic; the persistent form is ~8 % faster with the device to itself, the default form coexists better with
  * kernels of other streams.  Environment override: RTGS_ICP_PERSISTENT=0/1.
@@ -101,6 +102,12 @@ int rtgs_icp_track(const rtgs_icp_level* levels_host, int32_t n_levels, const fl
                                            instead of the float64 Cholesky; launch-per-iteration chain only.  A measurement aid: it
                                            separates "the solve" from "gate-flip amplification" in the distance to the reference's
                                            float32 answer on noisy depth */
+#define RTGS_ICP_FLAG_LAST_ARRIVER 32  /* launch-per-iteration form only: the earlier chain, in which every launch ends with a ticket, the
+                                           last workgroup to arrive sums the partial rows and one thread solves before the kernel ends.
+                                           The default moves that work to the HEAD of the next launch (every workgroup sums and solves
+                                           redundantly; no ticket, no election).  Same arithmetic in the
+                                           same order: results are bit-identical.  Kept as the reference of tests/test_icp_head_solve_gpu.py
+                                           and for A-B runs.  Environment override: RTGS_ICP_LAST_ARRIVER=0/1 */
 #define RTGS_ICP_FLAG_CLUSTER 2     /* every level but the finest in one launch on a cluster of workgroups of ONE XCD (an
                                        in-XCD barrier per Gauss-Newton iteration), the finest level one launch per iteration */
 

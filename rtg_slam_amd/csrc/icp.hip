@@ -31,6 +31,11 @@ struct Scratch {
   double sums[24 * 8 * PSTRIDE];              // persistent track: 8 rows of float64 totals per grid barrier
   unsigned long long dbg[96];                 // RTGS_ICP_DEBUG_TIMING=1: wall-clock stamps of workgroup 0 (5 per barrier)
   uint32_t minmax_b[2 * RTGS_ICP_MAX_LEVELS]; // second set: a build re-arms the set the NEXT build uses (no memset launch)
+  // head-solve chain (the default launch-per-iteration form): launch k+1 sums launch k's rows at its head while its own
+  // workgroups already write theirs, so the rows alternate between `partials` and `partials_b`; the pose alternates
+  // between the two slots for the same reason (workgroup 0 writes pose k while the others still read pose k-1)
+  float partials_b[MAX_BLOCKS * PSTRIDE];
+  float pose_slots[2][16];
 };
 
 // The tracker's kernels are a chain the frame waits for; beside the mapper (VALU-issue-bound tile walks on every SIMD)
@@ -269,8 +274,9 @@ __device__ __forceinline__ float wave_sum63(float v) {
   return v;
 }
 
-// The workgroup's sums of the first NCOL columns -> its partial row.
-template <int NCOL>
+// The workgroup's sums of the first NCOL columns -> its partial row.  SC1: write-through stores for a reader inside the
+// same launch (the last arriver); plain stores when the next launch on the stream is the reader.
+template <int NCOL, bool SC1 = true>
 __device__ __forceinline__ void block_write_partials(float (&acc)[NCOL], float* __restrict__ partials) {
   __shared__ float s_part[4 * PSTRIDE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -282,10 +288,10 @@ __device__ __forceinline__ void block_write_partials(float (&acc)[NCOL], float* 
   __syncthreads();
   if (threadIdx.x < NCOL) {
     const int k = threadIdx.x;
+    const float v = (s_part[k] + s_part[PSTRIDE + k]) + (s_part[2 * PSTRIDE + k] + s_part[3 * PSTRIDE + k]);
     // write-through (sc1) store: visible to the electing workgroup without an L2 write-back fence
-    __hip_atomic_store(&partials[(size_t)blockIdx.x * PSTRIDE + k],
-                       (s_part[k] + s_part[PSTRIDE + k]) + (s_part[2 * PSTRIDE + k] + s_part[3 * PSTRIDE + k]),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (SC1) __hip_atomic_store(&partials[(size_t)blockIdx.x * PSTRIDE + k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else partials[(size_t)blockIdx.x * PSTRIDE + k] = v;
   }
 }
 
@@ -332,7 +338,9 @@ struct FinalArgs {
 // Sum of the per-workgroup partial rows in float64, by ONE whole workgroup (256 threads); the 28 totals land in
 // s_tot (shared, PSTRIDE doubles) and are visible to every thread on return.
 // 256 threads = 32 row groups x 8 four-float columns: every thread issues all of its (<= 16 x 4) write-through loads
-// before the first add, so the whole partial matrix costs ~2 memory round trips.
+// before the first add, so the whole partial matrix costs ~2 memory round trips.  SC1 = false: the rows were written by
+// the PREVIOUS launch on the stream - plain 16-byte loads (same values, same order of the float64 adds).
+template <bool SC1 = true>
 __device__ __forceinline__ void sum_partials(const float* __restrict__ partials, int nblocks, double* s_sum, double* s_tot) {
   {
     const int q = threadIdx.x & 7, grp = threadIdx.x >> 3;
@@ -345,13 +353,21 @@ __device__ __forceinline__ void sum_partials(const float* __restrict__ partials,
         const int r = grp + 32 * i;
         if (r < nblocks) {
           const float* row = partials + (size_t)r * PSTRIDE + 4 * q;
-          t[i][0] = ld_sc1(row); t[i][1] = ld_sc1(row + 1); t[i][2] = ld_sc1(row + 2); t[i][3] = ld_sc1(row + 3);
+          if constexpr (SC1) {
+            t[i][0] = ld_sc1(row); t[i][1] = ld_sc1(row + 1); t[i][2] = ld_sc1(row + 2); t[i][3] = ld_sc1(row + 3);
+          } else {
+            const float4 v = *reinterpret_cast<const float4*>(row);
+            t[i][0] = v.x; t[i][1] = v.y; t[i][2] = v.z; t[i][3] = v.w;
+          }
         } else {
           t[i][0] = t[i][1] = t[i][2] = t[i][3] = 0.f;
         }
       }
 #pragma unroll
-      for (int i = 0; i < MAXR; ++i) { a0 += (double)t[i][0]; a1 += (double)t[i][1]; a2 += (double)t[i][2]; a3 += (double)t[i][3]; }
+      for (int i = 0; i < MAXR; ++i) {
+        if (!SC1 && 32 * i >= nblocks) break;      // every workgroup runs the head's sum: skip the groups past the grid (adds of +0)
+        a0 += (double)t[i][0]; a1 += (double)t[i][1]; a2 += (double)t[i][2]; a3 += (double)t[i][3];
+      }
     }
     s_sum[grp * PSTRIDE + 4 * q] = a0; s_sum[grp * PSTRIDE + 4 * q + 1] = a1;
     s_sum[grp * PSTRIDE + 4 * q + 2] = a2; s_sum[grp * PSTRIDE + 4 * q + 3] = a3;
@@ -660,6 +676,74 @@ __device__ __forceinline__ bool arrive_and_elect_last(uint32_t* ticket) {
   return s_is_last != 0;
 }
 
+// ---- the head-solve chain: launch k+1 finishes launch k -------------------------------------------
+// The last-arriver chain above ends every launch with a serial tail (write-through rows, drain, ticket round trip, one
+// workgroup re-reads all rows, one thread solves, pose store, kernel end) and the next launch starts by loading that
+// pose.  Here a launch only WRITES its rows (plain stores; the kernel boundary on the stream orders them) and the NEXT
+// launch - the next iteration, or icp_p2p after the last one - sums them, solves and steps the pose at its head, every
+// workgroup redundantly and in the same order of operations (bit-identical pose everywhere).  No ticket, no election, no
+// wait on another workgroup.  (Issuing the lane's first source loads ahead of the head - they do not depend on the pose -
+// was measured: 24 more VGPRs, 176 instead of 152, the same track time alone and a SLOWER unit beside the mapper, 0.3555
+// against 0.349 ms; profiles/README.md r21.  The kernel keeps the registers of the last-arriver form instead.)
+// Only workgroup 0 writes what leaves the kernel: the stepped pose (to the slot the launch after reads), stats[0] and
+// the stats[2] count of non-positive-definite systems (the pose is then carried over unchanged).
+struct HeadArgs {
+  const float* partials;   // the previous launch's rows; nullptr = first launch of a track, nothing to consume
+  int rows;                // how many rows (that launch's grid)
+  float inv_pixels;        // 1 / pixels of that launch's level (valid_ratio, icp.py:46-47)
+  float damping;
+  const float* pose_in;    // the pose that launch ran at (first launch: the caller's pose, not read with first & 2)
+  float* pose_out;         // workgroup 0: the pose this launch runs at, for the next launch (icp_p2p: the caller's pose)
+  float* stats;
+  int first;               // as FinalArgs::first
+  int f32_solve;
+};
+
+// Leaves the pose this launch runs at in s_pose (LDS, 16 floats), visible to every thread on return.  STAMP: cyc[0] / cyc[1]
+// = shader cycles of the row loads + float64 sum / of the solve, pose update and the barrier behind it, this wave's view.
+template <bool STAMP>
+__device__ __forceinline__ void head_consume(const HeadArgs& h, float* s_pose, unsigned long long (&cyc)[2]) {
+  __shared__ double s_hsum[32 * PSTRIDE];
+  __shared__ double s_htot[PSTRIDE];
+  if (h.partials == nullptr) {                 // first launch of a track: hand the starting pose on, clear the counters
+    if (threadIdx.x < 16) {
+      const float v = (h.first & 2) ? ((threadIdx.x % 5 == 0) ? 1.f : 0.f) : h.pose_in[threadIdx.x];
+      s_pose[threadIdx.x] = v;
+      if (blockIdx.x == 0) h.pose_out[threadIdx.x] = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { h.stats[1] = 0.f; h.stats[2] = 0.f; h.stats[3] = 0.f; }
+    __syncthreads();
+    return;
+  }
+  unsigned long long t0 = 0;
+  if constexpr (STAMP) t0 = __builtin_readcyclecounter();
+  float pin[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) pin[k] = 0.f;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) pin[k] = h.pose_in[k];
+  }
+  sum_partials<false>(h.partials, h.rows, s_hsum, s_htot);
+  if constexpr (STAMP) { const unsigned long long t = __builtin_readcyclecounter(); cyc[0] = t - t0; t0 = t; }
+  if (threadIdx.x == 0) {
+    double S[NACC];
+#pragma unroll
+    for (int c = 0; c < NACC; ++c) S[c] = s_htot[c];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s_pose[k] = pin[k];
+    const bool ok = h.f32_solve ? gn_update_f32(S, h.damping, pin, s_pose) : gn_update(S, h.damping, pin, s_pose);
+    if (blockIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) h.pose_out[k] = s_pose[k];
+      h.stats[0] = (float)(S[27] * (double)h.inv_pixels);            // valid_ratio (icp.py:46-47)
+      if (!ok) h.stats[2] += 1.f;
+    }
+  }
+  __syncthreads();
+  if constexpr (STAMP) cyc[1] = __builtin_readcyclecounter() - t0;
+}
+
 // ---- K12: residual + Jacobian + 6x6 reduction (icp.py:52-119) ---------------------------------
 struct LevelGeom {
   float R00, R01, R02, t0, R10, R11, R12, t1, R20, R21, R22, t2;
@@ -853,6 +937,52 @@ __global__ void __launch_bounds__(256) icp_reduce_stamped_kernel(RTGS_ICP_REDUCE
 #undef RTGS_ICP_REDUCE_ARGS
 #undef RTGS_ICP_REDUCE_PASS
 
+// The residual launch of the head-solve chain: head (the previous launch's rows -> pose) -> residuals at that pose ->
+// this workgroup's row, plain stores, end.  STAMP: the eight words as above, with [5] = the row's write alone and
+// [6] / [7] = the head's sum / solve of THIS wave's workgroup (every workgroup has one).
+template <bool STAMP>
+__device__ __forceinline__ void icp_reduce_head_body(
+    const float* __restrict__ vs, const float* __restrict__ ns, const float* __restrict__ vt,
+    const float* __restrict__ nt, int H, int W, const float* __restrict__ K, float ds, float dist_thr, float cos_thr,
+    float* __restrict__ partials, const HeadArgs& h, unsigned long long* __restrict__ stamps) {
+  wave_priority_high();
+  __shared__ float s_pose[16];
+  unsigned long long wall0 = 0;
+  Stamp st{0, 0, 0, 0};
+  if constexpr (STAMP) wall0 = wall_clock64();
+  unsigned long long head[2] = {0, 0};
+  head_consume<STAMP>(h, s_pose, head);
+  if constexpr (STAMP) st.t = __builtin_readcyclecounter();
+  const LevelGeom g = make_geom(s_pose, K, ds, H, W, dist_thr, cos_thr);
+  float acc[NACC];
+#pragma unroll
+  for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
+  accumulate_range<STAMP>(g, vs, ns, vt, nt, H * W, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, acc, st);
+  block_write_partials<NACC, false>(acc, partials);
+  unsigned long long pub = 0;
+  stamp_lap<STAMP>(st, pub, true);
+  if constexpr (STAMP) {
+    if ((threadIdx.x & 63) == 0) {
+      unsigned long long* o = stamps + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+      o[0] = wall0; o[1] = wall_clock64(); o[2] = st.src; o[3] = st.gat; o[4] = st.acc; o[5] = pub;
+      o[6] = head[0]; o[7] = head[1];
+    }
+  }
+}
+#define RTGS_ICP_REDUCE_ARGS                                                                                            \
+  const float *__restrict__ vs, const float *__restrict__ ns, const float *__restrict__ vt,                             \
+      const float *__restrict__ nt, int H, int W, const float *__restrict__ K, float ds, float dist_thr, float cos_thr, \
+      float *__restrict__ partials, HeadArgs h, unsigned long long *__restrict__ stamps
+#define RTGS_ICP_REDUCE_PASS vs, ns, vt, nt, H, W, K, ds, dist_thr, cos_thr, partials, h, stamps
+__global__ void __launch_bounds__(256) icp_reduce_head_kernel(RTGS_ICP_REDUCE_ARGS) {
+  icp_reduce_head_body<false>(RTGS_ICP_REDUCE_PASS);
+}
+__global__ void __launch_bounds__(256) icp_reduce_head_stamped_kernel(RTGS_ICP_REDUCE_ARGS) {
+  icp_reduce_head_body<true>(RTGS_ICP_REDUCE_PASS);
+}
+#undef RTGS_ICP_REDUCE_ARGS
+#undef RTGS_ICP_REDUCE_PASS
+
 // ---- point2plane_loss (icp.py:7-13) at one level: sum(((R v1 + t - v0) . n0)^2) ---------------
 // Quads as in accumulate_range: a lane issues the nine 16-B loads (source vertex, target vertex, target normal) of each of
 // its (up to) two quads of a pass before the first use - one memory round trip per pass, two passes per lane at 1200x680
@@ -867,15 +997,8 @@ __device__ __forceinline__ float p2p_term(const float* Rt, float v0, float v1, f
   return l * l;
 }
 
-__global__ void __launch_bounds__(256) icp_p2p_kernel(const float* __restrict__ vs, const float* __restrict__ vt,
-                                                      const float* __restrict__ nt, int n,
-                                                      const float* __restrict__ pose, float* __restrict__ partials,
-                                                      uint32_t* __restrict__ ticket, FinalArgs fa) {
-  wave_priority_high();
-  float Rt[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) Rt[k] = pose[k];
-  float acc[1] = {0.f};
+__device__ __forceinline__ void p2p_accumulate(const float (&Rt)[12], const float* __restrict__ vs, const float* __restrict__ vt,
+                                               const float* __restrict__ nt, int n, float (&acc)[1]) {
   const int n4 = n >> 2, first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
   const float4* vs4 = reinterpret_cast<const float4*>(vs);
   const float4* vt4 = reinterpret_cast<const float4*>(vt);
@@ -904,6 +1027,40 @@ __global__ void __launch_bounds__(256) icp_p2p_kernel(const float* __restrict__ 
     const size_t j = (size_t)idx * 3;
     acc[0] += p2p_term(Rt, vs[j], vs[j + 1], vs[j + 2], vt[j], vt[j + 1], vt[j + 2], nt[j], nt[j + 1], nt[j + 2]);
   }
+}
+
+__global__ void __launch_bounds__(256) icp_p2p_kernel(const float* __restrict__ vs, const float* __restrict__ vt,
+                                                      const float* __restrict__ nt, int n,
+                                                      const float* __restrict__ pose, float* __restrict__ partials,
+                                                      uint32_t* __restrict__ ticket, FinalArgs fa) {
+  wave_priority_high();
+  float Rt[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Rt[k] = pose[k];
+  float acc[1] = {0.f};
+  p2p_accumulate(Rt, vs, vt, nt, n, acc);
+  block_write_partials<1>(acc, partials);      // only column 0: the last arriver reads nothing else in MODE_P2P
+  unsigned long long fin[2];
+  if (arrive_and_elect_last(ticket)) final_stage<false>(partials, (int)gridDim.x, fa, fin);
+}
+
+// The same at the end of a head-solve chain: the head consumes the LAST iteration's rows, so the pose the loss is taken
+// at - the track's result - is computed here; workgroup 0 writes it to the caller's pose (h.pose_out), which no workgroup
+// reads.  Same terms in the same order as icp_p2p_kernel; the loss keeps the last-arriver reduction (the host reads that
+// sum), on rows of their own (`partials` is not the buffer the head reads).
+__global__ void __launch_bounds__(256) icp_p2p_head_kernel(const float* __restrict__ vs, const float* __restrict__ vt,
+                                                           const float* __restrict__ nt, int n,
+                                                           float* __restrict__ partials, uint32_t* __restrict__ ticket,
+                                                           FinalArgs fa, HeadArgs h) {
+  wave_priority_high();
+  __shared__ float s_pose[16];
+  unsigned long long cyc[2];
+  head_consume<false>(h, s_pose, cyc);
+  float Rt[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Rt[k] = s_pose[k];
+  float acc[1] = {0.f};
+  p2p_accumulate(Rt, vs, vt, nt, n, acc);
   block_write_partials<1>(acc, partials);      // only column 0: the last arriver reads nothing else in MODE_P2P
   unsigned long long fin[2];
   if (arrive_and_elect_last(ticket)) final_stage<false>(partials, (int)gridDim.x, fa, fin);
@@ -1100,6 +1257,21 @@ static void launch_reduce(const float* vs, const float* ns, const float* vt, con
 #undef RTGS_ICP_LAUNCH
 }
 
+// The same launch in the head-solve chain; returns its grid = the rows the next launch's head has to sum.
+static int launch_reduce_head(const float* vs, const float* ns, const float* vt, const float* nt, int H, int W,
+                              const float* K, float ds, float dist_thr, float cos_thr, float* partials,
+                              const HeadArgs& h, hipStream_t st) {
+  const int g = grid_for((H * W + 3) / 4);
+  unsigned long long* stamps = nullptr;
+  if (g_stamps) stamps = g_stamps + (size_t)(g_stamp_launch++ % RTGS_ICP_STAMP_LAUNCHES) * RTGS_ICP_STAMP_WGS * 4 * 8;
+#define RTGS_ICP_LAUNCH(KERNEL)                                                                                     \
+  hipLaunchKernelGGL(KERNEL, dim3(g), dim3(256), 0, st, vs, ns, vt, nt, H, W, K, ds, dist_thr, cos_thr, partials, h, \
+                     stamps)
+  if (stamps) RTGS_ICP_LAUNCH(icp_reduce_head_stamped_kernel); else RTGS_ICP_LAUNCH(icp_reduce_head_kernel);
+#undef RTGS_ICP_LAUNCH
+  return g;
+}
+
 }  // namespace rtgs_icp
 
 using namespace rtgs_icp;
@@ -1264,6 +1436,52 @@ int rtgs_icp_track(const rtgs_icp_level* lv, int32_t n_levels, const float* K, f
     hipLaunchKernelGGL(icp_track_kernel, dim3(8 * a.cluster), dim3(256), 0, st, a);
     ICP_TRY(hipMemsetAsync(&sc->ticket, 0, sizeof(uint32_t), st));       // the launches below elect their last arriver from 0
     first_launched = n_levels - 1;
+  }
+  // Head-solve chain (default for the launch-per-iteration form; RTGS_ICP_FLAG_LAST_ARRIVER or RTGS_ICP_LAST_ARRIVER=1
+  // selects the last-arriver chain below): launch j = 1, 2, ... writes its rows to buffer j % 2 and tells the next launch
+  // - the next iteration, at this or a finer level, or icp_p2p - where they are, how many, and the level's 1 / pixels;
+  // launch j reads the pose it steps from slot j % 2 and workgroup 0 leaves the stepped pose in slot (j + 1) % 2
+  // (launch 1 puts the starting pose there).  The caller's pose is read by launch 1 only and written by icp_p2p only.
+  static const int env_last_arriver = [] { const char* e = getenv("RTGS_ICP_LAST_ARRIVER"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+  const bool last_arriver = env_last_arriver >= 0 ? env_last_arriver == 1 : (flags & RTGS_ICP_FLAG_LAST_ARRIVER) != 0;
+  if (plain && !last_arriver) {
+    float* bufs[2] = {sc->partials, sc->partials_b};
+    HeadArgs h{nullptr, 0, 0.f, damping, pose, nullptr, stats, 1 | (from_identity ? 2 : 0), (flags & RTGS_ICP_FLAG_F32_SOLVE) ? 1 : 0};
+    int j = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      const rtgs_icp_level& L = lv[l];
+      for (int it = 0; it < L.iters; ++it) {
+        ++j;
+        h.pose_out = sc->pose_slots[(j + 1) & 1];
+        h.rows = launch_reduce_head(L.vertex_src, L.normal_src, L.vertex_tgt, L.normal_tgt, L.H, L.W, K, L.downscale,
+                                    dist_thr, cos_thr, bufs[j & 1], h, st);
+        h.partials = bufs[j & 1];
+        h.inv_pixels = 1.f / ((float)L.H * (float)L.W);
+        h.pose_in = h.pose_out;
+        h.first = 0;
+      }
+    }
+    const rtgs_icp_level& F = lv[n_levels - 1];
+    const int n = F.H * F.W;
+    const int g = grid_for((n + 3) / 4);
+    if (j == 0) {                                    // no iteration anywhere: nothing to consume, the pose is the caller's
+      ICP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(float), st));
+      if (from_identity) {
+        static const float eye1[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+        ICP_TRY(hipMemcpyAsync(pose, eye1, sizeof(eye1), hipMemcpyHostToDevice, st));
+      }
+      FinalArgs fp{(int)MODE_P2P, 0.f, 1.f / (float)n, pose, stats, nullptr, nullptr, nullptr, 0, 0};
+      hipLaunchKernelGGL(icp_p2p_kernel, dim3(g), dim3(256), 0, st, F.vertex_src, F.vertex_tgt, F.normal_tgt, n,
+                         (const float*)pose, sc->partials, &sc->ticket, fp);
+    } else {
+      ++j;
+      h.pose_out = pose;
+      FinalArgs fp{(int)MODE_P2P, 0.f, 1.f / (float)n, nullptr, stats, nullptr, nullptr, nullptr, 0, 0};
+      hipLaunchKernelGGL(icp_p2p_head_kernel, dim3(g), dim3(256), 0, st, F.vertex_src, F.vertex_tgt, F.normal_tgt, n,
+                         bufs[j & 1], &sc->ticket, fp, h);
+    }
+    ICP_TRY(hipGetLastError());
+    return 0;
   }
   bool launched_any = false;
   for (int l = first_launched; l < n_levels; ++l) {

@@ -34,7 +34,7 @@ def _vp(t: torch.Tensor):
 
 _scratch = {}
 _builds = {}            # pyramid builds per scratch: the min / max set alternates (include/rtgs_icp.h)
-FLAG_PERSISTENT, FLAG_CLUSTER, FLAG_SCRATCH_READY, FLAG_FROM_IDENTITY, FLAG_F32_SOLVE = 1, 2, 4, 8, 16
+FLAG_PERSISTENT, FLAG_CLUSTER, FLAG_SCRATCH_READY, FLAG_FROM_IDENTITY, FLAG_F32_SOLVE, FLAG_LAST_ARRIVER = 1, 2, 4, 8, 16, 32
 PYR_SCRATCH_READY, PYR_SECOND_SET = 1, 2
 
 
@@ -110,11 +110,13 @@ def icp_step(v_src, n_src, v_tgt, n_tgt, K, pose, dist_thr: float, cos_thr: floa
 def icp_track(vertex_src: Sequence[torch.Tensor], normal_src, vertex_tgt, normal_tgt, K: torch.Tensor,
               downscales: Sequence[float], iters: Sequence[int], dist_thr: float, cos_thr: float,
               damping: float, pose0: torch.Tensor | None = None, persistent: bool = False,
-              f32_solve: bool = False) -> torch.Tensor:
+              f32_solve: bool = False, last_arriver: bool = False) -> torch.Tensor:
     """The level loop of IcpTracker.predict_pose (icp.py:428-447) on the device.
     Returns a device float32[20]: pose (16, row-major) + [valid_ratio, p2p_loss, n_singular, aborted].
     f32_solve: the Gauss-Newton update in float32 in the reference's order of operations (RTGS_ICP_FLAG_F32_SOLVE,
-    include/rtgs_icp.h) - a measurement aid, launch-per-iteration chain only."""
+    include/rtgs_icp.h) - a measurement aid, launch-per-iteration chain only.
+    last_arriver: the earlier launch-per-iteration chain (RTGS_ICP_FLAG_LAST_ARRIVER: sum and solve at the END of every
+    launch by its last workgroup instead of at the head of the next) - bit-identical results; tests and A-B runs."""
     lib = _lib.load()
     dev = vertex_src[0].device
     _require_device(vertex_src[0])
@@ -129,6 +131,7 @@ def icp_track(vertex_src: Sequence[torch.Tensor], normal_src, vertex_tgt, normal
     K = _f32c(K.to(dev))
     out = torch.empty(20, dtype=torch.float32, device=dev)
     flags = (FLAG_PERSISTENT if persistent else 0) | FLAG_SCRATCH_READY | (FLAG_F32_SOLVE if f32_solve else 0)
+    flags |= FLAG_LAST_ARRIVER if last_arriver else 0
     if pose0 is None:
         flags |= FLAG_FROM_IDENTITY            # the first iteration's last workgroup writes the pose: no fill / copy launches
     else:

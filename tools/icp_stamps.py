@@ -1,9 +1,12 @@
 """Where a Gauss-Newton launch of the tracker spends its time: per-wave stamps (rtgs_icp_set_stamps, include/rtgs_debug.h) of
 the 15 residual launches of ONE 3-level x 5-iteration track, on tools/prof_icp.py's frames.
-    python tools/icp_stamps.py [replica|tum]
+    python tools/icp_stamps.py [replica|tum] [last-arriver]
 Prints per level (mean over its 5 launches): launch span (first wave in -> last wave out), the mean wave's lifetime and its
-phases in us (source loads | gathers | projection, gates, sums | publish + ticket), and the last arriver's partial reads +
-float64 sum and solve.  Shader cycles are converted at the clock the stamps themselves show (cycles / wall time)."""
+phases in us.  Head-solve chain (default): head sum (the previous launch's rows, float64) | head solve (+ the barrier
+behind it) - both per workgroup, mean over all waves - | source loads | gathers | projection, gates, sums | the row's store.  The solve of the LAST iteration runs in icp_p2p, which carries no
+stamps.  `last-arriver` (RTGS_ICP_FLAG_LAST_ARRIVER): source loads | gathers | compute | publish + ticket, and the last
+arriver's partial reads + float64 sum and solve.  Shader cycles are converted at the clock the stamps themselves show
+(cycles / wall time)."""
 import math
 import os
 import sys
@@ -14,6 +17,7 @@ from rtg_slam_amd import _lib, synth, icp as hicp
 
 LAUNCHES, WGS = 16, 256           # RTGS_ICP_STAMP_LAUNCHES, RTGS_ICP_STAMP_WGS
 cam = synth.REPLICA if (len(sys.argv) < 2 or sys.argv[1] == "replica") else synth.TUM_FR1
+OLD = "last-arriver" in sys.argv[2:]
 lib = _lib.load()
 dev = torch.device("cuda", 0)
 poses = synth.trajectory(2, seed=9)
@@ -24,7 +28,7 @@ K = torch.tensor([[cam.fx, 0, cam.cx], [0, cam.fy, cam.cy], [0, 0, 1]], dtype=to
 vp0, np0 = hicp.build_pyramids(d0, K, 3)
 vp1, np1 = hicp.build_pyramids(d1, K, 3)
 cos_thr = math.cos(math.radians(20.0))
-track = lambda: hicp.icp_track(vp1, np1, vp0, np0, K, [0.25, 0.5, 1.0], [5, 5, 5], 0.1, cos_thr, 1e-4)
+track = lambda: hicp.icp_track(vp1, np1, vp0, np0, K, [0.25, 0.5, 1.0], [5, 5, 5], 0.1, cos_thr, 1e-4, last_arriver=OLD)
 for _ in range(20):
     track()
 torch.cuda.synchronize()
@@ -40,7 +44,8 @@ for rep in range(5):
 torch.cuda.synchronize()
 
 print(f"{cam.H}x{cam.W}: per-wave stamps of the residual launches, mean of {len(runs)} tracks; us")
-print("level  px       WGs  span   wave_life | src_loads gathers  compute  publish | last: sum   solve | gap_to_next")
+print(("last-arriver chain\n" if OLD else "head-solve chain\n") +
+      "level  px       WGs  span   wave_life | src_loads gathers  compute  publish | " + ("last: sum   solve" if OLD else "head: sum   solve") + " | gap_to_next")
 rows = []
 for s in runs:
     per = []
@@ -50,13 +55,20 @@ for s in runs:
         t_in, t_out = w[:, :, 0][live], w[:, :, 1][live]
         span = (t_out.max() - t_in.min()) * 0.01
         life = (t_out - t_in) * 0.01
-        plain = live & (w[:, :, 6] == 0)                             # waves without the last arriver's work
-        cyc_total = (w[:, :, 2] + w[:, :, 3] + w[:, :, 4] + w[:, :, 5])[plain]
+        if OLD:
+            plain = live & (w[:, :, 6] == 0)                         # waves without the last arriver's work
+            cyc_total = (w[:, :, 2] + w[:, :, 3] + w[:, :, 4] + w[:, :, 5])[plain]
+        else:                                                        # every wave has a head; its cycles are stamped too
+            plain = live
+            cyc_total = w[:, :, 2:8].sum(-1)[plain]
         ghz = (cyc_total.sum() / max(((w[:, :, 1] - w[:, :, 0])[plain] * 0.01).sum(), 1e-9)) * 1e-3   # cycles per us -> GHz
         mhz = ghz * 1e3
         ph = [float(w[:, :, c][live].mean()) / mhz for c in (2, 3, 4, 5)]
-        lastw = w[:, 0, 6] > 0
-        fin = [float(w[lastw, 0, 6].mean()) / mhz, float(w[lastw, 0, 7].mean()) / mhz] if lastw.any() else [0.0, 0.0]
+        if OLD:
+            lastw = w[:, 0, 6] > 0
+            fin = [float(w[lastw, 0, 6].mean()) / mhz, float(w[lastw, 0, 7].mean()) / mhz] if lastw.any() else [0.0, 0.0]
+        else:                                                        # launch 0 of a track has no head to run: zeros
+            fin = [float(w[:, :, 6][live].mean()) / mhz, float(w[:, :, 7][live].mean()) / mhz]
         nxt = s[k + 1] if k + 1 < 15 else None
         gap = ((nxt[:, :, 0][nxt[:, :, 0] > 0].min() - t_out.max()) * 0.01) if nxt is not None else float("nan")
         per.append([int(live.any(1).sum()), span, float(life.mean())] + ph + fin + [gap, ghz])
