@@ -218,6 +218,29 @@ int rtgs_raster_backward_walk_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* set
                                   float* dL_dmeans3D, float* dL_dopacities, float* dL_dshs,
                                   float* dL_dscales, float* dL_drotations, float* dL_dnormal_w,
                                   void* grad_scratch, uint8_t* row_state, int32_t train_begin, int32_t train_end, void* stream);
+/* The walk above with the image gradients of the SLAM loss given as what rtgs_slam_loss_sums_signs leaves: one byte per
+ * pixel, the sums and the two weights; the entry walk rebuilds the four floats per pixel bit for bit.  Only for a forward
+ * this context remembers and whose tiles all take the entry walk - rtgs_raster_signs_ok_ctx() says whether (and whether
+ * the switch is on: RTGS_LOSS_SIGNS / rtgs_raster_set_loss_signs_ctx, default on); RTGS_E_INVALID otherwise. */
+typedef struct rtgs_loss_signs {
+  const uint8_t* signs;      /* [H, W] */
+  const float* sums;         /* the loss scratch's header (16-byte aligned): words 0-3 are read */
+  float color_weight, depth_weight;
+  float* loss_out4;          /* nullable: the loss values {total, colour, depth, 0} - the walk has the sums in hand, its first
+                                workgroup writes them (a one-thread launch does where no walk is launched) */
+} rtgs_loss_signs;
+int rtgs_raster_signs_ok_ctx(rtgs_ctx* ctx, const void* geom_buffer);
+void rtgs_raster_set_loss_signs_ctx(rtgs_ctx* ctx, int enable);
+/* out2 = {map steps whose backward read signs, map steps that took the float planes} (rtgs_slam_map_step*). */
+int rtgs_raster_loss_signs_stats_ctx(rtgs_ctx* ctx, int64_t* out2);
+void rtgs_raster_note_loss_path_ctx(rtgs_ctx* ctx, int signs);
+int rtgs_raster_backward_walk_signs_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* settings, int32_t P, int32_t sh_coeffs,
+                                        int64_t num_rendered, const float* means3D, const float* opacities, const float* shs,
+                                        const float* scales, const float* rotations, const float* normal_w, void* geom_buffer,
+                                        void* binning_buffer, const void* image_buffer, const float* out_color,
+                                        const float* out_T, const int32_t* out_depth_index, const rtgs_loss_signs* loss,
+                                        void* grad_scratch, uint8_t* row_state, int32_t train_begin, int32_t train_end,
+                                        void* stream);
 
 /* Sizes the forward will request through the callbacks (for pre-allocation / accounting).  The geometry buffer's size
  * depends on the context's near-slice budget; its layout is such that a backward never needs to know that budget. */
@@ -405,6 +428,18 @@ int rtgs_slam_loss_sums(const float* color, const float* depth, const int32_t* d
 int rtgs_slam_loss_grads(const float* color, const float* depth, const int32_t* depth_index, const float* gt_color,
                          const float* gt_depth, int32_t H, int32_t W, const rtgs_loss_cfg* cfg, void* scratch,
                          float* loss_out4, float* g_color, float* g_depth, void* stream);
+/* _sums for a backward that reads SIGNS (rtgs_raster_backward_walk_signs_ctx).  While the SSIM term is off (a render mask,
+ * or ssim_weight == 0; -1 otherwise) every value _grads would write is +k, -k or 0 with two image-wide scalars
+ *   kc = color_weight / (3 max(sums[3], 1))   kd = depth_weight / max(sums[2], 1),
+ * so one pass leaves the five sums AND one byte per pixel at scratch + rtgs_slam_loss_signs_offset(H, W, with_ssim):
+ *   bits 0-1, 2-3, 4-5: colour channels 0, 1, 2   bits 6-7: depth   code 0 = zero, 1 = +k, 2 = -k
+ * (the conditions are _grads': the mask, sign(0) = 0, the depth gate).  loss_out4 (nullable) is written as _grads would, by
+ * a one-thread launch behind the sums (rtgs_slam_loss_values); NULL where the backward that reads the signs writes it. */
+size_t rtgs_slam_loss_signs_offset(int32_t H, int32_t W, int32_t with_ssim);
+int rtgs_slam_loss_values(const rtgs_loss_cfg* cfg, const void* scratch, float* loss_out4, void* stream);
+int rtgs_slam_loss_sums_signs(const float* color, const float* depth, const int32_t* depth_index, const float* gt_color,
+                              const float* gt_depth, int32_t H, int32_t W, const rtgs_loss_cfg* cfg, void* scratch,
+                              float* loss_out4, void* stream);
 
 /* One map-optimisation iteration as a single call (the body of local_optimize's inner loop, mapper.py:176-205, with
  * loss_update's image terms, attach regulariser, Adam step and confidence increment, mapper.py:371-456):

@@ -170,6 +170,15 @@ _SIGNATURES = {
     "rtgs_raster_set_onepass_ctx": (None, [_P, C.c_int]),
     "rtgs_raster_set_fused_sort_ctx": (None, [_P, C.c_int]),
     "rtgs_raster_fused_sort_stats_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "rtgs_raster_set_loss_signs_ctx": (None, [_P, C.c_int]),
+    "rtgs_raster_loss_signs_stats_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "rtgs_raster_signs_ok_ctx": (C.c_int, [_P, _P]),
+    "rtgs_raster_note_loss_path_ctx": (None, [_P, C.c_int]),
+    "rtgs_raster_backward_walk_signs_ctx": (C.c_int, [_P, C.POINTER(RasterSettingsC), C.c_int32, C.c_int32, C.c_int64] + [_P] * 6
+                                            + [_P] * 3 + [_P, _P, _P] + [_P] + [_P, _P, C.c_int32, C.c_int32, _P]),
+    "rtgs_slam_loss_values": (C.c_int, [C.POINTER(LossCfgC), _P, _P, _P]),
+    "rtgs_slam_loss_signs_offset": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rtgs_slam_loss_sums_signs": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(LossCfgC), _P, _P, _P]),
     "rtgs_raster_forward_verify_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "rtgs_raster_spec_fail_ptr_ctx": (C.c_void_p, [_P]),
     "rtgs_raster_set_speculation_ctx": (None, [_P, C.c_int]),

@@ -33,13 +33,31 @@ static int map_step_front(rtgs_ctx* ctx, const rtgs_map_step_args* a, int64_t* n
   void *geom = bufs[0], *bin = bufs[1], *img = bufs[2];
   rtgs_loss_cfg lcfg = a->loss;
   lcfg.sums_zeroed = P > 0 ? 1 : 0;
-  rc = rtgs_slam_loss(a->out_color, a->out_depth, a->out_depth_index, a->gt_color, a->gt_depth, H, W, &lcfg,
-                      a->loss_scratch, a->loss4, a->dL_dcolor, a->dL_ddepth, stream);
+  // The loss as sums and SIGNS - one pass over the images, no gradient planes, one launch less - where the backward can read
+  // them: the SSIM term off (the gradient is then a sign times one of two scalars), only the walk to follow, and every tile
+  // of this forward on the entry walk.  Else the sums, the float planes and the walks that read those, as ever.
+  const bool ssim_off = a->loss.render_mask != nullptr || a->loss.ssim_weight == 0.f;
+  const bool signs = walk_only && ssim_off && rtgs_raster_signs_ok_ctx(ctx, geom) != 0;
+  rtgs_raster_note_loss_path_ctx(ctx, signs ? 1 : 0);
+  if (signs)
+    rc = rtgs_slam_loss_sums_signs(a->out_color, a->out_depth, a->out_depth_index, a->gt_color, a->gt_depth, H, W, &lcfg,
+                                   a->loss_scratch, nullptr, stream);       // the values: the walk below, or _values
+  else
+    rc = rtgs_slam_loss(a->out_color, a->out_depth, a->out_depth_index, a->gt_color, a->gt_depth, H, W, &lcfg,
+                        a->loss_scratch, a->loss4, a->dL_dcolor, a->dL_ddepth, stream);
   if (rc != 0) return RTGS_E_HIP;
   int32_t t0 = 0, t1 = P;                                 // the trainable rows (rtgs_map_step_args: ONLY 0, 0 = all)
   if (a->train_begin != 0 || a->train_end != 0) { t0 = a->train_begin; t1 = a->train_end; }
   if (t0 < 0 || t1 > P || t1 < t0) return RTGS_E_INVALID;
-  if (t1 == t0) return RTGS_OK;                           // an empty range (a fully frozen map): rendered, loss evaluated, nothing differentiated
+  if (t1 == t0)                                           // an empty range (a fully frozen map): rendered, loss evaluated, nothing differentiated
+    return signs && rtgs_slam_loss_values(&lcfg, a->loss_scratch, a->loss4, stream) != 0 ? RTGS_E_HIP : RTGS_OK;
+  if (signs) {
+    const rtgs_loss_signs ls{reinterpret_cast<const uint8_t*>(a->loss_scratch) + rtgs_slam_loss_signs_offset(H, W, a->loss.render_mask == nullptr),
+                             reinterpret_cast<const float*>(a->loss_scratch), a->loss.color_weight, a->loss.depth_weight, a->loss4};
+    return rtgs_raster_backward_walk_signs_ctx(ctx, a->settings, P, M, *num_rendered_host, a->xyz, a->opacity, a->shs, a->scales,
+                                               a->rotations, a->normal, geom, bin, img, a->out_color, a->out_T, a->out_depth_index,
+                                               &ls, a->grad_scratch, a->row_state, t0, t1, stream);
+  }
   rc = (walk_only ? rtgs_raster_backward_walk_ctx : rtgs_raster_backward_range_ctx)(
       ctx, a->settings, P, M, *num_rendered_host, a->xyz, a->opacity, a->shs, a->scales, a->rotations, a->normal, geom, bin, img,
       a->out_color, a->out_T, a->out_depth_index, a->dL_dcolor, a->dL_ddepth, a->d_xyz, a->d_opacity, a->d_shs, a->d_scales,

@@ -32,7 +32,8 @@ void launch_blend_bwd(const RasterParams&, const uint2*, const uint32_t*, const 
                       const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, int, uint32_t, uint32_t, hipStream_t);
 void launch_blend_bwd_entry(const RasterParams&, const uint2*, const uint32_t*, const Splat*, const float*, const uint32_t*,
                             const int32_t*, const uint32_t*, const uint32_t*, const float*, const float*, const uint32_t*, uint32_t*,
-                            const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, uint32_t, uint32_t, TileCache, uint32_t, hipStream_t);
+                            const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, uint32_t, uint32_t, TileCache, uint32_t, hipStream_t,
+                            const LossSigns* signs = nullptr);
 void launch_grad_reduce(int, const uint8_t*, const uint32_t*, uint32_t*, const BwdInfo*, SplatGrad*, const uint32_t*, hipStream_t);
 void launch_preprocess_bwd(const RasterParams&, const float*, const float*, const float*, const float*, const float*,
                            const float*, const int32_t*, const uint8_t*, SplatGrad*, uint8_t*, uint8_t*, float*, float*,
@@ -99,7 +100,11 @@ struct rtgs_ctx {
     bool speculation = true;        // the speculative forward (RTGS_FWD_SPECULATE; see rtgs_raster.h)
     bool plain_onepass = true;      // RTGS_PLAIN_ONEPASS=0: count / scan / scatter with the two host waits, as before round 6
     bool cull_cache = true, cull_check = false;   // the cull cache and its self-check (rtgs_raster_set_cull_cache_ctx)
+    // Map step: the loss leaves one sign byte per pixel and the entry walk rebuilds the image gradients from it, where that
+    // is possible (rtgs_raster_signs_ok_ctx); RTGS_LOSS_SIGNS=0: the float planes and slam_loss_grads' launch, as before.
+    bool loss_signs = true;
   } sw;
+  int64_t loss_path_stats[2] = {0, 0};   // map steps whose backward read signs, map steps that took the float planes
   int64_t slice_stats[4] = {0};     // used, near-slice instances, tiles finished, tiles left to pass 2
   unsigned long long* counters = nullptr;
   uint32_t last_listed = 0;         // Gaussians the last verified speculative forward listed for binning
@@ -196,6 +201,7 @@ static rtgs_ctx* default_ctx() {
     if (const char* e = getenv("RTGS_BWD_WALK")) { const int m = atoi(e); n->sw.bwd_walk = (m >= 1 && m <= 4) ? m : 0; }
     if (const char* e = getenv("RTGS_CULL_CACHE")) n->sw.cull_cache = atoi(e) != 0;
     if (const char* e = getenv("RTGS_CULL_CACHE_CHECK")) n->sw.cull_check = atoi(e) != 0;
+    if (const char* e = getenv("RTGS_LOSS_SIGNS")) n->sw.loss_signs = atoi(e) != 0;
     return n;
   }();
   return c;
@@ -1094,7 +1100,7 @@ static int backward_impl(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_t P
                          const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans3D, float* dL_dopacities,
                          float* dL_dshs, float* dL_dscales, float* dL_drotations, float* dL_dnormal_w,
                          void* grad_scratch, uint8_t* row_state, int32_t train_begin, int32_t train_end, void* stream,
-                         bool walk_only = false) {
+                         bool walk_only = false, const rtgs_loss_signs* lsg = nullptr) {
   rtgs_ctx* c = use(ctx);   // NOTE: the geometry buffer is written here (slot counters): it is scratch of the pair
   RasterParams p;
   int rc = make_params(s, P, M, p);
@@ -1103,8 +1109,13 @@ static int backward_impl(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_t P
   // the backward of a speculative forward guards itself with that forward's device word (see rtgs_raster_forward_verify)
   if (c->spec.geom == geom_buffer && c->spec.fail_dev) p.spec_fail = c->spec.fail_dev;
   if (!means3D || !opacities || !shs || !scales || !rotations || !normal_w || !geom_buffer || !binning_buffer ||
-      !image_buffer || !out_color || !out_T || !out_didx || !dL_dcolor || !dL_ddepth || !grad_scratch || R < 0)
+      !image_buffer || !out_color || !out_T || !out_didx || (!lsg && (!dL_dcolor || !dL_ddepth)) || !grad_scratch || R < 0)
     return RTGS_E_INVALID;
+  // signs in place of the gradient images: only the entry walk reads them, so the forward must be remembered as all-entry
+  if (lsg && (!walk_only || !lsg->signs || !lsg->sums || c->hint_geom != geom_buffer || c->hint_walk != 2)) return RTGS_E_INVALID;
+  const LossSigns lsd = lsg ? LossSigns{lsg->signs, lsg->sums, lsg->color_weight, lsg->depth_weight, lsg->loss_out4}
+                            : LossSigns{nullptr, nullptr, 0.f, 0.f, nullptr};
+  int entry_launches = 0;
   if (!walk_only && (!dL_dmeans3D || !dL_dopacities || !dL_dshs || !dL_dscales || !dL_drotations || !dL_dnormal_w)) return RTGS_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int ntiles = p.gx * p.gy;
@@ -1145,13 +1156,14 @@ static int backward_impl(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_t P
       if (which & 3)
         launch_blend_bwd(p, rg, pl, (const Splat*)(geom + G.splats), out_color, out_T, (const uint32_t*)(img + I.n_contrib),
                          out_didx, dL_dcolor, dL_ddepth, gbase, slot_count, binfo, grads, touched, tile_mode, which & 3, t0, tn, st);
+      if (which & 4) ++entry_launches;
       if (which & 4)
         launch_blend_bwd_entry(p, rg, pl, (const Splat*)(geom + G.splats), out_color, (const uint32_t*)(img + I.n_contrib),
                                out_didx, depth_pos, (const uint32_t*)(img + I.tile_last), dL_dcolor, dL_ddepth, gbase, slot_count, binfo, grads,
                                touched, tile_mode, t0, tn,
                                TileCache{(float4*)(img + I.tile_recs), (uint16_t*)(img + I.tile_masks), (float2*)(img + I.depth_aux)},
                                set == 0 ? (uint32_t)(BLOCK / 4) : (uint32_t)BLOCK,      // the near slice's first batch is a quarter batch
-                               st);
+                               st, lsg ? &lsd : nullptr);
     }
     prof_mark(c, EV_BWALK, st);
     // sum each touched Gaussian's slots into its SplatGrad record (no-op on the atomic fallback)
@@ -1159,6 +1171,10 @@ static int backward_impl(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_t P
     DBG(s, st);
   }
   prof_mark(c, EV_BBLEND, st);
+  if (lsg && lsg->loss_out4 && entry_launches == 0) {     // nothing to walk: nobody has written the loss values yet
+    const rtgs_loss_cfg lc{lsg->color_weight, lsg->depth_weight, 0.f, 0.f, nullptr, 0};
+    if (rtgs_slam_loss_values(&lc, lsg->sums, lsg->loss_out4, stream) != 0) return RTGS_E_HIP;
+  }
   if (walk_only) { prof_mark(c, EV_BPRE, st); HIP_TRY(hipGetLastError()); return RTGS_OK; }   // a fused consumer takes over
   launch_preprocess_bwd(p, means3D, opacities, shs, scales, rotations, normal_w, radii,
                         (const uint8_t*)(geom + G.clamped), grads, touched, row_state, dL_dmeans3D, dL_dopacities,
@@ -1221,6 +1237,29 @@ int rtgs_raster_backward_walk_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, 
                        image_buffer, out_color, out_T, out_didx, dL_dcolor, dL_ddepth, dL_dmeans3D, dL_dopacities,
                        dL_dshs, dL_dscales, dL_drotations, dL_dnormal_w, grad_scratch, row_state, train_begin, train_end, stream, true);
 }
+
+int rtgs_raster_backward_walk_signs_ctx(rtgs_ctx* ctx, const rtgs_raster_settings* s, int32_t P, int32_t M, int64_t R,
+                                        const float* means3D, const float* opacities, const float* shs, const float* scales,
+                                        const float* rotations, const float* normal_w, void* geom_buffer, void* binning_buffer,
+                                        const void* image_buffer, const float* out_color, const float* out_T,
+                                        const int32_t* out_didx, const rtgs_loss_signs* loss, void* grad_scratch,
+                                        uint8_t* row_state, int32_t train_begin, int32_t train_end, void* stream) {
+  if (!loss || (P > 0 && !row_state)) return RTGS_E_INVALID;
+  return backward_impl(ctx, s, P, M, R, means3D, opacities, shs, scales, rotations, normal_w, geom_buffer, binning_buffer,
+                       image_buffer, out_color, out_T, out_didx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, grad_scratch, row_state, train_begin, train_end, stream, true, loss);
+}
+int rtgs_raster_signs_ok_ctx(rtgs_ctx* ctx, const void* geom_buffer) {
+  rtgs_ctx* c = use(ctx);
+  return c->sw.loss_signs && geom_buffer && c->hint_geom == geom_buffer && c->hint_walk == 2 ? 1 : 0;
+}
+void rtgs_raster_set_loss_signs_ctx(rtgs_ctx* ctx, int enable) { use(ctx)->sw.loss_signs = enable != 0; }
+int rtgs_raster_loss_signs_stats_ctx(rtgs_ctx* ctx, int64_t* out2) {
+  if (!out2) return RTGS_E_INVALID;
+  memcpy(out2, use(ctx)->loss_path_stats, sizeof(use(ctx)->loss_path_stats));
+  return RTGS_OK;
+}
+void rtgs_raster_note_loss_path_ctx(rtgs_ctx* ctx, int signs) { ++use(ctx)->loss_path_stats[signs ? 0 : 1]; }
 
 void rtgs_raster_set_profiling_ctx(rtgs_ctx* c, int enable) { use(c)->prof = enable != 0; }
 void rtgs_raster_set_near_slice_ctx(rtgs_ctx* c, int mode, int budget_per_tile) {

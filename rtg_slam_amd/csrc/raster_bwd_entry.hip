@@ -308,6 +308,8 @@ struct TileLoads {
   uint4 info;                           // BwdInfo: slot_grads (two words), slots, use_slots
   uint32_t last;                        // per pixel
   float g0, g1, g2, oc0, oc1, oc2, gD;
+  uint32_t sg;                          // SIGNS: the pixel's sign byte, and the loss sums (same address in every lane): the
+  float4 sm;                            //        scalars kc, kd follow from the two counts .z .w
   int owner;
   uint32_t dpos;
   float2 aux;
@@ -321,7 +323,12 @@ struct TileLoads {
 // partials | staging: records -> LDS (gather path: the gather and the quadrant test) | compaction + the barrier before the
 // walk | barrier behind the loop: the tile's slowest quadrant | per-entry tail: moments -> slot store, incl. the barrier
 // behind it) and two marks inside the prologue (unused | every load of the prologue there).
-template <bool STAMP>
+//
+// SIGNS: the image gradients of the SLAM loss arrive as one byte per pixel (LossSigns, raster_common.h) in place of the four
+// float planes - one byte load for four dword loads in the prologue, and slam_loss_grads_kernel's launch, its 30 MB of
+// reads and its 13 MB of writes are gone from the map step.  g0 g1 g2 gD are rebuilt here, bit for bit what that kernel
+// writes (same expressions for kc and kd, IEEE division), before their first use; nothing downstream knows the difference.
+template <bool STAMP, bool SIGNS>
 __device__ __forceinline__ void blend_bwd_entry_body(
     const RasterParams& p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const Splat* __restrict__ splats, const float* __restrict__ out_color, const uint32_t* __restrict__ n_contrib,
@@ -329,7 +336,8 @@ __device__ __forceinline__ void blend_bwd_entry_body(
     const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
     const uint32_t* __restrict__ gbase, uint32_t* __restrict__ slot_count, const BwdInfo* __restrict__ info,
     SplatGrad* __restrict__ grads, uint8_t* __restrict__ touched, const uint32_t* __restrict__ tile_mode,
-    uint32_t t0, uint32_t tn, uint32_t dbg, unsigned long long* __restrict__ stamps, const TileCache& tc, uint32_t pre) {
+    uint32_t t0, uint32_t tn, uint32_t dbg, unsigned long long* __restrict__ stamps, const TileCache& tc, uint32_t pre,
+    const LossSigns& ls) {
   __shared__ float4 s_rec[MB * 3];              // u v ca cb | cc o r g | b id blockmask -
   __shared__ float s_acc[MB * MACC];            // per-entry sums of the tile (LDS float adds: one flush per wave and group)
   __shared__ uint8_t s_sub[4][MB];              // per quadrant: the staged entries that reach it, in list order
@@ -365,10 +373,11 @@ __device__ __forceinline__ void blend_bwd_entry_body(
     L.fail = p.spec_fail ? p.spec_fail[tz - tile] : 0u;
     L.info = reinterpret_cast<const uint4*>(info)[tz - tile];
     L.last = n_contrib[pix];
-    L.g0 = dL_dcolor[pix]; L.g1 = dL_dcolor[HW + pix]; L.g2 = dL_dcolor[2 * HW + pix];
+    if constexpr (SIGNS) { L.sg = ls.signs[pix]; L.sm = reinterpret_cast<const float4*>(ls.sums)[tz - tile]; }
+    else { L.g0 = dL_dcolor[pix]; L.g1 = dL_dcolor[HW + pix]; L.g2 = dL_dcolor[2 * HW + pix]; }
     L.oc0 = out_color[pix]; L.oc1 = out_color[HW + pix]; L.oc2 = out_color[2 * HW + pix];
     L.owner = depth_index[pix];
-    L.gD = dL_ddepth[pix];
+    if constexpr (!SIGNS) L.gD = dL_ddepth[pix];
     L.dpos = depth_pos[pix];
     {
       // the records of the first `pre` list positions travel with the prologue (64 behind a near-slice pass - its first batch,
@@ -476,6 +485,19 @@ __device__ __forceinline__ void blend_bwd_entry_body(
     const float tx0 = (float)(bx * TILE), ty0 = (float)(by * TILE);
     const float cxT = tx0 + 7.5f, cyT = ty0 + 7.5f;     // moments are taken about the tile centre
 
+    if constexpr (SIGNS) {
+      // slam_loss_grads_kernel's scalars, term for term
+      const float inv_c = 1.f / (3.f * fmaxf(L.sm.w, 1.f)), inv_m = 1.f / fmaxf(L.sm.z, 1.f);
+      const float kc = ls.cw * inv_c, kd = ls.dw * inv_m;
+      // the loss VALUES, for the launch: the sums kernel ends with its adds, and the first reader of the final sums is here
+      if (ls.loss4 && cur == 0 && tid == 0) {
+        const float lc = L.sm.x * inv_c, ld = L.sm.y * inv_m;
+        ls.loss4[1] = lc; ls.loss4[2] = ld; ls.loss4[3] = 0.f;
+        ls.loss4[0] = ls.dw * ld + ls.cw * lc;
+      }
+      L.g0 = sign_value(L.sg & 3u, kc); L.g1 = sign_value((L.sg >> 2) & 3u, kc); L.g2 = sign_value((L.sg >> 4) & 3u, kc);
+      L.gD = sign_value((L.sg >> 6) & 3u, kd);
+    }
     EntryWalk W;
     W.n = n;
     W.last = inside ? L.last : 0u;
@@ -502,7 +524,11 @@ __device__ __forceinline__ void blend_bwd_entry_body(
         const float rx = ((float)px - p.cx) / p.fx, ry = ((float)py - p.cy) / p.fy;
         uint32_t pl = pix;
         asm volatile("" : "+v"(pl));              // the addresses of these rare loads are formed here, not held from the prologue on
-        if (reload) { gD = dL_ddepth[pl]; const float2 a2 = cached ? tc.depth_aux[pl] : make_float2(0.f, 0.f); iden = a2.x; Dd = a2.y; }
+        if (reload) {
+          if constexpr (SIGNS) gD = sign_value(((uint32_t)ls.signs[pl] >> 6) & 3u, ls.dw * (1.f / fmaxf(ls.sums[2], 1.f)));
+          else gD = dL_ddepth[pl];
+          const float2 a2 = cached ? tc.depth_aux[pl] : make_float2(0.f, 0.f); iden = a2.x; Dd = a2.y;
+        }
         if (!cached) {
           const int owner = depth_index[pl];
           const float4 r2 = reinterpret_cast<const float4*>(splats + owner)[2];   // b nx ny nz
@@ -652,9 +678,12 @@ __device__ __forceinline__ void blend_bwd_entry_body(
   p, ranges, point_list, splats, out_color, n_contrib, depth_index, depth_pos, tile_last, dL_dcolor, dL_ddepth, gbase, slot_count, \
       info, grads, touched, tile_mode, t0, tn, dbg, stamps, tc, pre
 // the product kernel
-__global__ void __launch_bounds__(256, 5) blend_bwd_entry_kernel(RTGS_BWD_ARGS) { blend_bwd_entry_body<false>(RTGS_BWD_PASS); }
+__global__ void __launch_bounds__(256, 5) blend_bwd_entry_kernel(RTGS_BWD_ARGS) { blend_bwd_entry_body<false, false>(RTGS_BWD_PASS, LossSigns{}); }
 // the same, leaving per-wave time stamps (tools/bwd_stamps.py)
-__global__ void __launch_bounds__(256, 5) blend_bwd_entry_stamped_kernel(RTGS_BWD_ARGS) { blend_bwd_entry_body<true>(RTGS_BWD_PASS); }
+__global__ void __launch_bounds__(256, 5) blend_bwd_entry_stamped_kernel(RTGS_BWD_ARGS) { blend_bwd_entry_body<true, false>(RTGS_BWD_PASS, LossSigns{}); }
+// both again for image gradients given as signs (dL_dcolor, dL_ddepth are not read)
+__global__ void __launch_bounds__(256, 5) blend_bwd_entry_signs_kernel(RTGS_BWD_ARGS, LossSigns ls) { blend_bwd_entry_body<false, true>(RTGS_BWD_PASS, ls); }
+__global__ void __launch_bounds__(256, 5) blend_bwd_entry_signs_stamped_kernel(RTGS_BWD_ARGS, LossSigns ls) { blend_bwd_entry_body<true, true>(RTGS_BWD_PASS, ls); }
 #undef RTGS_BWD_ARGS
 #undef RTGS_BWD_PASS
 
@@ -670,13 +699,18 @@ void launch_blend_bwd_entry(const RasterParams& p, const uint2* ranges, const ui
                             const float* out_color, const uint32_t* n_contrib, const int32_t* depth_index,
                             const uint32_t* depth_pos, const uint32_t* tile_last, const float* dL_dcolor, const float* dL_ddepth,
                             const uint32_t* gbase, uint32_t* slot_count, const BwdInfo* info, SplatGrad* grads, uint8_t* touched,
-                            const uint32_t* tile_mode, uint32_t t0, uint32_t tn, TileCache tc, uint32_t pre, hipStream_t st) {
+                            const uint32_t* tile_mode, uint32_t t0, uint32_t tn, TileCache tc, uint32_t pre, hipStream_t st,
+                            const LossSigns* signs) {
   const uint32_t dbg = (uint32_t)g_bwd_dbg;
-#define RTGS_BWD_LAUNCH(KERNEL)                                                                                                      \
+#define RTGS_BWD_LAUNCH(KERNEL, ...)                                                                                                 \
   hipLaunchKernelGGL(KERNEL, dim3(p.gx, p.gy), dim3(BLOCK), 0, st, p, ranges, point_list, splats, out_color, n_contrib, depth_index, \
                      depth_pos, tile_last, dL_dcolor, dL_ddepth, gbase, slot_count, info, grads, touched, tile_mode, t0, tn, dbg,    \
-                     g_bwd_stamps, tc, pre)
-  if (g_bwd_stamps) RTGS_BWD_LAUNCH(blend_bwd_entry_stamped_kernel); else RTGS_BWD_LAUNCH(blend_bwd_entry_kernel);
+                     g_bwd_stamps, tc, pre, ##__VA_ARGS__)
+  if (signs) {
+    if (g_bwd_stamps) RTGS_BWD_LAUNCH(blend_bwd_entry_signs_stamped_kernel, *signs); else RTGS_BWD_LAUNCH(blend_bwd_entry_signs_kernel, *signs);
+  } else {
+    if (g_bwd_stamps) RTGS_BWD_LAUNCH(blend_bwd_entry_stamped_kernel); else RTGS_BWD_LAUNCH(blend_bwd_entry_kernel);
+  }
 #undef RTGS_BWD_LAUNCH
 }
 

@@ -175,6 +175,16 @@ struct TileCache {
   uint16_t* masks;     // [tiles][TILE_RECS]: blocks_reached() of the entry on this tile
   float2* depth_aux;   // [H * W]: 1 / (n_c . r) of the pixel's depth owner, and the depth D = pd / (n_c . r) itself (0, 0: none)
 };
+// The image gradients of the SLAM loss as signs (map_ops.hip: slam_loss_sums_signs_kernel): per pixel one byte, 2 bits per
+// channel (colour 0 1 2, depth; 0 zero, 1 +k, 2 -k), and what the two scalars k follow from.
+struct LossSigns {
+  const uint8_t* signs;   // [H * W]
+  const float* sums;      // the loss header: [0] sum |dC|, [1] sum |dD|, [2] #valid-depth, [3] #mask
+  float cw, dw;           // colour and depth weight
+  float* loss4;           // nullable: the loss values, written by the walk's first workgroup
+};
+// the float a two-bit sign code stands for
+__device__ __forceinline__ float sign_value(uint32_t code, float k) { return code == 1u ? k : (code == 2u ? -k : 0.f); }
 // blend_fwd leaves one word per tile for its backward: bits 0..1 = the walk - 0 tile-uniform strip walk (the tile's 4x4
 // blocks share its list), 1 row-granular walk (each block needs only a fraction of it), 2 entry-per-lane MFMA walk
 // (raster_bwd_mfma.hip); bits 8.. hold the measured share in 1/1000.  See raster_bwd.hip.

@@ -91,6 +91,17 @@ class RasterContext:
         names = ("empty", "single", "bitonic", "radix", "launch", "pass2")
         return {n: dict(tiles=int(out[3 * k]), shortest=int(out[3 * k + 1]), longest=int(out[3 * k + 2])) for k, n in enumerate(names)}
 
+    def set_loss_signs(self, enable: bool):
+        """Map step: the loss leaves one sign byte per pixel and the entry walk rebuilds the image gradients from it (default
+        on, where the SSIM term is off and every tile takes the entry walk); off = the float planes.  Same gradients."""
+        _lib.load().rtgs_raster_set_loss_signs_ctx(self.ptr, int(bool(enable)))
+
+    def loss_signs_stats(self):
+        """Map steps enqueued on this context since it was made, by the path their image gradients took."""
+        out = (C.c_int64 * 2)()
+        _lib.check(_lib.load().rtgs_raster_loss_signs_stats_ctx(self.ptr, out), "rtgs_raster_loss_signs_stats")
+        return dict(signs=int(out[0]), floats=int(out[1]))
+
     def set_speculation(self, enable: bool):
         """Speculative sizing of the forward inside the one-call map step (RTGS_FWD_SPECULATE); default on."""
         _lib.load().rtgs_raster_set_speculation_ctx(self.ptr, int(bool(enable)))
