@@ -524,6 +524,30 @@ int rtgs_mesh_render(const float* vertices, int64_t V, const int32_t* faces, int
                      float cx, float cy, const float* w2c12_host, float near, int32_t small_max, void* scratch, float* depth,
                      int32_t* face, void* stream);
 
+/* The colour pass: a picture of the mesh from a face map rtgs_mesh_render made at this pose, coloured from the vertices or from
+ * a texture atlas.  tests/mesh_shade_reference.py restates it in numpy; the kernel matches it bit for bit.
+ *
+ * vertices, faces, H, W, fx .. cy, w2c12_host, near as rtgs_mesh_render was given them; face_map [H][W] int32.  Exactly one
+ * source: colors [V][3] float32 in 0..1, or uv [F][3][2] float32 (a face's three texture coordinates, x right and y down in
+ * 0..1, as meshing.texture_mesh gives them) with texture [Ht][Wt][3] uint8; the other source's pointers are null.
+ * background3_host: 3 floats on the HOST.  out [3][H][W] float32.  Float32, one correctly rounded operation per step, per pixel
+ * (px, py) with f = face_map[py][px]:
+ *   no face     f < 0, f >= F, or the face setup of rtgs_mesh_render fails for f at this view: the pixel gets the background
+ *   weights     w0 = E(b,c), w1 = E(c,a), w2 = E(a,b) at ((float)px, (float)py), the values whose signs admitted the pixel;
+ *               b0 = w0 iz_a, b1 = w1 iz_b, b2 = w2 iz_c, s = (b0 + b1) + b2, l_k = b_k / s (perspective-correct); an l_k that
+ *               is not finite gives the background
+ *   vertices    per channel c = (l0 c_a + l1 c_b) + l2 c_c, then fminf(fmaxf(c, 0), 1)
+ *   texture     tu = (l0 u_a + l1 u_b) + l2 u_c, tv likewise; X = fminf(fmaxf(tu (float)Wt - 0.5, 0), (float)(Wt - 1)) (a NaN
+ *               gives 0), ix = floorf(X), ix1 = min(ix + 1, Wt - 1), tx = X - ix; Y, iy, iy1, ty likewise with Ht; a texel is
+ *               (float)byte / 255; top = c00 + tx (c10 - c00), bot = c01 + tx (c11 - c01), c = top + ty (bot - top)
+ * One launch on `stream`, one thread per pixel, no host read, no scratch.  Any face map is safe to pass: nothing is read out of
+ * bounds as long as 0 <= faces[i] < V.  F == 0 gives the background everywhere.
+ * Return 0, -1 on a bad argument (a null pointer that is needed; no source or both; uv without texture or the reverse; Ht or Wt
+ * < 1 or > RTGS_MESH_TEXTURE_MAX_SIDE; F or H W >= 2^31; near <= 0 or NaN), -2 on a launch failure. */
+int rtgs_mesh_shade(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face_map, int32_t H, int32_t W,
+                    float fx, float fy, float cx, float cy, const float* w2c12_host, float near, const float* colors, const float* uv,
+                    const uint8_t* texture, int32_t Ht, int32_t Wt, const float* background3_host, float* out, void* stream);
+
 /* ---- mesh distance: the exact distance from a point to the nearest triangle of an indexed mesh, with that triangle's index (no
  * counterpart in the reference; csrc/mesh_distance.hip).  tests/mesh_distance_reference.py restates it in numpy as a brute
  * force over all faces; the kernels match it bit for bit, whatever the grid.

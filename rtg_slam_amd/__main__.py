@@ -24,6 +24,11 @@ would be refused; --texture also bakes a texture atlas for the final mesh from t
 eval_metric/gt_mesh_culled.ply and eval_metric/gt_cull_report.json; --cull-depth mesh decides that against the GT mesh's own
 rendered depth, not the sensor's.  `metric --mesh-depth` renders save_model/mesh_tsdf.ply at every evaluated pose
 (evaluation.MeshRenderer) and writes its depth L1 to eval_metric/mesh_depth_frame_F_iter_I.csv and mesh_depth_report.json.
+`metric --mesh-color {vertex,texture,both}` renders save_model/mesh_tsdf.ply in its vertex colours and / or
+save_model/mesh_textured.obj with its atlas at every evaluated pose (evaluation.MeshRenderer.render_color), scores the pictures
+against the frames' colour (PSNR, MS-SSIM, colour L1 over the whole picture, a hole counting as black; the hit ratio and the colour
+L1 over the hit pixels) and writes eval_metric/mesh_color_frame_F_iter_I.csv and mesh_color_report.json; --mesh-color-save-every K
+also writes every K-th render as eval_metric/mesh_color/frame_XXXX_vertex.png / frame_XXXX_texture.png.
 `mesh --cull-unseen` removes the surface no fused view could see before the mesh is written.
 `metric --mesh --surface-distance` scores save_model/mesh_tsdf.ply against the GT mesh's SURFACE by exact point-to-triangle
 distances (evaluation.eval_mesh_surface), with the normal consistency, and writes eval_metric/surface_distance_frame_F_iter_I.json.
@@ -200,6 +205,8 @@ MESH_TEXTURE_PNG = "mesh_texture.png"
 GT_CULL_PLY = "gt_mesh_culled.ply"
 GT_CULL_REPORT = "gt_cull_report.json"
 MESH_DEPTH_REPORT = "mesh_depth_report.json"
+MESH_COLOR_REPORT = "mesh_color_report.json"
+MESH_COLOR_DIR = "mesh_color"
 
 
 def geometry_ply(args, model_base: str, select_ply: str) -> str:
@@ -391,6 +398,27 @@ def cmd_metric(opts) -> int:
         if not os.path.isfile(mesh_depth_path):
             log(f"--mesh-depth: {mesh_depth_path} does not exist; write it first with `python -m rtg_slam_amd mesh --config {opts.config}`")
             return 2
+    if opts.mesh_color_save_every is not None and (opts.mesh_color is None or opts.mesh_color_save_every < 1):
+        log("--mesh-color-save-every K needs --mesh-color and K >= 1")
+        return 2
+    color_ply, color_obj = None, None
+    if opts.mesh_color in ("vertex", "both"):
+        path = os.path.join(model_base, MESH_PLY)
+        if not os.path.isfile(path):
+            log(f"--mesh-color {opts.mesh_color}: {path} does not exist; write it first with `python -m rtg_slam_amd mesh --config {opts.config}`")
+            return 2
+        color_ply = iof.load_mesh_ply(path, with_colors=True)
+        if color_ply[2] is None:
+            log(f"--mesh-color {opts.mesh_color}: {path} holds no vertex colours; write it again with `python -m rtg_slam_amd mesh "
+                f"--config {opts.config}`")
+            return 2
+    if opts.mesh_color in ("texture", "both"):
+        path = os.path.join(model_base, MESH_TEXTURED_OBJ)
+        if not os.path.isfile(path):
+            log(f"--mesh-color {opts.mesh_color}: {path} does not exist; write it first with `python -m rtg_slam_amd mesh --config "
+                f"{opts.config} --texture`")
+            return 2
+        color_obj = iof.load_textured_obj(path)
     if opts.surface_distance and not opts.mesh:
         log("--surface-distance needs --mesh")
         return 2
@@ -452,13 +480,33 @@ def cmd_metric(opts) -> int:
             if xyz.shape[0] == 0:
                 raise ValueError(f"rtg_slam_amd: {pcd_path} holds no points")
             rec_points = torch.from_numpy(xyz).to(device=device, dtype=torch.float32)
-    if opts.mesh_depth:                      # the mesh lies in the stream's frame: no transform
-        mv, mf = iof.load_mesh_ply(os.path.join(model_base, MESH_PLY))
-        mesh_renderer = evaluation.MeshRenderer(mv, mf, info.camera(), device=device)
+    if opts.mesh_depth or color_ply is not None:       # the mesh lies in the stream's frame: no transform
+        mv, mf, mc = color_ply if color_ply is not None else (*iof.load_mesh_ply(os.path.join(model_base, MESH_PLY)), None)
+        mesh_renderer = evaluation.MeshRenderer(mv, mf, info.camera(), device=device, colors=mc)
+    color_kw, texture_renderer = {}, None
+    if color_obj is not None:                # the OBJ's own vertices and faces: the final mesh, which the PLY need not be
+        texture_renderer = evaluation.MeshRenderer(color_obj[0], color_obj[1], info.camera(), device=device, uv=color_obj[2],
+                                                   texture=color_obj[3])
+        if mesh_renderer is None:
+            mesh_renderer = texture_renderer
+        else:
+            color_kw["mesh_texture_renderer"] = texture_renderer
+    md_dir = os.path.join(args.save_path, "eval_metric")
+    if opts.mesh_color is not None:
+        color_kw["mesh_color"] = opts.mesh_color
+        if opts.mesh_color_save_every is not None:
+            from PIL import Image
+            os.makedirs(os.path.join(md_dir, MESH_COLOR_DIR), exist_ok=True)
+
+            def save_render(i, name, picture):
+                if i % opts.mesh_color_save_every == 0:
+                    q = torch.floor(picture * 255.0 + 0.5).clamp(0.0, 255.0).to(torch.uint8).permute(1, 2, 0).contiguous()
+                    Image.fromarray(q.cpu().numpy()).save(os.path.join(md_dir, MESH_COLOR_DIR, f"frame_{i:04d}_{name}.png"))
+            color_kw["mesh_color_hook"] = save_render
     res = evaluation.evaluate_sequence(mapper, info.camera(), source, poses=poses, args=args, gt_points=gt_points,
                                        dist_thres=[0.03], transform=transform, sample_nums=1_000_000, rec_points=rec_points,
                                        gt_cull=gt_cull, mesh_renderer=mesh_renderer, gt_mesh_renderer=gt_mesh_renderer,
-                                       gt_cull_depth=opts.cull_depth)
+                                       gt_cull_depth=opts.cull_depth, **color_kw)
     if gt_cull is not None:
         cull_dir = os.path.join(args.save_path, "eval_metric")
         os.makedirs(cull_dir, exist_ok=True)
@@ -471,8 +519,7 @@ def cmd_metric(opts) -> int:
         with open(os.path.join(cull_dir, GT_CULL_REPORT), "w") as fo:
             json.dump(report, fo, indent=1, default=float)
         log(f"geometry eval gt: culled {report['F_kept']} of {report['F']} faces over {report['frames']} frames -> {cull_path}")
-    if mesh_renderer is not None:
-        md_dir = os.path.join(args.save_path, "eval_metric")
+    if opts.mesh_depth:
         os.makedirs(md_dir, exist_ok=True)
         md_path = os.path.join(md_dir, f"mesh_depth_frame_{mapper.time}_iter_{test_iter}.csv")
         rows = res["mesh_depth_rows"]
@@ -487,7 +534,29 @@ def cmd_metric(opts) -> int:
             json.dump(md, fo, indent=1, default=float)
         log(f"mesh depth: L1 {100 * md.get('mesh_depth_l1', float('nan')):.3f} cm over {md.get('mesh_valid_ratio', float('nan')):.4f} "
             f"of the pixels, {len(rows)} frames -> {md_path}")
-    if opts.surface_distance:                # the reconstructed mesh against the GT surface (the culled one with --cull-gt)
+    if opts.mesh_color is not None:
+        os.makedirs(md_dir, exist_ok=True)
+        mc_path = os.path.join(md_dir, f"mesh_color_frame_{mapper.time}_iter_{test_iter}.csv")
+        rows = res["mesh_color_rows"]
+        suffixes = [s for s, name in (("", "vertex"), ("_tex", "texture")) if opts.mesh_color in (name, "both")]
+        keys = ["frame"] + [k + s for s in suffixes for k in ("mesh_hit_ratio", "mesh_psnr", "mesh_ssim", "mesh_color_l1", "mesh_color_l1_hit")]
+        with open(mc_path, "w") as fo:
+            fo.write(",".join(keys) + "\n")
+            fo.write("".join(",".join(repr(r[k]) for k in keys) + "\n" for r in rows))
+        mc = dict(res["mesh_color_mean"])
+        mc.update(frames=len(rows), source=opts.mesh_color, near=mesh_renderer.near,
+                  mesh=os.path.join(model_base, MESH_PLY) if color_ply is not None else None,
+                  textured_mesh=os.path.join(model_base, MESH_TEXTURED_OBJ) if color_obj is not None else None,
+                  atlas_size=[int(color_obj[3].shape[1]), int(color_obj[3].shape[0])] if color_obj is not None else None,
+                  render_s=mesh_renderer.seconds if color_ply is not None else None,
+                  texture_render_s=texture_renderer.seconds if texture_renderer is not None else None,
+                  saved_every=opts.mesh_color_save_every)
+        with open(os.path.join(md_dir, MESH_COLOR_REPORT), "w") as fo:
+            json.dump(mc, fo, indent=1, default=float)
+        db = lambda k: f"{mc[k]:.3f} dB" if k in mc else "-"
+        log(f"mesh colour: PSNR {db('mesh_psnr')} (vertex) / {db('mesh_psnr_tex')} (texture), hit ratio "
+            f"{mc.get('mesh_hit_ratio', mc.get('mesh_hit_ratio_tex', float('nan'))):.4f}, {len(rows)} frames -> {mc_path}")
+    if opts.surface_distance:               # the reconstructed mesh against the GT surface (the culled one with --cull-gt)
         gv, gf = gt_cull.mesh() if gt_cull is not None else iof.load_mesh_ply(info.mesh_path)
         mv, mf = iof.load_mesh_ply(mesh_path)
         reports = {}
@@ -601,6 +670,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="render save_model/mesh_tsdf.ply at every evaluated pose and write its depth L1 against the sensor depth "
                         "(and against the GT mesh rendered at the GT pose, where there is one) to eval_metric/mesh_depth_frame_F_iter_I.csv "
                         "and eval_metric/mesh_depth_report.json")
+    m.add_argument("--mesh-color", choices=("vertex", "texture", "both"), default=None,
+                   help="render the mesh in colour at every evaluated pose and score it against the frame's colour: save_model/"
+                        "mesh_tsdf.ply in its vertex colours, save_model/mesh_textured.obj (written by `mesh --texture`) with its "
+                        "atlas, or both; writes eval_metric/mesh_color_frame_F_iter_I.csv and eval_metric/mesh_color_report.json")
+    m.add_argument("--mesh-color-save-every", type=int, default=None, metavar="K",
+                   help="with --mesh-color: also write every K-th colour render (K >= 1) as an 8-bit PNG, "
+                        "eval_metric/mesh_color/frame_XXXX_vertex.png or frame_XXXX_texture.png")
     m.add_argument("--surface-distance", action="store_true",
                    help="with --mesh: score save_model/mesh_tsdf.ply against the GT SURFACE (with --cull-gt: the culled one) by exact "
                         "point-to-triangle distances - accuracy from 1 M samples of the mesh to the GT surface, completion from 1 M "

@@ -299,6 +299,8 @@ _SIGNATURES = {
     "rtgs_mesh_render_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "rtgs_mesh_render": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                    _P, C.c_float, C.c_int32, _P, _P, _P, _P]),
+    "rtgs_mesh_shade": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                  _P, C.c_float, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     # mesh distance
     "rtgs_mesh_distance_queue_bytes": (C.c_size_t, [C.c_int64]),
     "rtgs_mesh_distance_count": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P, C.c_float, C.c_int32, _P, _P, _P]),

@@ -19,6 +19,9 @@
 // smallest key (bits(z) << 32 | face) wins whatever order the faces arrive in: the picture depends neither on the queue's order
 // nor on small_max.
 //
+// The colour pass (rtgs_mesh_shade) is a fifth kernel in a call of its own, after the face map exists: shade_kernel, below the
+// four above, with its definition in tests/mesh_shade_reference.py.
+//
 // Index range: the caller guarantees 0 <= faces[i] < V (rtg_slam_amd/evaluation.py checks it once, when the mesh is given).
 // Element indices are 64-bit: 3 V and 3 F can pass 2^31.
 #include "../../include/rtgs_slam.h"
@@ -178,6 +181,71 @@ __global__ void __launch_bounds__(NT) resolve_kernel(const unsigned long long* _
 
 inline size_t keys_bytes(int32_t H, int32_t W) { return (size_t)H * (size_t)W * sizeof(unsigned long long); }
 
+// ---- the colour pass (rtgs_mesh_shade; tests/mesh_shade_reference.py is its definition) ----
+// One thread per pixel of a finished face map, a wave per 64 consecutive pixels of one row: the face's setup again (the same
+// code as the rasteriser's, so the very edge values whose signs admitted the pixel), the perspective-correct barycentrics, then
+// the three corner colours, or four texels of the atlas.  No LDS, no atomics; every read is guarded by 0 <= face < F, the
+// caller's 0 <= faces[i] < V and the clamp of the texel coordinates, so any face map is safe.
+
+struct Source {
+  const float* colors;         // [V][3], or null: the texture is the source
+  const float* uv;             // [F][3][2], y down
+  const uint8_t* texture;      // [Ht][Wt][3]
+  int Ht, Wt;
+  float bg[3];
+};
+
+__device__ __forceinline__ float clamp_to(float x, float hi) { return fminf(fmaxf(x, 0.0f), hi); }      // NaN gives 0
+
+__device__ __forceinline__ float texel(const uint8_t* __restrict__ texture, int64_t Wt, int y, int x, int c) {
+  return (float)texture[((int64_t)y * Wt + x) * 3 + c] / 255.0f;
+}
+
+__global__ void __launch_bounds__(NT) shade_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces, int64_t F, View f,
+                                                   const int32_t* __restrict__ face_map, Source src, int32_t chunks,
+                                                   float* __restrict__ out) {
+  const int64_t wave = ((int64_t)blockIdx.x * NT + threadIdx.x) / WAVE;                    // (row, chunk of 64 columns)
+  const int64_t row = wave / chunks;
+  const int px = (int)(wave % chunks) * WAVE + (int)(threadIdx.x & (WAVE - 1));
+  if (row >= f.H || px >= f.W) return;
+  const int py = (int)row;
+  const int64_t n = (int64_t)f.H * f.W, p = row * f.W + px;
+  float c[3] = {src.bg[0], src.bg[1], src.bg[2]};
+  const int64_t i = face_map[p];
+  Face t;
+  if (i >= 0 && i < F && setup_face(vertices, faces, i, f, &t)) {
+    const float x = (float)px, y = (float)py;
+    const float b0 = edge_at(t.e0, x, y) * t.iza, b1 = edge_at(t.e1, x, y) * t.izb, b2 = edge_at(t.e2, x, y) * t.izc;
+    const float s = (b0 + b1) + b2;
+    const float l0 = b0 / s, l1 = b1 / s, l2 = b2 / s;
+    if (fabsf(l0) < INFINITY && fabsf(l1) < INFINITY && fabsf(l2) < INFINITY) {            // false for NaN too
+      if (src.colors) {
+        const int64_t va = faces[i * 3], vb = faces[i * 3 + 1], vc = faces[i * 3 + 2];
+        for (int k = 0; k < 3; ++k)
+          c[k] = clamp_to((l0 * src.colors[va * 3 + k] + l1 * src.colors[vb * 3 + k]) + l2 * src.colors[vc * 3 + k], 1.0f);
+      } else {
+        const float* q = src.uv + i * 6;
+        const float tu = (l0 * q[0] + l1 * q[2]) + l2 * q[4], tv = (l0 * q[1] + l1 * q[3]) + l2 * q[5];
+        const float X = clamp_to(tu * (float)src.Wt - 0.5f, (float)(src.Wt - 1));
+        const float Y = clamp_to(tv * (float)src.Ht - 0.5f, (float)(src.Ht - 1));
+        const float fx0 = floorf(X), fy0 = floorf(Y);
+        const float tx = X - fx0, ty = Y - fy0;
+        const int ix = (int)fx0, iy = (int)fy0;                                            // 0 .. Wt - 1, 0 .. Ht - 1
+        const int ix1 = ix + 1 < src.Wt ? ix + 1 : src.Wt - 1, iy1 = iy + 1 < src.Ht ? iy + 1 : src.Ht - 1;
+        for (int k = 0; k < 3; ++k) {
+          const float c00 = texel(src.texture, src.Wt, iy, ix, k), c10 = texel(src.texture, src.Wt, iy, ix1, k);
+          const float c01 = texel(src.texture, src.Wt, iy1, ix, k), c11 = texel(src.texture, src.Wt, iy1, ix1, k);
+          const float top = c00 + tx * (c10 - c00), bot = c01 + tx * (c11 - c01);
+          c[k] = top + ty * (bot - top);
+        }
+      }
+    }
+  }
+  out[p] = c[0];
+  out[n + p] = c[1];
+  out[2 * n + p] = c[2];
+}
+
 }  // namespace rtgs_mesh_render_k
 
 extern "C" {
@@ -216,6 +284,31 @@ int rtgs_mesh_render(const float* vertices, int64_t V, const int32_t* faces, int
     hipLaunchKernelGGL(large_kernel, dim3(large_blocks), dim3(NT), 0, s, vertices, faces, F, f, keys, counter, queue);
   }
   hipLaunchKernelGGL(resolve_kernel, dim3(pixel_blocks), dim3(NT), 0, s, keys, n, depth, face);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int rtgs_mesh_shade(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face_map, int32_t H, int32_t W,
+                    float fx, float fy, float cx, float cy, const float* w2c12_host, float near, const float* colors, const float* uv,
+                    const uint8_t* texture, int32_t Ht, int32_t Wt, const float* background3_host, float* out, void* stream) {
+  if (V < 0 || F < 0 || F >= 0x80000000LL || H <= 0 || W <= 0 || (int64_t)H * W >= 0x80000000LL) return -1;
+  if (!w2c12_host || !(near > 0.0f) || !face_map || !background3_host || !out) return -1;
+  if (F > 0 && (!faces || !vertices || V == 0)) return -1;
+  if ((uv != nullptr) != (texture != nullptr)) return -1;
+  if ((colors != nullptr) == (uv != nullptr)) return -1;                                   // one source, not none and not both
+  if (uv && (Ht < 1 || Wt < 1 || Ht > RTGS_MESH_TEXTURE_MAX_SIDE || Wt > RTGS_MESH_TEXTURE_MAX_SIDE)) return -1;
+  View f;
+  for (int k = 0; k < 12; ++k) f.m[k] = w2c12_host[k];
+  f.fx = fx; f.fy = fy; f.cx = cx; f.cy = cy;
+  f.H = H; f.W = W;
+  f.near = near;
+  Source src;
+  src.colors = colors; src.uv = uv; src.texture = texture;
+  src.Ht = uv ? Ht : 1; src.Wt = uv ? Wt : 1;
+  for (int k = 0; k < 3; ++k) src.bg[k] = background3_host[k];
+  const int32_t chunks = (W + WAVE - 1) / WAVE;                                            // waves per row
+  unsigned blocks;
+  if (!grid_for((int64_t)H * chunks * WAVE, &blocks)) return -1;                           // H chunks <= H W < 2^31 waves
+  hipLaunchKernelGGL(shade_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, vertices, faces, F, f, face_map, src, chunks, out);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -17,7 +17,9 @@
     VisibilityCull     (no counterpart)       the part of the GT mesh the evaluated frames saw: per vertex, against the sensor
                                               depth, at the GT poses (include/rtgs_slam.h, "visibility")
     MeshRenderer       (no counterpart)       the depth and face maps of a triangle mesh at a pose (include/rtgs_slam.h, "mesh
-                                              render"); mesh_depth_metrics: the depth L1 of such a map
+                                              render"); mesh_depth_metrics: the depth L1 of such a map; render_color: the
+                                              mesh in its vertex colours or its baked atlas, mesh_color_metrics: its PSNR,
+                                              MS-SSIM and colour L1 against a frame
 
 Each metric call reads its float64 result vector from the device once; that read is its only synchronisation.  The results
 are bitwise reproducible run to run (fixed-order reductions, no float atomics).  There is no CPU path."""
@@ -475,6 +477,7 @@ class VisibilityCull:
 MESH_RENDER_NEAR = 0.05
 # Boxes of more than this many pixels go to the wave path of csrc/mesh_render.hip (DESIGN.md §4h has the measurement).
 MESH_RENDER_SMALL_MAX = 16
+MESH_TEXTURE_MAX_SIDE = 16384                    # RTGS_MESH_TEXTURE_MAX_SIDE of include/rtgs_slam.h
 
 
 class MeshRenderer:
@@ -487,10 +490,17 @@ class MeshRenderer:
     vertices [V,3] and faces [F,3] are arrays or device tensors, cast to float32 / int32 and checked once, here, as
     VisibilityCull does; `transform @ c2w` is the camera in the mesh's frame.  A face with a corner at or behind `near` metres
     is dropped whole, not clipped: a camera within `near` of a large triangle sees a hole there.  small_max: the largest pixel
-    box one thread walks (larger faces take a wave each); it changes the time only, never the picture."""
+    box one thread walks (larger faces take a wave each); it changes the time only, never the picture.
+
+        r = MeshRenderer(vertices, faces, cam, colors=colors, uv=uv, texture=image)
+        color, depth, face = r.render_color(c2w, source="texture")        # [3,H,W] float32 in 0..1
+
+    colors [V,3] float32 in 0..1, uv [F,3,2] float32 (y down, as meshing.texture_mesh and load_textured_obj give it) and
+    texture [Ht,Wt,3] uint8 are the colour sources of render_color, cast and checked once, here; without them the object and
+    render() are what they are."""
 
     def __init__(self, vertices, faces, cam, transform=None, near: float = MESH_RENDER_NEAR, small_max: Optional[int] = None,
-                 device=None):
+                 device=None, colors=None, uv=None, texture=None):
         for t in (vertices, faces):
             if torch.is_tensor(t) and not t.is_cuda:
                 raise RuntimeError("rtg_slam_amd.evaluation: tensors must live on a HIP device; this build has no CPU path.")
@@ -526,9 +536,89 @@ class MeshRenderer:
         self.transform = np.eye(4) if transform is None else np.asarray(transform, dtype=np.float64).reshape(4, 4)
         n = _lib.load().rtgs_mesh_render_scratch_bytes(V, int(self.faces.shape[0]), H, W)
         self._scratch = torch.empty((n + 7) // 8, dtype=torch.int64, device=self.device)      # once; 8-byte aligned keys
+        self.colors, self.uv, self.texture = self._color_sources(colors, uv, texture, V, int(self.faces.shape[0]))
         self.renders = 0
         self._events: List = []
         self._seconds = 0.0
+
+    def _color_sources(self, colors, uv, texture, V: int, F: int):
+        """The colour sources, cast and checked once -> (colors [V,3] float32, uv [F,3,2] float32, texture [Ht,Wt,3] uint8) on
+        the device, None for what was not given."""
+        def up(name, a, shape, dtypes, dt):
+            if torch.is_tensor(a) and not a.is_cuda:
+                raise RuntimeError("rtg_slam_amd.evaluation: tensors must live on a HIP device; this build has no CPU path.")
+            t = a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+            if t.dtype not in dtypes:
+                raise ValueError(f"rtg_slam_amd.evaluation: {name} must be {dtypes[0]}, got {t.dtype}")
+            if t.dim() != len(shape) or any(want is not None and int(got) != want for got, want in zip(t.shape, shape)):
+                want = "[" + ",".join("*" if k is None else str(k) for k in shape) + "]"
+                raise ValueError(f"rtg_slam_amd.evaluation: {name} must have the shape {want}, got {tuple(t.shape)}")
+            return t.to(device=self.device, dtype=dt).contiguous()
+        floats = (torch.float32, torch.float64)
+        if colors is not None:
+            colors = up("colors", colors, (V, 3), floats, torch.float32)
+        if (uv is None) != (texture is None):
+            raise ValueError(f"rtg_slam_amd.evaluation: {'texture' if uv is None else 'uv'} needs "
+                             f"{'uv' if uv is None else 'texture'} beside it")
+        if uv is not None:
+            uv = up("uv", uv, (F, 3, 2), floats, torch.float32)
+            texture = up("texture", texture, (None, None, 3), (torch.uint8,), torch.uint8)
+            Ht, Wt = int(texture.shape[0]), int(texture.shape[1])
+            if not (1 <= Ht <= MESH_TEXTURE_MAX_SIDE and 1 <= Wt <= MESH_TEXTURE_MAX_SIDE):
+                raise ValueError(f"rtg_slam_amd.evaluation: texture must be 1..{MESH_TEXTURE_MAX_SIDE} texels on a side, got {Ht}x{Wt}")
+        return colors, uv, texture
+
+    def _view(self, c2w):
+        """-> the 12 floats of inv(transform @ c2w) (inverted in float64 on the host, then cast to float32), H, W, fx .. cy."""
+        c2w = c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else np.asarray(c2w)
+        if c2w.size != 16:
+            raise ValueError(f"rtg_slam_amd.evaluation: c2w must be a 4x4 matrix, got shape {tuple(c2w.shape)}")
+        w2c = np.linalg.inv(self.transform @ c2w.astype(np.float64).reshape(4, 4)).astype(np.float32)
+        m = np.ascontiguousarray(w2c.reshape(-1)[:12])
+        fx, fy, cx, cy = (float(np.float32(k)) for k in (self.cam.fx, self.cam.fy, self.cam.cx, self.cam.cy))
+        return (C.c_float * 12)(*m.tolist()), int(self.cam.H), int(self.cam.W), fx, fy, cx, cy
+
+    def render_color(self, c2w, source: str = "vertex", background=(0.0, 0.0, 0.0)):
+        """-> (color [3,H,W] float32, depth [H,W] float32, face [H,W] int32), new tensors: render()'s maps, then the colour pass
+        (rtgs_mesh_shade) with the same float32 matrix, bit for bit tests/mesh_shade_reference.py.  source "vertex": the
+        perspective-correct blend of the face's three `colors`, clamped to 0..1; "texture": `texture` sampled bilinearly at the
+        blend of the face's three `uv` (y down).  A pixel no face covers gets `background`.  No anti-aliasing, no mip levels, no
+        lighting.  No synchronisation."""
+        if source not in ("vertex", "texture"):
+            raise ValueError(f"rtg_slam_amd.evaluation: source must be 'vertex' or 'texture', got {source!r}")
+        if source == "vertex" and self.colors is None:
+            raise ValueError("rtg_slam_amd.evaluation: source 'vertex' needs the renderer built with colors")
+        if source == "texture" and self.uv is None:
+            raise ValueError("rtg_slam_amd.evaluation: source 'texture' needs the renderer built with uv and texture")
+        bg = np.asarray(background, dtype=np.float32).reshape(-1)
+        if bg.size != 3:
+            raise ValueError(f"rtg_slam_amd.evaluation: background must hold 3 values, got {bg.size}")
+        m, H, W, fx, fy, cx, cy = self._view(c2w)
+        V, F = int(self.vertices.shape[0]), int(self.faces.shape[0])
+        depth = torch.empty(H, W, dtype=torch.float32, device=self.device)
+        face = torch.empty(H, W, dtype=torch.int32, device=self.device)
+        color = torch.empty(3, H, W, dtype=torch.float32, device=self.device)
+        # an empty tensor has no address: a source of no rows is still named by a pointer the kernel never follows
+        named = lambda t: _p(t) if t.numel() else _p(self._scratch)
+        null = C.c_void_p(None)
+        vertex = source == "vertex"
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            rc = lib.rtgs_mesh_render(_p(self.vertices), V, _p(self.faces), F, H, W, fx, fy, cx, cy, m, self.near, self.small_max,
+                                      _p(self._scratch), _p(depth), _p(face), _stream(self.device))
+            _lib.check(rc, "rtgs_mesh_render")
+            rc = lib.rtgs_mesh_shade(
+                _p(self.vertices), V, _p(self.faces), F, _p(face), H, W, fx, fy, cx, cy, m, self.near,
+                named(self.colors) if vertex else null, null if vertex else named(self.uv), null if vertex else _p(self.texture),
+                1 if vertex else int(self.texture.shape[0]), 1 if vertex else int(self.texture.shape[1]),
+                (C.c_float * 3)(*bg.tolist()), _p(color), _stream(self.device))
+            b.record()
+        _lib.check(rc, "rtgs_mesh_shade")
+        self._events.append((a, b))
+        self.renders += 1
+        return color, depth, face
 
     def render(self, c2w):
         """-> (depth [H,W] float32, face [H,W] int32), new tensors.  c2w: the camera's pose as the stream gives it; the matrix
@@ -591,6 +681,41 @@ def mesh_depth_metrics(mesh_depth: torch.Tensor, ref_depth: torch.Tensor, min_de
     return _mesh_depth_result(_mesh_depth_sums(mesh_depth, ref_depth, min_depth, max_depth).cpu().tolist(), mesh_depth.numel())
 
 
+def _mesh_color_vector(color: torch.Tensor, gt_color: torch.Tensor, face: torch.Tensor, with_ms_ssim: bool) -> torch.Tensor:
+    """-> float64 [PICTURE_OUT + 2] on the device: rtgs_eval_picture's vector of the whole picture, the number of hit pixels
+    (face >= 0), the sum of |color - gt_color| over their three channels."""
+    dev = _dev(color, gt_color, face)
+    if color.dtype != torch.float32 or color.dim() != 3 or color.shape[0] != 3:
+        raise ValueError(f"rtg_slam_amd.evaluation: color must be [3,H,W] float32, got {tuple(color.shape)} {color.dtype}")
+    H, W = int(color.shape[1]), int(color.shape[2])
+    if gt_color.numel() != 3 * H * W or face.numel() != H * W or H * W == 0 or gt_color.device != dev or face.device != dev:
+        raise ValueError(f"rtg_slam_amd.evaluation: gt_color {tuple(gt_color.shape)} and face {tuple(face.shape)} do not fit a "
+                         f"{H}x{W} picture on one device")
+    c, g = color.detach(), gt_color.detach().float().reshape(3, H, W)
+    none = torch.zeros(H, W, dtype=torch.float32, device=dev)                  # no depth is scored here
+    pic = picture_metrics(c, g, none, none, none.to(torch.int32), 0.0, 1.0, with_ms_ssim)
+    hit = face.detach().reshape(1, H, W) >= 0
+    diff = torch.where(hit, (c - g).abs(), torch.zeros_like(c))                # float32 differences, summed in float64
+    return torch.cat([pic, torch.stack([hit.sum().to(torch.float64), diff.sum(dtype=torch.float64)])])
+
+
+def _mesh_color_result(v, n_pixels: int, with_ms_ssim: bool, suffix: str = "") -> Dict:
+    n, s = float(v[PICTURE_OUT]), float(v[PICTURE_OUT + 1])
+    return {"mesh_hit_ratio" + suffix: n / n_pixels, "mesh_psnr" + suffix: v[OUT_PSNR],
+            "mesh_ssim" + suffix: v[OUT_MS_SSIM] if with_ms_ssim else None, "mesh_color_l1" + suffix: v[OUT_COLOR_L1],
+            "mesh_color_l1_hit" + suffix: s / (3.0 * n) if n else 0.0}
+
+
+def mesh_color_metrics(color: torch.Tensor, gt_color: torch.Tensor, face: torch.Tensor, with_ms_ssim: bool = True) -> Dict:
+    """A colour render of a mesh (MeshRenderer.render_color: color [3,H,W] float32, face [H,W]) against a frame's colour
+    [3,H,W] in 0..1.  "mesh_hit_ratio" is the share of pixels with face >= 0.  "mesh_psnr", "mesh_ssim" (MS-SSIM; None without
+    with_ms_ssim) and "mesh_color_l1" cover the WHOLE picture as eval_picture scores the map's (rtgs_eval_picture): a hole counts
+    as the background it was given, as an un-rendered pixel counts against the map.  "mesh_color_l1_hit" is the float64 mean of
+    the float32 |color - gt_color| over the hit pixels' channels only (0 without any).  One host read."""
+    v = _mesh_color_vector(color, gt_color, face, with_ms_ssim).cpu().tolist()
+    return _mesh_color_result(v, int(face.numel()), with_ms_ssim)
+
+
 def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: Optional[float] = None,
                max_depth: Optional[float] = None, renderer=None, run_picture: bool = True, run_pcd: bool = False,
                gt_points=None, dist_thres: Sequence[float] = (0.03,), sample_nums: int = 1_000_000, transform=None,
@@ -617,7 +742,9 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
                       transform=None, sample_nums: int = 1_000_000, generator: Optional[torch.Generator] = None,
                       with_ms_ssim: bool = True, rec_points: Optional[torch.Tensor] = None,
                       gt_cull: Optional["VisibilityCull"] = None, mesh_renderer: Optional["MeshRenderer"] = None,
-                      gt_mesh_renderer: Optional["MeshRenderer"] = None, gt_cull_depth: str = "sensor") -> Dict:
+                      gt_mesh_renderer: Optional["MeshRenderer"] = None, gt_cull_depth: str = "sensor",
+                      mesh_color: Optional[str] = None, mesh_texture_renderer: Optional["MeshRenderer"] = None,
+                      mesh_color_hook=None) -> Dict:
     """metric.py:137-219 over a finished map.  `stream` yields (depth [H,W] metres, colour [3,H,W], GT c2w) as run_sequence's
     does; frame i is rendered at poses[i] (the estimated trajectory, e.g. tracker.pose_es) or, without poses, at its GT pose,
     by a Renderer whose opaque threshold is args.renderer_opaque_threshold_eval (metric.py:138).  With gt_points, the
@@ -633,11 +760,23 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
     max_depth) and, with gt_mesh_renderer, against the GT mesh rendered at the GT pose (keys ending in _gt).  These rows are
     returned apart, under "mesh_depth_rows" and "mesh_depth_mean", and read from the device once, after the last frame: "rows"
     and "mean" are what they are without the mesh renderers.
+    With mesh_color ("vertex", "texture" or "both"; needs mesh_renderer) the mesh is also rendered in colour at that pose
+    (MeshRenderer.render_color, black background) and scored against the frame's colour (mesh_color_metrics): the vertex source
+    by mesh_renderer, the texture source - its keys end in _tex - by mesh_texture_renderer when one is given (the textured mesh
+    need not be the mesh whose depth is scored), else by mesh_renderer.  These rows come under "mesh_color_rows" and
+    "mesh_color_mean", read from the device once, after the last frame; everything else is what it is without mesh_color.
+    mesh_color_hook(i, source, color) receives every colour render ([3,H,W] on the device) as it is made.
     Returns {"rows": one dict per frame (with "frame" and "iter"), "mean": the mean row of metric.py:205-211}."""
     if gt_cull_depth not in ("sensor", "mesh"):
         raise ValueError(f"rtg_slam_amd.evaluation: gt_cull_depth must be 'sensor' or 'mesh', got {gt_cull_depth!r}")
     if gt_cull_depth == "mesh" and (gt_cull is None or gt_mesh_renderer is None):
         raise ValueError("rtg_slam_amd.evaluation: gt_cull_depth='mesh' needs gt_cull and gt_mesh_renderer")
+    if mesh_color not in (None, "vertex", "texture", "both"):
+        raise ValueError(f"rtg_slam_amd.evaluation: mesh_color must be None, 'vertex', 'texture' or 'both', got {mesh_color!r}")
+    if mesh_color is not None and mesh_renderer is None:
+        raise ValueError("rtg_slam_amd.evaluation: mesh_color needs mesh_renderer")
+    color_sources = [] if mesh_color is None else [s for s in ("vertex", "texture") if mesh_color in (s, "both")]
+    color_vectors: List[torch.Tensor] = []
     from .mapping import Frame
     from .render import Renderer
     args = mapper.args if args is None else args
@@ -661,6 +800,15 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
             if gt_mesh_depth is not None:
                 sums.append(_mesh_depth_sums(mesh_depth, gt_mesh_depth, args.min_depth, args.max_depth))
             mesh_sums.append(torch.cat(sums))
+            per_source = []
+            for s in color_sources:
+                r = mesh_texture_renderer if s == "texture" and mesh_texture_renderer is not None else mesh_renderer
+                mesh_picture, _, mesh_face = r.render_color(poses[i] if poses is not None else gt_c2w, source=s)
+                if mesh_color_hook is not None:
+                    mesh_color_hook(i, s, mesh_picture)
+                per_source.append(_mesh_color_vector(mesh_picture, color, mesh_face, with_ms_ssim))
+            if per_source:
+                color_vectors.append(torch.stack(per_source))
         row = eval_frame(mapper, frame, color, depth, args.min_depth, args.max_depth, renderer=renderer,
                          with_ms_ssim=with_ms_ssim)
         row["frame"] = i
@@ -688,4 +836,15 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
         keys = [k for k in (mesh_rows[0] if mesh_rows else {}) if k != "frame"]
         res["mesh_depth_rows"] = mesh_rows
         res["mesh_depth_mean"] = {k: float(np.mean([r[k] for r in mesh_rows])) for k in keys}
+    if color_sources:
+        n_pixels = int(cam.H) * int(cam.W)
+        color_rows = []
+        for i, per_source in enumerate(torch.stack(color_vectors).cpu().tolist() if color_vectors else []):   # the one host read
+            row = {"frame": i}
+            for s, v in zip(color_sources, per_source):
+                row.update(_mesh_color_result(v, n_pixels, with_ms_ssim, "_tex" if s == "texture" else ""))
+            color_rows.append(row)
+        keys = [k for k in (color_rows[0] if color_rows else {}) if k != "frame" and color_rows[0][k] is not None]
+        res["mesh_color_rows"] = color_rows
+        res["mesh_color_mean"] = {k: float(np.mean([r[k] for r in color_rows])) for k in keys}
     return res
