@@ -120,6 +120,31 @@ int rtgs_icp_fill_model_depth(float* render_depth, const float* frame_depth, con
 
 size_t rtgs_icp_scratch_bytes(void);
 
+/* ---- RGB-D refinement (csrc/rgbd_align.hip) -------------------------------------------------------------------------------
+ * A separate stage after the tracker, no counterpart in the reference: the normal equations of the joint point-to-plane +
+ * photometric alignment of a source frame (vertex, normal, intensity maps) against a target, at `pose`.  Conventions are
+ * rtgs_icp_step's (pose: device float[16], source -> target; K: device float[9] of THIS level; Jacobian ordered rotation,
+ * translation).  tests/rgbd_align_reference.py is the definition - gates, float32 per-pixel terms, float64 sums and their
+ * order - and is matched bit for bit; no atomics: two runs give the same bits.  Nothing here touches the tracker's kernels. */
+
+/* color[3,H,W] -> intensity levels out_host[l] ([H >> (L-1-l), W >> (L-1-l)], caller-allocated, coarsest first, the sizes of the
+ * ICP pyramids): grey = (0.299 R + 0.587 G) + 0.114 B at the finest level, each coarser level the mean
+ * ((a + b) + (c + d)) * 0.25 of the 2 x 2 block at (2y, 2x) of the next finer one; odd rows / columns left over are dropped.
+ * -1: null pointer, non-positive size, H W >= 2^31, levels outside 1..RTGS_ICP_MAX_LEVELS or a level of size 0. */
+int rtgs_rgbd_intensity_pyramid(const float* color, int32_t H, int32_t W, int32_t levels, float* const* out_host, void* stream);
+
+#define RTGS_RGBD_ALIGN_OUT 31
+/* sums_out[31] (device, float64): H upper triangle row-major (21), b (6), sum r_G^2, geometric count, sum w r_I^2, photometric
+ * count, with H = sum J_G J_G^T + w lambda^2 J_I J_I^T and b = sum J_G r_G + w lambda^2 J_I r_I; lambda = photo_weight
+ * (metres per unit of intensity), w the Huber weight of r_I at `huber`.  Two launches (a workgroup per 1024 pixels, then one
+ * over the chunk sums); scratch: device, >= rtgs_rgbd_align_scratch_bytes(H, W).
+ * -1 before anything is launched: H W >= 2^31, non-positive size, null pointer, negative huber or photo_weight. */
+int rtgs_rgbd_align_accumulate(const float* vertex_src, const float* normal_src, const float* intensity_src,
+                               const float* vertex_tgt, const float* normal_tgt, const float* intensity_tgt, int32_t H, int32_t W,
+                               const float* K, const float* pose, float distance_threshold, float cos_threshold,
+                               float photo_weight, float huber, double* sums_out, void* scratch, void* stream);
+size_t rtgs_rgbd_align_scratch_bytes(int32_t H, int32_t W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,9 @@ distances (evaluation.eval_mesh_surface), with the normal consistency, and write
 (evaluation.align_to_gt: point-to-plane ICP on exact nearest faces), scores it again under that transform and writes the transform,
 the registration report and the unaligned and aligned figures to eval_metric/aligned_frame_F_iter_I.json: the transform measures
 the tracker's drift, the aligned figures the shape.
+`slam --rgbd-refine [--rgbd-refine-photo-weight L] [--rgbd-refine-huber D]` refines every ICP pose with the joint photometric and
+geometric RGB-D alignment (rtg_slam_amd.rgbd_align) against the previous frame's colour; the keys go into config.yaml only when
+given and run_report.json gains `rgbd_refine` (mean iterations, photometric inliers and ms per frame).
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -118,6 +121,19 @@ def cmd_slam(opts) -> int:
     _apply_resolution_scale(args, opts)
     if opts.frames is not None:
         args.frame_num = int(opts.frames)
+    for flag, value in (("--rgbd-refine-photo-weight", opts.rgbd_refine_photo_weight), ("--rgbd-refine-huber", opts.rgbd_refine_huber)):
+        if value is not None and not value > 0:
+            log(f"{flag} must be positive, not {value}")
+            return 2
+        if value is not None and not opts.rgbd_refine:
+            log(f"{flag} needs --rgbd-refine")
+            return 2
+    if opts.rgbd_refine:
+        args.rgbd_refine = True
+        if opts.rgbd_refine_photo_weight is not None:
+            args.rgbd_refine_photo_weight = float(opts.rgbd_refine_photo_weight)
+        if opts.rgbd_refine_huber is not None:
+            args.rgbd_refine_huber = float(opts.rgbd_refine_huber)
     save_path = args.save_path
     if os.path.isdir(save_path) and os.listdir(save_path):
         if not opts.overwrite:
@@ -128,6 +144,10 @@ def cmd_slam(opts) -> int:
         os.makedirs(os.path.join(save_path, sub), exist_ok=True)
     if getattr(args, "use_orb_backend", False):
         log("use_orb_backend: the ORB-SLAM2 back end is not available; tracking with ICP only")
+    if getattr(args, "rgbd_refine", False):
+        from . import rgbd_align
+        log(f"rgbd refine: on (photo weight {getattr(args, 'rgbd_refine_photo_weight', rgbd_align.DEFAULT_PHOTO_WEIGHT):g}, "
+            f"huber {getattr(args, 'rgbd_refine_huber', rgbd_align.DEFAULT_HUBER):g})")
     if "device_list" in vars(args):
         log(f"device_list {args.device_list} ignored; running on {opts.device}")
     device = torch.device(opts.device)
@@ -642,6 +662,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="overrides resolution_scales[0]: the frames are resized to 1/S of their size on the device (loadCam)")
     s.add_argument("--pcd-densify", action="store_true",
                    help="when the config sets pcd_densify, write save_model/pcd_densify.ply after the run (slam.py:146-150)")
+    s.add_argument("--rgbd-refine", action="store_true",
+                   help="refine every ICP pose with the joint photometric + geometric RGB-D alignment (rtg_slam_amd.rgbd_align)")
+    s.add_argument("--rgbd-refine-photo-weight", type=float, default=None, metavar="L",
+                   help="metres per unit of intensity (default 0.25, derived from nominal noise levels, not measured)")
+    s.add_argument("--rgbd-refine-huber", type=float, default=None, metavar="D",
+                   help="Huber threshold of the intensity residual (default 0.05, a choice, not measured)")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)

@@ -199,6 +199,11 @@ _SIGNATURES = {
                                  C.c_int32, _P]),
     "rtgs_icp_fill_model_depth": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
     "rtgs_icp_scratch_bytes": (C.c_size_t, []),
+    # RGB-D refinement
+    "rtgs_rgbd_intensity_pyramid": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), _P]),
+    "rtgs_rgbd_align_accumulate": (C.c_int, [_P] * 6 + [C.c_int32, C.c_int32, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float,
+                                             _P, _P, _P]),
+    "rtgs_rgbd_align_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     # include/rtgs_slam.h
     "rtgs_tile_sum": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rtgs_transmission2tilemask": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),

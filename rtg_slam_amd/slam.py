@@ -26,6 +26,15 @@ class Tracker:
         self.pose_es, self.pose_gt = [], []
         self.initialized = False
         self.curr_frame = None
+        # extension (off by default): the RGB-D refinement of rtg_slam_amd.rgbd_align after every ICP track
+        self.rgbd_refiner = None
+        self.intensity_pyramid_t0 = None
+        self._intensity_t1 = None
+        self._K_host = None
+        self.rgbd_reports = []
+        if bool(getattr(args, "rgbd_refine", False)):
+            from .rgbd_align import RgbdRefiner
+            self.rgbd_refiner = RgbdRefiner(args)
 
     def map_preprocess(self, frame: Frame, depth: torch.Tensor, color: torch.Tensor, frame_id: int):
         """tracker.py:97-159: range mask, vertex / normal / confidence maps, confidence mask; the tracker's current status."""
@@ -51,8 +60,12 @@ class Tracker:
             pose = np.eye(4) if init_pose is None else np.asarray(init_pose, dtype=np.float64)
         else:
             rel, ok = self.icp_tracker.predict_pose(self.curr_frame)
+            if self.rgbd_refiner is not None:
+                rel = self._rgbd_refine(rel, frame_map)
             pose = self.pose_es[-1] @ rel.astype(np.float64)
         self.icp_tracker.move_last_status()
+        if self.rgbd_refiner is not None and not self.args.use_gt_pose:
+            self.intensity_pyramid_t0 = self._intensity_pyramid(frame_map)       # the next frame's target
         self.pose_es.append(pose)
         frame.updatePose(pose)
         c2w = frame.get_c2w                                                   # transform_map, SLAM/utils.py:56-63; tracker.py:283-288
@@ -61,6 +74,29 @@ class Tracker:
         frame_map["normal_map_w"] = self.so.transform_map(frame_map["normal_map_c"], rot)
         # transform_map moves the zero vertices of invalid pixels too; they are never sampled (depth 0 / zero normal masks)
         return ok
+
+    def _intensity_pyramid(self, frame_map):
+        """This frame's intensity pyramid, built once per frame (it is the source now and the target of the next frame)."""
+        if self._intensity_t1 is None or self._intensity_t1[0] is not frame_map:
+            from .rgbd_align import intensity_pyramid
+            self._intensity_t1 = (frame_map, intensity_pyramid(frame_map["color_chw"], len(self.icp_tracker.icp_downscales)))
+        return self._intensity_t1[1]
+
+    def _rgbd_refine(self, rel, frame_map):
+        """Between predict_pose and move_last_status, while the t0 pyramids still hold what ICP tracked against: source = this
+        frame, target = the t0 pyramids with the previous frame's intensity, start = ICP's pose.  tracking_success stays ICP's."""
+        if self.intensity_pyramid_t0 is None:
+            return rel
+        it = self.icp_tracker
+        if self._K_host is None:
+            self._K_host = self.curr_frame["K"].detach().cpu().numpy()        # one read per sequence: the tracker's K is fixed
+        t0 = time.perf_counter()
+        refined, rep = self.rgbd_refiner.refine(rel, it.vertex_pyramid_t1, it.normal_pyramid_t1, self._intensity_pyramid(frame_map),
+                                                it.vertex_pyramid_t0, it.normal_pyramid_t0, self.intensity_pyramid_t0,
+                                                self._K_host, it.icp_downscales)
+        rep["wall_s"] = time.perf_counter() - t0                  # the source pyramid, the launches, the host reads and solves
+        self.rgbd_reports.append(rep)
+        return refined
 
     def update_last_status(self, frame, render_depth, frame_depth, render_normal, frame_normal):
         self.icp_tracker.update_last_status(frame, render_depth, frame_depth, render_normal, frame_normal)
@@ -159,4 +195,14 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
     }
     if eval_every:
         report["eval"] = evals
+    if tracker.rgbd_refiner is not None:
+        reps = tracker.rgbd_reports
+        k = max(len(reps), 1)
+        report["rgbd_refine"] = {
+            "frames": len(reps), "iterations_mean": sum(sum(r["iterations"]) for r in reps) / k,
+            "host_reads_mean": sum(r["host_reads"] for r in reps) / k,
+            "photometric_inliers_mean": sum(r["inliers_photometric"][-1] for r in reps if r["inliers_photometric"]) / k,
+            "device_ms_mean": 1e3 * sum(r["device_s"] for r in reps) / k,
+            "ms_mean": 1e3 * sum(r["wall_s"] for r in reps) / k,
+            "photo_weight": tracker.rgbd_refiner.photo_weight, "huber": tracker.rgbd_refiner.huber}
     return mapper, tracker, report
