@@ -88,7 +88,8 @@ extern "C" int rtgs_slam_map_step_front(const rtgs_map_step_args* a, int64_t* nu
 // verified at the end - while the GPU is still busy with the backward.
 static int map_step_once(rtgs_ctx* ctx, const rtgs_map_step_args* a, int64_t* num_rendered_host, bool speculate, void* stream) {
   // one fused kernel for everything per-Gaussian behind the tile walk, unless the caller asks for the three-kernel form or
-  // the normal term (which adds to the arena's d_normal rows) is on
+  // the normal term (which adds to the arena's d_normal rows) is on.  ShardedMapOptimizer._fused_tail (map_optim.py) restates
+  // this predicate to know whether a step left gradient rows in the arena (RowGradArena.written): change the two together
   const bool fused = a->tail_mode == 0 && !(a->normal_weight > 0.f && a->gt_normal);
   // the caller's promise for the cull cache (rtgs_map_step_args.map_epoch): only a speculative forward may use it, and both
   // tails below leave a mark for every row they step while the cache is armed

@@ -686,6 +686,10 @@ class ShardedMapOptimizer:
 
     def _begin(self, confidence):
         self.flush()
+        if self.grad_rows is not None and self.grad_rows.written:
+            # gradient rows of the optimisation before: a new one starts from a zero arena (the fused tail never writes it;
+            # the three-kernel tail's attach term and the autograd step leave rows that no row state accounts for)
+            self._stale = True
         self._clean()
         st = self.state
         N, nf = self._active()
@@ -838,6 +842,8 @@ class ShardedMapOptimizer:
             ai = self.attach_init
             attach = _lib.AttachC(ai["xyz"].data_ptr(), ai["raw8"].data_ptr(), ai["info"].data_ptr())
         keep = _Keep(rs, dev)
+        if not self._fused_tail(gt_normal is not None):
+            a.written = True                # every form but the fused tail leaves this step's gradient rows in the arena
         self.step_count += 1
         self.total_steps = getattr(self, "total_steps", 0) + 1
         P = lambda t: t.data_ptr()
@@ -886,6 +892,12 @@ class ShardedMapOptimizer:
         self.last_num_rendered = int(R.value)
         self.last_losses = ws["loss"]               # device float[4]: total, colour, depth, ssim (mapper.py:458-466)
         return ws["loss"][0]
+
+    def _fused_tail(self, normal_term: bool) -> bool:
+        """Whether the one-call step of these arguments runs the fused per-Gaussian tail, which keeps the gradients in
+        registers and leaves the arena zero - THE SAME predicate as `fused` in map_step_once (csrc/map_step.hip): one rank
+        (the other fronts run rtgs_map_tail_rows), tail_mode 0, no normal term.  Change the two together."""
+        return self.world == 1 and self.tail_mode == 0 and not normal_term
 
     def _next_map_epoch(self) -> int:
         """The map epoch the next `step_slam` passes (called by it before its own version bump; pure bookkeeping).  The
@@ -1108,6 +1120,7 @@ class ShardedMapOptimizer:
         arena = self.grad_rows
         if arena is not None:
             arena.begin_step()
+            arena.written = True
             gd = activate8_hip(leaves["raw8"], arena)
             gd["grad_rows"] = arena
         else:

@@ -36,6 +36,7 @@ from __future__ import annotations
 
 import math
 import random
+import warnings
 from collections import deque
 from types import SimpleNamespace
 from typing import Dict, Optional
@@ -754,24 +755,26 @@ class Mapping:
             return
         scale = mo.global_lr_scale(final, a.feature_lr_coef, a.scaling_lr_coef, a.rotation_lr_coef)
         o.begin_global_optimization(scale)
-        total_iter = int(a.gaussian_update_iter)
-        sample_ratio = 0.4
-        w = SimpleNamespace(**vars(self.weights))
-        if final:
-            total_iter = self.get_keyframe_num * a.final_global_iter
-            select_keyframe_num = self.get_keyframe_num
-            w.depth_weight = 0.0
-            self.weights.depth_weight = 0.0                              # the reference overwrites update_args (:633)
-            sample_ratio = -1
-        select_keyframe_num = min(select_keyframe_num, self.get_keyframe_num)
-        sel = [-i - 1 for i in range(select_keyframe_num)]
-        frames = [self.keyframe_list[i] for i in sel]
-        maps = [self.keymap_list[i] for i in sel]
-        masks = [self.evaluate_render_range(f, global_opt=True, unstable=False, sample_ratio=sample_ratio,
-                                            gt_color=m["color_map"]) for f, m in zip(frames, maps)]
-        masks = [(m[0].to(torch.uint8), m[1], m[2]) for m in masks]
-        conf = self.aux("confidence", "stable").reshape(-1)
         try:
+            # everything between the begin and the end sits inside the try: an exception in the mask renders or in a step must
+            # not leave the map object in the global scope (every later append / permute would refuse: ADVICE r5)
+            total_iter = int(a.gaussian_update_iter)
+            sample_ratio = 0.4
+            w = SimpleNamespace(**vars(self.weights))
+            if final:
+                total_iter = self.get_keyframe_num * a.final_global_iter
+                select_keyframe_num = self.get_keyframe_num
+                w.depth_weight = 0.0
+                self.weights.depth_weight = 0.0                          # the reference overwrites update_args (:633)
+                sample_ratio = -1
+            select_keyframe_num = min(select_keyframe_num, self.get_keyframe_num)
+            sel = [-i - 1 for i in range(select_keyframe_num)]
+            frames = [self.keyframe_list[i] for i in sel]
+            maps = [self.keymap_list[i] for i in sel]
+            masks = [self.evaluate_render_range(f, global_opt=True, unstable=False, sample_ratio=sample_ratio,
+                                                gt_color=m["color_map"]) for f, m in zip(frames, maps)]
+            masks = [(m[0].to(torch.uint8), m[1], m[2]) for m in masks]
+            conf = self.aux("confidence", "stable").reshape(-1)
             for it in range(total_iter):
                 self.iter = it
                 j = self.rng.randint(0, select_keyframe_num - 1)
@@ -782,11 +785,20 @@ class Mapping:
                               gt_normal=im.get("normal_map_w"))
             self.stats["iterations"] += total_iter
             self.stats["global_opts"] += 1
-        finally:
-            # an exception inside a step must not leave the map object in the global scope (every later append / permute would
-            # refuse: ADVICE r5)
+        except BaseException as err:
+            # leave the scope, but let the ORIGINAL exception travel: a failure of the end itself (the device may be the
+            # reason for both) must not replace it - it is warned about and noted on the original
             self.iter = 0
-            o.end_global_optimization()
+            try:
+                o.end_global_optimization()
+            except Exception as end_err:
+                msg = f"end_global_optimization() failed too while leaving a failed global optimisation: {end_err!r}"
+                if hasattr(err, "add_note"):
+                    err.add_note(msg)
+                warnings.warn(msg, RuntimeWarning)
+            raise
+        self.iter = 0
+        o.end_global_optimization()
 
     # ------------------------------------------------------------------ state management
     def gaussians_fix(self, mask=None):

@@ -252,6 +252,7 @@ class RowGradArena:
         self._train = None
         self._dirty = "all"      # rows of the seven gradient arrays a backward may have written since the last clear(): "all" or (lo, hi)
         self.calls = 0           # rasterizer backward passes since begin_step(); the row states describe exactly one
+        self.written = False     # rows or states may be non-zero: set by whoever hands the arena to a backward that writes them
         self._views()
 
     @property
@@ -296,6 +297,7 @@ class RowGradArena:
         self.scratch.zero_()
         self._state_full.zero_()
         self.calls = 0
+        self.written = False
         self._dirty = None
         self.train = self._train          # the range in force stays in force: it is what the next backward writes
 
