@@ -81,6 +81,21 @@ void rtgs_raster_set_onepass_ctx(rtgs_ctx* ctx, int on);
  * bitonic, fused radix, separate launch, left to pass 2.  Waits for the device. */
 void rtgs_raster_set_fused_sort_ctx(rtgs_ctx* ctx, int on);
 int rtgs_raster_fused_sort_stats_ctx(rtgs_ctx* ctx, int64_t* out18);
+/* Near-slice forward of the speculative map step (kind 1: the slice finished every tile last time): the blend's workgroups
+ * gather their own lists.  The list-form shade appends one 4-byte word per tile ROW of a live Gaussian's rect to that row's
+ * band (x0 | x1 << 8 | list position << 16, in the bucket nobody else uses on this path); the tile's workgroup scans its row's
+ * band, keeps the entries whose column range holds it, runs bin_place's own test on them, and sorts what is left - bin_place
+ * and the sort launch in front of the blend are not launched.  Same lists, same counts, same outputs.
+ * mode 0 = off, 1 = automatic (default): taken when the structure allows it (per-tile segments, fused sort, at most 255 tile
+ * columns and 256 tile rows, the bands fit the bucket), the last verified work list is within the slice's Gaussian budget and the
+ * decayed longest slice list is at most 7/8 of the 1 024 entries the blend sorts; 2 = forced (tests): whatever those two are.
+ * A tile that finds more than 1 024 hits leaves itself to pass 2, the guess "every tile finished" fails, and the step is redone
+ * classically; that call reports the list, and in both modes the path then stays off while the reported (decaying) maximum is
+ * above 1 024.  RTGS_TILE_GATHER at load time; the setter forgets the speculative plan.
+ * rtgs_raster_tile_gather_stats_ctx: out6 = forwards that gathered | speculative kind-1 forwards on segments with the fused sort
+ * that did not: work list too long | longest list too long | layout; band entries scanned per round | candidates a round keeps. */
+void rtgs_raster_set_tile_gather_ctx(rtgs_ctx* ctx, int mode);
+int rtgs_raster_tile_gather_stats_ctx(rtgs_ctx* ctx, int64_t* out6);
 /* Timing decompositions of the entry-per-lane backward walk (tools only): bits 0..2 switch parts of the kernel OFF (1 walk,
  * 2 depth partials, 4 stores) - results are then wrong by construction, so the bits are never read from the environment and a
  * tool that sets them clears them again.  PROCESS-WIDE. */

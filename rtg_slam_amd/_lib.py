@@ -170,6 +170,8 @@ _SIGNATURES = {
     "rtgs_raster_set_onepass_ctx": (None, [_P, C.c_int]),
     "rtgs_raster_set_fused_sort_ctx": (None, [_P, C.c_int]),
     "rtgs_raster_fused_sort_stats_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "rtgs_raster_set_tile_gather_ctx": (None, [_P, C.c_int]),
+    "rtgs_raster_tile_gather_stats_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "rtgs_raster_set_loss_signs_ctx": (None, [_P, C.c_int]),
     "rtgs_raster_loss_signs_stats_ctx": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "rtgs_raster_signs_ok_ctx": (C.c_int, [_P, _P]),

@@ -25,8 +25,10 @@ void set_bwd_debug(int bits);
 void set_bwd_stamps(void* dev);
 void launch_blend_fwd(const RasterParams&, const uint2*, const uint32_t*, const Splat*, float*, float*, int32_t*,
                       int32_t*, float*, float*, float*, uint32_t*, unsigned long long*, SlicePass, uint32_t*, uint32_t*, uint32_t*, int, uint32_t*,
-                      TileCache, uint32_t, hipStream_t, FusedSort fs = FusedSort{nullptr, nullptr, nullptr, nullptr, nullptr});
+                      TileCache, uint32_t, hipStream_t, FusedSort fs = FusedSort{nullptr, nullptr, nullptr, nullptr, nullptr},
+                      TileGather tg = TileGather{nullptr, nullptr, 0u, nullptr, nullptr, nullptr});
 bool blend_fwd_fuses_sort();
+bool blend_fwd_gathers();
 void launch_blend_bwd(const RasterParams&, const uint2*, const uint32_t*, const Splat*, const float*, const float*,
                       const uint32_t*, const int32_t*, const float*, const float*, const uint32_t*, uint32_t*,
                       const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, int, uint32_t, uint32_t, hipStream_t);
@@ -60,7 +62,8 @@ void launch_cull_check(int, const uint32_t*, const uint32_t*, const int32_t*, co
                        const uint8_t*, const uint8_t*, const float2*, const float2*, const uint32_t*, const uint32_t*,
                        const uint32_t*, unsigned long long*, hipStream_t);
 void launch_preprocess_shade(const RasterParams&, const float*, const float*, const float*, const float*, const float*,
-                             const float*, Splat*, int32_t*, uint8_t*, float2*, SliceList, SliceSel, size_t, hipStream_t);
+                             const float*, Splat*, int32_t*, uint8_t*, float2*, SliceList, SliceSel, size_t, hipStream_t,
+                             RowBands rb = RowBands{nullptr, nullptr, 0u});
 void launch_bin_tilescan(int, const uint32_t*, uint2*, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*,
                          const uint32_t*, const uint32_t*, uint32_t, SpecCaps, hipStream_t);
 void launch_bin_scatter(const RasterParams&, const Splat*, const int32_t*, const int32_t*, const uint16_t*, uint32_t*,
@@ -103,7 +106,14 @@ struct rtgs_ctx {
     // Map step: the loss leaves one sign byte per pixel and the entry walk rebuilds the image gradients from it, where that
     // is possible (rtgs_raster_signs_ok_ctx); RTGS_LOSS_SIGNS=0: the float planes and slam_loss_grads' launch, as before.
     bool loss_signs = true;
+    // Near slice of a speculative kind-1 forward: the blend's workgroups gather their own lists from row bands the shade
+    // wrote, no bin_place (rtgs_debug.h: rtgs_raster_set_tile_gather_ctx).  0 off, 1 automatic, 2 forced (tests).
+    int tile_gather = 1;
   } sw;
+  int64_t gather_stats[4] = {0, 0, 0, 0};   // forwards that gathered; eligible ones that did not: listed / longest / layout
+  // a gathered forward failed its guess over a list the blend's arena cannot sort: not again - forced mode included - until a
+  // verified forward reports the longest slice list back inside the arena
+  bool gather_blocked = false;
   int64_t loss_path_stats[2] = {0, 0};   // map steps whose backward read signs, map steps that took the float planes
   int64_t slice_stats[4] = {0};     // used, near-slice instances, tiles finished, tiles left to pass 2
   unsigned long long* counters = nullptr;
@@ -140,6 +150,10 @@ struct rtgs_ctx {
     // an optimisation that alternates between the views of a window (mapper.py:176-183 picks a random frame per
     // iteration) does not fail its guess every time it returns to the larger view
     uint32_t R_hi = 0, longest_hi = 0, slots_hi = 0;
+    // ... and of the longest NEAR-SLICE tile list (slice_publish's payload word 1; per-tile segments only): what the tile
+    // gather's eligibility looks at
+    uint32_t slice_longest_hi = 0;
+    void note_slice(uint32_t l) { slice_longest_hi = l > slice_longest_hi - slice_longest_hi / 16 ? l : slice_longest_hi - slice_longest_hi / 16; }
     void note(uint32_t r, uint32_t l, uint32_t s) {
       R = r; longest = l; slots = s;
       R_hi = r > R_hi - R_hi / 16 ? r : R_hi - R_hi / 16;
@@ -150,6 +164,7 @@ struct rtgs_ctx {
   struct Spec {
     bool pending = false;           // a speculative forward awaits rtgs_raster_forward_verify
     int kind = -1;
+    bool gathered = false;          // kind 1: the blend gathered its lists (tile_gather_chosen)
     uint32_t seq = 0, capR = 0, capL = 0, capS = 0;
     const void* geom = nullptr;     // geometry buffer of that forward (the backward guards itself only for this one)
     const uint32_t* fail_dev = nullptr;
@@ -202,6 +217,7 @@ static rtgs_ctx* default_ctx() {
     if (const char* e = getenv("RTGS_CULL_CACHE")) n->sw.cull_cache = atoi(e) != 0;
     if (const char* e = getenv("RTGS_CULL_CACHE_CHECK")) n->sw.cull_check = atoi(e) != 0;
     if (const char* e = getenv("RTGS_LOSS_SIGNS")) n->sw.loss_signs = atoi(e) != 0;
+    if (const char* e = getenv("RTGS_TILE_GATHER")) { const int m = atoi(e); n->sw.tile_gather = (m >= 0 && m <= 2) ? m : 1; }
     return n;
   }();
   return c;
@@ -462,7 +478,7 @@ static void note_plan(rtgs_ctx::Plan& pl, const FwdCall& f, bool same, int kind,
   pl.kind = kind;
   pl.valid = kind >= 0 && usable && R <= 0xffffffffll;
   pl.P = f.p.P; pl.H = f.p.H; pl.W = f.p.W; pl.slice_mode = f.c->sw.slice_mode; pl.slice_budget = f.c->sw.slice_budget;
-  if (!same || !pl.valid) { pl.R_hi = pl.longest_hi = pl.slots_hi = 0; }
+  if (!same || !pl.valid) { pl.R_hi = pl.longest_hi = pl.slots_hi = 0; pl.slice_longest_hi = 0; }
   pl.note((uint32_t)R, longest, slots);
 }
 
@@ -477,15 +493,40 @@ static void preprocess_all(const FwdCall& f, const int32_t* sat, bool clear) {
   launch_preprocess_fwd(f.p, f.means3D, f.opacities, f.shs, f.scales, f.rotations, f.normal_w, sat, f.splats, f.tiles_touched,
                         f.radii, f.clamped, f.out_radii, clear ? f.zero_words : nullptr, clear ? f.zero_n : 0, nullptr, f.st);
 }
-static void shade(const FwdCall& f, const RasterParams& p, SliceList work, const SliceSel& sel, size_t max_list) {
+static void shade(const FwdCall& f, const RasterParams& p, SliceList work, const SliceSel& sel, size_t max_list,
+                  RowBands rb = RowBands{nullptr, nullptr, 0u}) {
   launch_preprocess_shade(p, f.means3D, f.opacities, f.shs, f.scales, f.rotations, f.normal_w, f.splats, f.radii, f.clamped,
-                          f.uv, work, sel, max_list, f.st);
+                          f.uv, work, sel, max_list, f.st, rb);
 }
 static void blend(const FwdCall& f, const RasterParams& p, const uint2* ranges, const uint32_t* list, SlicePass pass,
-                  uint32_t seg, FusedSort fs = FusedSort{nullptr, nullptr, nullptr, nullptr, nullptr}) {
+                  uint32_t seg, FusedSort fs = FusedSort{nullptr, nullptr, nullptr, nullptr, nullptr},
+                  TileGather tg = TileGather{nullptr, nullptr, 0u, nullptr, nullptr, nullptr}) {
   launch_blend_fwd(p, ranges, list, f.splats, f.out_color, f.out_depth, f.out_cidx, f.out_didx, f.out_cw, f.out_dw, f.out_T,
                    f.n_contrib, f.c->counters, pass, f.tile_mode, f.depth_pos, f.tile_last, f.fwd_walk, f.aux_zero, f.tcache,
-                   seg, f.st, fs);
+                   seg, f.st, fs, tg);
+}
+
+// The tile gather (Switches::tile_gather): may this speculative kind-1 forward leave bin_place and the long-list sort launch
+// out?  The structure must be the one the gather stands on - per-tile segments, the fused sort - and the layout must hold
+// the bands: entries are x0 | x1 << 8 | list position << 16, the shade counts rows in LDS, and gy bands of max_list words
+// must fit the bucket nobody else uses on this path.  Then, from the last verified forwards and without a host wait: the
+// work list within max_list, and the decayed longest slice list at most 7/8 of what the blend's arena sorts.  Forced mode
+// looks at neither.  In both modes a gathered forward that failed over a list above the arena blocks the path
+// (rtgs_raster_forward_verify_ctx); the classic call that redoes the step reports that list (forward_classic: note_slice),
+// and the path stays off for as long as the reported maximum stays above the arena: no alternation between gather and redo.
+static bool tile_gather_chosen(FwdCall& f, const rtgs_ctx::Plan& pl) {
+  rtgs_ctx* const c = f.c; const GeomLayout& G = f.G;
+  if (c->sw.tile_gather == 0 || !f.seg1 || !(c->sw.fused_sort && blend_fwd_fuses_sort() && blend_fwd_gathers())) return false;
+  const size_t cap1 = (size_t)f.ntiles * G.slice_seg > G.slice_cap ? (size_t)f.ntiles * G.slice_seg : G.slice_cap;
+  if (f.p.gx > 255 || f.p.gy > GATHER_ROWS_MAX || G.slice_max_list > 65536 ||
+      (size_t)f.p.gy * G.slice_max_list * sizeof(uint32_t) > cap1 * sizeof(uint64_t)) { ++c->gather_stats[3]; return false; }
+  const bool forced = c->sw.tile_gather == 2;
+  if (c->gather_blocked && pl.slice_longest_hi <= (uint32_t)FSORT_CAP) c->gather_blocked = false;
+  if (c->gather_blocked) { ++c->gather_stats[2]; return false; }
+  if (!forced && c->last_listed > (uint32_t)G.slice_max_list) { ++c->gather_stats[1]; return false; }
+  if (!forced && pl.slice_longest_hi > (uint32_t)(FSORT_CAP - FSORT_CAP / 8)) { ++c->gather_stats[2]; return false; }
+  ++c->gather_stats[0];
+  return true;
 }
 
 // gradient slots of the backward (BwdInfo): gbase = exclusive scan of the rect areas, into `offsets`
@@ -499,17 +540,10 @@ static int scan_slots(const FwdCall& f) {
 // The near slice's tile lists, after their placement into bucket1: sorted by the sort launches into list1, or - fused -
 // by the blend's own workgroups (fs1 tells it where the keys are); then only the size class that does not fit the
 // blend's LDS keeps its launch.  (That launch is unconditional: a slice whose longest list fits the blend still pays it.)
-static int sort_slice_lists(FwdCall& f, FusedSort& fs1) {
+// (with work counters set: the per-tile class words of the fused blend, cleared; nullptr otherwise)
+static int fsort_class_words(FwdCall& f, uint32_t*& cls) {
   rtgs_ctx* const c = f.c;
-  const unsigned long long* bucket1 = (const unsigned long long*)(f.geom + f.G.bucket1);
-  const uint32_t* cnt = f.seg1 ? f.tile_count1 : nullptr;
-  if (!(c->sw.fused_sort && blend_fwd_fuses_sort())) {
-    launch_bin_tilesort(f.ntiles, (uint32_t)SLICE_MAX_LIST, f.ranges1, bucket1, f.list1, nullptr, f.st, cnt, f.seg1,
-                        f.seg1 ? f.ranges1 : nullptr);
-    return RTGS_OK;
-  }
-  launch_bin_tilesort_long(f.ntiles, f.ranges1, bucket1, f.list1, nullptr, f.st, cnt, f.seg1);
-  uint32_t* cls = nullptr;
+  cls = nullptr;
   if (c->counters) {
     if (c->fsort_cap < f.ntiles) {
       if (c->fsort_cls) (void)hipFree(c->fsort_cls);
@@ -521,6 +555,21 @@ static int sort_slice_lists(FwdCall& f, FusedSort& fs1) {
     c->fsort_tiles = f.ntiles;
     cls = c->fsort_cls;
   }
+  return RTGS_OK;
+}
+static int sort_slice_lists(FwdCall& f, FusedSort& fs1) {
+  rtgs_ctx* const c = f.c;
+  const unsigned long long* bucket1 = (const unsigned long long*)(f.geom + f.G.bucket1);
+  const uint32_t* cnt = f.seg1 ? f.tile_count1 : nullptr;
+  if (!(c->sw.fused_sort && blend_fwd_fuses_sort())) {
+    launch_bin_tilesort(f.ntiles, (uint32_t)SLICE_MAX_LIST, f.ranges1, bucket1, f.list1, nullptr, f.st, cnt, f.seg1,
+                        f.seg1 ? f.ranges1 : nullptr);
+    return RTGS_OK;
+  }
+  launch_bin_tilesort_long(f.ntiles, f.ranges1, bucket1, f.list1, nullptr, f.st, cnt, f.seg1);
+  uint32_t* cls = nullptr;
+  const int rc = fsort_class_words(f, cls);
+  if (rc != RTGS_OK) return rc;
   fs1 = FusedSort{bucket1, cnt, f.seg1 ? f.ranges1 : nullptr, f.list1, cls};
   return RTGS_OK;
 }
@@ -528,11 +577,30 @@ static int sort_slice_lists(FwdCall& f, FusedSort& fs1) {
 // Pass 1 over the slice's work list (slice_compact laid it out): shade, bin, sort and blend only the nearest Gaussians, then
 // publish how many tiles are left.  No host sync: the arrays are sized by the budget, the sort classes are launched blind.
 // The caller has advanced c->seq; `guard` is the speculation word slice_publish raises (nullptr: nothing is guessed).
-static int slice_pass1(FwdCall& f, uint32_t* guard) {
+static int slice_pass1(FwdCall& f, uint32_t* guard, bool gather = false) {
   const RasterParams& p = f.p; const GeomLayout& G = f.G;
   const SliceSel sel1 = slice_sel(f);
   const SliceList work{(const uint32_t*)(f.geom + G.slice_ids), f.slice_ctr + 2};
   unsigned long long* const bucket1 = (unsigned long long*)(f.geom + G.bucket1);
+  if (gather) {
+    // The tile gather: the shade leaves row bands in the bucket (their counters: the main pass' tile counters, which the cull
+    // stage cleared and a kind-1 forward never uses), the blend's workgroups build, sort and count their own lists.  No
+    // bin_place, no sort launch; the blend writes tile_count1 and ranges1 as they did.
+    const RowBands rb{f.tile_count, (uint32_t*)bucket1, (uint32_t)G.slice_max_list};
+    shade(f, p, work, sel1, G.slice_max_list, rb);
+    uint32_t* cls = nullptr;
+    const int rcc = fsort_class_words(f, cls);
+    if (rcc != RTGS_OK) return rcc;
+    DBG(f.s, f.st);
+    prof_mark(f.c, EV_SL_BIN, f.st);
+    blend(f, p, f.ranges1, f.list1, SlicePass{1, f.tile_mask, f.mask2, f.ranges1_bwd, f.ranges}, f.seg1,
+          FusedSort{bucket1, f.tile_count1, f.ranges1, f.list1, cls},
+          TileGather{rb.count, rb.entries, rb.stride, work.ids, f.radii, f.tile_count1});
+    prof_mark(f.c, EV_SL_BLEND, f.st);
+    launch_slice_publish(f.ntiles, f.tile_mask, f.mask2, f.info + 2, f.slice_ctr, f.info_host, f.c->seq, guard, f.st, f.tile_count1);
+    DBG(f.s, f.st);
+    return RTGS_OK;
+  }
   shade(f, p, work, sel1, G.slice_max_list);
   if (f.seg1) {       // one pass: no count, no scan (tile_count1 was cleared by the cull pass; the sort writes ranges1)
     launch_bin_place(p, f.splats, f.radii, f.tile_mask, f.tile_count1, bucket1, f.seg1, nullptr, sel1, work, G.slice_max_list, f.st);
@@ -726,7 +794,8 @@ static int forward_speculative(FwdCall& f, bool sort_path, bool sliced, SpecOutc
     prof_mark(c, EV_PRE, st);
     launch_slice_compact(P, slice_sel(f), (uint32_t*)(f.geom + G.slice_ids), f.slice_ctr + 2, f.tiles_touched, f.offsets,
                          f.slice_ctr + 4, nullptr, 0u, nullptr, st);
-    if ((rc = slice_pass1(f, fail)) != RTGS_OK) return rc;
+    c->spec.gathered = tile_gather_chosen(f, pl);
+    if ((rc = slice_pass1(f, fail, c->spec.gathered)) != RTGS_OK) return rc;
     prof_mark(c, EV_BLEND0, st); prof_mark(c, EV_BLEND, st);
     c->hint_slice_lists = true; c->hint_main_lists = false;
     c->slice_stats[0] = 1; c->slice_stats[1] = pl.R1; c->slice_stats[2] = pl.n_fin; c->slice_stats[3] = 0;
@@ -826,7 +895,7 @@ static int forward_classic(FwdCall& f, bool sort_path, bool sliced) {
   int rc;
   const bool sliced0 = sliced;                 // what this call started as (the variable follows the passes below)
   int64_t R = 0, R1 = 0;
-  uint32_t longest = 0, slots = 0, n_left = 0, n_fin = 0;
+  uint32_t longest = 0, slots = 0, n_left = 0, n_fin = 0, slice_longest = 0;
   SlicePass pass{0, nullptr, nullptr, nullptr, nullptr};
   bool declined = false, considered = false;
   SliceList vis{nullptr, nullptr};             // every visible Gaussian, when the declined single pass built the list
@@ -877,6 +946,7 @@ static int forward_classic(FwdCall& f, bool sort_path, bool sliced) {
       if ((rc = wait_published(f)) != RTGS_OK) return rc;
       n_left = f.pub[2]; n_fin = f.pub[3];
       R1 = (int64_t)f.pub[4];          // total of the slice lists, finished or not (accounting only)
+      slice_longest = f.pub[1];        // (per-tile segments; 0 otherwise)
       if (n_left > 0) {
         mask_main = f.mask2;
         pass = SlicePass{2, nullptr, f.mask2, nullptr, nullptr};
@@ -990,6 +1060,7 @@ static int forward_classic(FwdCall& f, bool sort_path, bool sliced) {
   note_plan(c->plan, f, c->plan.P == P, sort_path ? -1 : ((sliced && n_left == 0) ? 1 : (considered ? 2 : (!sliced && P > 0 ? 0 : -1))),
             want_bwd, R, longest, slots);
   c->plan.R1 = (uint32_t)R1; c->plan.n_fin = n_fin;
+  c->plan.note_slice(slice_longest);      // (after a failed tile gather: the list that outgrew the blend's arena)
   // ... and what the next forward WITHOUT a backward on this image may assume (any Gaussian count)
   if (!want_bwd)
     note_plan(sliced0 ? c->plan_plain : c->plan_plain0, f, true, sort_path ? -1 : (sliced0 ? (considered ? 2 : -1) : (P > 0 ? 0 : -1)),
@@ -1286,6 +1357,8 @@ int rtgs_raster_forward_verify_ctx(rtgs_ctx* ctx, int64_t* num_rendered_host) {
     ok = n_left == 0u && pub[5] == 0u;           // ... and recull_rows did not see the view move under the cached cull
     if (pub[5] != 0u) ++c->cull.stats[3];
     pl.R1 = pub[4]; pl.n_fin = pub[3]; pl.R = 0; pl.longest = 0;
+    pl.note_slice(pub[1]);
+    if (c->spec.gathered && pub[1] > (uint32_t)FSORT_CAP) c->gather_blocked = true;
     c->last_listed = pub[0];
     c->slice_stats[1] = pub[4]; c->slice_stats[2] = pub[3]; c->slice_stats[3] = n_left;
   } else {
@@ -1369,6 +1442,15 @@ int rtgs_raster_fused_sort_stats_ctx(rtgs_ctx* ctx, int64_t* out18) {
     o[2] = len > o[2] ? len : o[2];
     ++o[0];
   }
+  return RTGS_OK;
+}
+void rtgs_raster_set_tile_gather_ctx(rtgs_ctx* c, int mode) {
+  use(c)->sw.tile_gather = (mode >= 0 && mode <= 2) ? mode : 1; use(c)->plan.valid = false; use(c)->gather_blocked = false;
+}
+int rtgs_raster_tile_gather_stats_ctx(rtgs_ctx* ctx, int64_t* out6) {
+  if (!out6) return RTGS_E_INVALID;
+  memcpy(out6, use(ctx)->gather_stats, sizeof(use(ctx)->gather_stats));
+  out6[4] = GATHER_CHUNK; out6[5] = GATHER_CAND;
   return RTGS_OK;
 }
 void rtgs_raster_set_bwd_walk_ctx(rtgs_ctx* c, int mode) { use(c)->sw.bwd_walk = (mode >= 1 && mode <= 4) ? mode : 0; }

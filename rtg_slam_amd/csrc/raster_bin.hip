@@ -51,13 +51,7 @@ constexpr int GPB = 1024;       // Gaussians per workgroup in bin_count / bin_sc
 constexpr int SLICE_GPB = RTGS_SLICE_GPB;   // ... when they walk the near slice's short work list: 8 Gaussians per wave (each covers
                                 // tens of tiles, the candidates are spread over all 64 lanes), many workgroups
 
-struct BinG {
-  float u, v, ca, cb, cc, thr;  // thr = 2 ln(255 o) with margin; < 0 -> never visible
-  float ica, icc;               // 1/ca, 1/cc
-  int x0, y0, x1, y1;
-  uint32_t zbits;
-};
-
+// (BinG, bing_of_splat and tile_visible: raster_common.h - the near-slice blend that gathers its own list runs the same test)
 __device__ __forceinline__ bool load_bing(const RasterParams& p, const Splat* __restrict__ splats,
                                           const int32_t* __restrict__ radii, const uint8_t* __restrict__ zbin, int cut,
                                           const int32_t* __restrict__ sat, const float2* __restrict__ uv, int i, BinG& g) {
@@ -73,41 +67,7 @@ __device__ __forceinline__ bool load_bing(const RasterParams& p, const Splat* __
     tile_rect_of(c.x, c.y, radius, p.gx, p.gy, x0, y0, x1, y1);
     if ((x1 - x0) * (y1 - y0) <= 0 || sat_count(sat, p.gx, x0, y0, x1, y1) == 0) return false;
   }
-  const float4 r0 = reinterpret_cast<const float4*>(splats + i)[0];
-  const float4 r1 = reinterpret_cast<const float4*>(splats + i)[1];
-  g.u = r0.x; g.v = r0.y; g.ca = r0.z; g.cb = r0.w; g.cc = r1.x;
-  const float o = r1.y;
-  if (!(o >= 1.f / 255.f)) return false;            // alpha = min(.99, o G) <= o < 1/255 everywhere
-  g.zbits = __float_as_uint(reinterpret_cast<const float*>(splats + i)[13]);
-  const bool pd = (g.ca > 0.f) && (g.cc > 0.f) && (g.ca * g.cc - g.cb * g.cb > 0.f);
-  // q <= 2 ln(255 o) <=> alpha >= 1/255; margin: 1e-3 relative + 1e-2 absolute on q (float rounding
-  // of power in blend is ~1e-6 relative).  Non-PD conics (never seen; det guard) keep every tile.
-  g.thr = pd ? (2.f * __logf(255.f * o)) * 1.001f + 1e-2f : 3.0e38f;
-  g.ica = __builtin_amdgcn_rcpf(g.ca); g.icc = __builtin_amdgcn_rcpf(g.cc);   // only place the clamp points
-  tile_rect_of(g.u, g.v, radius, p.gx, p.gy, g.x0, g.y0, g.x1, g.y1);
-  return (g.x1 - g.x0) * (g.y1 - g.y0) > 0;
-}
-
-// min over the tile's pixel-centre box of q(d) = ca dx^2 + 2 cb dx dy + cc dy^2, d = centre - pixel
-__device__ __forceinline__ bool tile_visible(const BinG& g, int tx, int ty) {
-  const float dx0 = g.u - (float)(tx * TILE + TILE - 1), dx1 = g.u - (float)(tx * TILE);
-  const float dy0 = g.v - (float)(ty * TILE + TILE - 1), dy1 = g.v - (float)(ty * TILE);
-  if (dx0 <= 0.f && dx1 >= 0.f && dy0 <= 0.f && dy1 >= 0.f) return true;
-  float qmin = 3.4e38f;
-  const float ica = g.ica, icc = g.icc;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {                      // edges dx = const
-    const float dx = e ? dx1 : dx0;
-    const float dy = fminf(dy1, fmaxf(dy0, -g.cb * dx * icc));
-    qmin = fminf(qmin, g.ca * dx * dx + 2.f * g.cb * dx * dy + g.cc * dy * dy);
-  }
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {                      // edges dy = const
-    const float dy = e ? dy1 : dy0;
-    const float dx = fminf(dx1, fmaxf(dx0, -g.cb * dy * ica));
-    qmin = fminf(qmin, g.ca * dx * dx + 2.f * g.cb * dx * dy + g.cc * dy * dy);
-  }
-  return qmin <= g.thr;
+  return bing_of_splat(p, splats, radius, i, g);
 }
 
 // ---------------------------------------------------------------------------------------------

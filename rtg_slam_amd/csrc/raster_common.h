@@ -291,6 +291,80 @@ __device__ __forceinline__ uint32_t quads_reached(float u, float v, float hx, fl
   return m;
 }
 
+// The tile-level hit test of the binning (raster_bin.hip) - and of the near-slice blend that gathers its own list
+// (blend_fwd_kernel<.., GATHER>): ONE definition, so that both decide every (Gaussian, tile) pair alike, down to the
+// instance count.  BinG is what the test needs of a Gaussian; bing_of_splat fills it from the Splat record.
+struct BinG {
+  float u, v, ca, cb, cc, thr;  // thr = 2 ln(255 o) with margin; < 0 -> never visible
+  float ica, icc;               // 1/ca, 1/cc
+  int x0, y0, x1, y1;
+  uint32_t zbits;
+};
+// false: not visible anywhere (opacity below 1/255, empty rect).  r0, r1 = the first two float4 of the Splat record, zbits
+// its depth; radius > 0.  (A caller that reads g after `false` has cleared it first.)
+__device__ __forceinline__ bool bing_of_record(const RasterParams& p, const float4 r0, const float4 r1, uint32_t zbits, int radius, BinG& g) {
+  g.u = r0.x; g.v = r0.y; g.ca = r0.z; g.cb = r0.w; g.cc = r1.x;
+  const float o = r1.y;
+  if (!(o >= 1.f / 255.f)) return false;            // alpha = min(.99, o G) <= o < 1/255 everywhere
+  g.zbits = zbits;
+  const bool pd = (g.ca > 0.f) && (g.cc > 0.f) && (g.ca * g.cc - g.cb * g.cb > 0.f);
+  // q <= 2 ln(255 o) <=> alpha >= 1/255; margin: 1e-3 relative + 1e-2 absolute on q (float rounding
+  // of power in blend is ~1e-6 relative).  Non-PD conics (never seen; det guard) keep every tile.
+  g.thr = pd ? (2.f * __logf(255.f * o)) * 1.001f + 1e-2f : 3.0e38f;
+  g.ica = __builtin_amdgcn_rcpf(g.ca); g.icc = __builtin_amdgcn_rcpf(g.cc);   // only place the clamp points
+  tile_rect_of(g.u, g.v, radius, p.gx, p.gy, g.x0, g.y0, g.x1, g.y1);
+  return (g.x1 - g.x0) * (g.y1 - g.y0) > 0;
+}
+__device__ __forceinline__ bool bing_of_splat(const RasterParams& p, const Splat* __restrict__ splats, int radius, int i, BinG& g) {
+  const float4 r0 = reinterpret_cast<const float4*>(splats + i)[0];
+  const float4 r1 = reinterpret_cast<const float4*>(splats + i)[1];
+  return bing_of_record(p, r0, r1, __float_as_uint(reinterpret_cast<const float*>(splats + i)[13]), radius, g);
+}
+// min over the tile's pixel-centre box of q(d) = ca dx^2 + 2 cb dx dy + cc dy^2, d = centre - pixel
+__device__ __forceinline__ bool tile_visible(const BinG& g, int tx, int ty) {
+  const float dx0 = g.u - (float)(tx * TILE + TILE - 1), dx1 = g.u - (float)(tx * TILE);
+  const float dy0 = g.v - (float)(ty * TILE + TILE - 1), dy1 = g.v - (float)(ty * TILE);
+  if (dx0 <= 0.f && dx1 >= 0.f && dy0 <= 0.f && dy1 >= 0.f) return true;
+  float qmin = 3.4e38f;
+  const float ica = g.ica, icc = g.icc;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {                      // edges dx = const
+    const float dx = e ? dx1 : dx0;
+    const float dy = fminf(dy1, fmaxf(dy0, -g.cb * dx * icc));
+    qmin = fminf(qmin, g.ca * dx * dx + 2.f * g.cb * dx * dy + g.cc * dy * dy);
+  }
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {                      // edges dy = const
+    const float dy = e ? dy1 : dy0;
+    const float dx = fminf(dx1, fmaxf(dx0, -g.cb * dy * ica));
+    qmin = fminf(qmin, g.ca * dx * dx + 2.f * g.cb * dx * dy + g.cc * dy * dy);
+  }
+  return qmin <= g.thr;
+}
+
+// Near slice without bin_place (raster_api.hip: the tile gather).  The list-form shade appends, for every live Gaussian of
+// the slice's work list, one word per tile ROW of its rect to that row's band: x0 | x1 << 8 | list position << 16 (hence
+// gx <= 255 and a work list of at most 65 536 ids).  The blend's workgroup scans its row's band GATHER_CHUNK entries per
+// round, keeps the entries whose [x0, x1) holds its column - at most GATHER_CAND at a time, the kB half of the sort's arena -
+// (16-bit list positions) and runs tile_visible on those.  Bands and counters live in memory the path leaves unused (bucket1, the main pass'
+// tile counters the cull stage has cleared).
+constexpr int GATHER_CHUNK = 2048;      // band entries scanned per round: eight per thread, all in flight
+constexpr int GATHER_CAND = 4096;       // candidates held before they are tested (every entry scanned may be one)
+constexpr int GATHER_ROWS_MAX = 256;    // tile rows the shade's LDS counters hold
+struct RowBands {
+  uint32_t* count;               // [gy] entries of every band; nullptr: no bands
+  uint32_t* entries;             // [gy][stride]
+  uint32_t stride;
+};
+struct TileGather {
+  const uint32_t* band_count;    // nullptr: lists arrive in the bucket
+  const uint32_t* bands;
+  uint32_t stride;
+  const uint32_t* ids;           // the slice's work list: list position -> Gaussian
+  const int32_t* radii;
+  uint32_t* tile_count;          // [tiles] written: the tile's true number of hits (slice_publish sums them)
+};
+
 // Pinned SH constants (utils/sh_utils.py:26-45 of the reference).
 #define RTGS_SH_C0 0.28209479177387814f
 #define RTGS_SH_C1 0.4886025119029199f

@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
     Splat* __restrict__ splats, uint32_t* __restrict__ tiles_touched, int32_t* __restrict__ radii,
     uint8_t* __restrict__ clamped, int32_t* __restrict__ out_radii, uint32_t* __restrict__ zero_words, int zero_n,
     uint8_t* __restrict__ zbin, float2* __restrict__ uv, SliceList list, SliceSel sel,
-    uint32_t* __restrict__ zero2, int zero2_n) {
+    uint32_t* __restrict__ zero2, int zero2_n, RowBands rb) {
   // no automatic FMA contraction: the three instantiations must round identically (the two-pass forward is tested
   // bit for bit against the single pass)
 #pragma clang fp contract(off)
@@ -169,7 +169,40 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
   } else {
     if (spec_failed(p.spec_fail)) return;      // speculative forward already known to be wrong: the work list is not valid
     if (list.ids) {
-      if (i >= (int)*list.count) return;
+      const int n_list = (int)*list.count;
+      if (rb.count) {
+        // Row bands for the blend that gathers its own lists (raster_common.h: RowBands): list position i, if load_bing would
+        // call its Gaussian live, leaves one word in the band of every tile row of its rect.  Appends are aggregated per
+        // workgroup - LDS counters per row, one global atomic per (workgroup, row touched), then the entries.
+        if ((int)(blockIdx.x * blockDim.x) >= n_list) return;      // (the whole workgroup)
+        __shared__ uint32_t s_rows[GATHER_ROWS_MAX], s_rbase[GATHER_ROWS_MAX];
+        for (int y = threadIdx.x; y < GATHER_ROWS_MAX; y += blockDim.x) s_rows[y] = 0u;
+        __syncthreads();
+        int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+        if (i < n_list) {
+          const int id = (int)list.ids[i];
+          const int rad = radii[id];
+          if (rad > 0 && opac[id] >= 1.f / 255.f) {
+            const float2 c = uv[id];
+            tile_rect_of(c.x, c.y, rad, p.gx, p.gy, x0, y0, x1, y1);
+            if ((x1 - x0) * (y1 - y0) <= 0) y1 = y0;
+          }
+        }
+        for (int y = y0; y < y1; ++y) atomicAdd(&s_rows[y], 1u);
+        __syncthreads();
+        for (int y = threadIdx.x; y < p.gy; y += blockDim.x) {
+          const uint32_t c = s_rows[y];
+          s_rbase[y] = c ? atomicAdd(&rb.count[y], c) : 0u;
+          s_rows[y] = 0u;
+        }
+        __syncthreads();
+        const uint32_t word = (uint32_t)x0 | ((uint32_t)x1 << 8) | ((uint32_t)i << 16);
+        for (int y = y0; y < y1; ++y) {
+          const uint32_t slot = s_rbase[y] + atomicAdd(&s_rows[y], 1u);
+          if (slot < rb.stride) rb.entries[(size_t)y * rb.stride + slot] = word;      // (always: a band holds the whole list)
+        }
+      }
+      if (i >= n_list) return;
       i = (int)list.ids[i];
     } else {
       if (sel.ctr && sel.ctr[0] == 0u) return;   // the slice finished every tile: nobody will read the other Splats
@@ -347,15 +380,16 @@ constexpr int FWD_CHUNKS = FWD_BATCH / 32;      // 32-entry words of a block's s
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-template <int OCC, bool STAMP, bool COUNT, bool ASMW, bool FSORT>
-__global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
+// (the body of the two kernels below: blend_fwd_kernel, and blend_fwd_gather_kernel with the GATHER prologue)
+template <bool STAMP, bool COUNT, bool ASMW, bool FSORT, bool GATHER>
+__device__ __forceinline__ void blend_fwd_body(
     RasterParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const Splat* __restrict__ splats, float* __restrict__ out_color, float* __restrict__ out_depth,
     int32_t* __restrict__ out_cidx, int32_t* __restrict__ out_didx, float* __restrict__ out_cw,
     float* __restrict__ out_dw, float* __restrict__ out_T, uint32_t* __restrict__ n_contrib,
     unsigned long long* __restrict__ counters, SlicePass sp, uint32_t* __restrict__ tile_mode,
     uint32_t* __restrict__ depth_pos, uint32_t* __restrict__ tile_last, int walk, uint32_t* __restrict__ aux_zero,
-    TileCache tc, unsigned long long* __restrict__ stamps, uint32_t seg, FusedSort fs) {
+    TileCache tc, unsigned long long* __restrict__ stamps, uint32_t seg, FusedSort fs, TileGather tg) {
   // ONE raw LDS arena.  The walk's view of it: s_rec 16 KB | s_z 1 KB | s_live 512 B, and (FSORT) the tile's sorted ids
   // behind them, 4 KB.  The sorting prologue's view of the same bytes, BEFORE anything is staged: the bitonic network's
   // keys in [0, 2 KB), or the radix's kA 8 KB | kB 8 KB | digit counters of the four waves 4 KB | digit totals 1 KB | one
@@ -364,6 +398,9 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   constexpr int A_BYTES = FSORT ? A_IDS + FSORT_CAP * 4 : A_IDS;
   static_assert(2 * FSORT_CAP * 8 + (BLOCK / 64 + 1) * 256 * 4 + 4 <= A_IDS + FSORT_CAP * 4, "the radix's LDS fits the arena");
   static_assert(2 * FSORT_CAP * 8 <= A_IDS, "the sorted keys end in front of the id area they are copied to");
+  static_assert(!GATHER || FSORT, "the gathering prologue feeds the sorting one");
+  static_assert(FSORT_CAP * 8 + GATHER_CAND * 2 <= 2 * FSORT_CAP * 8 && GATHER_CHUNK <= GATHER_CAND && GATHER_CHUNK % BLOCK == 0,
+                "the candidates (16-bit list positions) fit the kB half of the sort's arena");
   __shared__ __attribute__((aligned(16))) unsigned char s_arena[A_BYTES];
   float4* const s_rec = reinterpret_cast<float4*>(s_arena);     // u v ca cb | cc o r g | b - - id | nx ny nz pd: the walk reads the first three
   // (entry-major, 64 B per entry.  Four planes of FWD_BATCH float4 - the four rows of a wave read four DIFFERENT entries per
@@ -387,7 +424,10 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   asm volatile("" : "+v"(z));
   // (FSORT on per-tile segments: nobody has written the range yet - it follows from the tile's count)
   uint2 range_v;
-  if (FSORT && fs.count) { const uint32_t x0 = (uint32_t)tile * seg; range_v = make_uint2(x0, x0 + fs.count[tile + z]); }
+  // (GATHER: not even a count - the tile finds its entries in its row's band, whose length is the word it waits for)
+  [[maybe_unused]] uint32_t nb_v = 0u;
+  if constexpr (GATHER) { range_v = make_uint2((uint32_t)tile * seg, (uint32_t)tile * seg); nb_v = tg.band_count[blockIdx.y + z]; }
+  else if (FSORT && fs.count) { const uint32_t x0 = (uint32_t)tile * seg; range_v = make_uint2(x0, x0 + fs.count[tile + z]); }
   else range_v = ranges[tile + z];
   const uint32_t fail_v = p.spec_fail ? p.spec_fail[z] : 0u;
   const int32_t m2_v = sp.mode == 2 ? sp.mask2[tile + z] : 1;
@@ -395,7 +435,7 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   uint32_t id_first = 0u;
   // (FSORT: the unsorted key of segment position tid instead - what the one-key-per-thread sort starts from)
   [[maybe_unused]] unsigned long long key_first = ~0ull;
-  if (FSORT && fs.count) key_first = fs.bucket[(size_t)tile * seg + (size_t)tid];
+  if (FSORT && !GATHER && fs.count) key_first = fs.bucket[(size_t)tile * seg + (size_t)tid];
   if (!FSORT && seg != 0u) id_first = point_list[(size_t)tile * seg + (size_t)tid];     // (inside the tile's segment whatever its count)
   // eight words a later kernel of the caller's step accumulates into (the loss sums of rtgs_slam_map_step): cleared here,
   // stream-ordered before that kernel, instead of by a memset launch of their own
@@ -410,10 +450,98 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   const float tx0 = (float)(blockIdx.x * TILE), ty0 = (float)(blockIdx.y * TILE);
   if (__builtin_amdgcn_readfirstlane((int)fail_v) != 0) return;   // lists were not built (speculative sizes did not hold): redone by the host
   if (__builtin_amdgcn_readfirstlane(m2_v) == 0) return;          // finished by the near slice (or masked off): outputs stay
-  const uint2 range = make_uint2((uint32_t)__builtin_amdgcn_readfirstlane((int)range_v.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)range_v.y));
+  uint2 range = make_uint2((uint32_t)__builtin_amdgcn_readfirstlane((int)range_v.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)range_v.y));
   int n = (int)(range.y - range.x);
   if (sp.mode == 1 && n > SLICE_MAX_LIST) n = 0;       // near-slice list too long to have been sorted: leave the tile to pass 2
   if constexpr (STAMP) { st_range = __builtin_readcyclecounter() - st_cyc; }
+
+  // ---- GATHER: the tile finds its list HERE instead of reading what bin_place scattered (raster_common.h: RowBands).  The
+  // row's band is scanned GATHER_CHUNK entries per round - every load of a thread in flight before the first is used, and the
+  // next round's loads in flight under this round's compaction; the entries whose [x0, x1) holds this column are compacted, as
+  // 16-bit list positions, into the kB half of the sort's arena.  When another round might not fit there (the entries scanned
+  // bound the candidates held: no count is read) and at the end, dense lanes run bin_place's own test on the candidates, two
+  // per thread with the loads of both in flight (bing_of_record / tile_visible: one definition), and compact the hits' keys
+  // into kA, where the sort below takes them from.  All hits are counted - what bin_place leaves in the tile's counter - and
+  // FSORT_CAP of them kept: a longer list leaves its tile to pass 2 (n = 0), as one above SLICE_MAX_LIST does, and the host
+  // redoes the step.
+  if constexpr (GATHER) {
+    constexpr int K = GATHER_CHUNK / BLOCK;
+    unsigned long long* const g_keys = reinterpret_cast<unsigned long long*>(s_arena);
+    uint16_t* const s_cand = reinterpret_cast<uint16_t*>(s_arena + FSORT_CAP * 8);
+    __shared__ uint32_t s_gn[2];                     // candidates held, hits of the tile
+    const int tcol = (int)blockIdx.x, trow = (int)blockIdx.y;
+    const bool on = __builtin_amdgcn_readfirstlane(on_v) != 0;      // (bin_place: mask[t] != 0)
+    const int nb = on ? (int)min((uint32_t)__builtin_amdgcn_readfirstlane((int)nb_v), tg.stride) : 0;
+    const uint32_t* const band = tg.bands + (size_t)trow * tg.stride;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const int wv_u = __builtin_amdgcn_readfirstlane(wv);            // (wave-uniform trip counts: the lanes ballot)
+    // the candidates held so far: test them, keep the hits.  `again`: another round follows - clear the counter behind a barrier
+    auto flush = [&](bool again) {
+      __syncthreads();
+      const int nc = __builtin_amdgcn_readfirstlane((int)s_gn[0]);
+      for (int c0 = wv_u * 64; c0 < nc; c0 += 2 * BLOCK) {
+        const int c_a = c0 + lane, c_b = c_a + BLOCK;
+        const bool v_a = c_a < nc, v_b = c_b < nc;
+        // (clamped, not predicated: position 0 holds a candidate)
+        const int i_a = (int)tg.ids[s_cand[v_a ? c_a : 0]], i_b = (int)tg.ids[s_cand[v_b ? c_b : 0]];
+        const int r_a = tg.radii[i_a], r_b = tg.radii[i_b];
+        const float4 a0 = reinterpret_cast<const float4*>(splats + i_a)[0], a1 = reinterpret_cast<const float4*>(splats + i_a)[1];
+        const float4 b0 = reinterpret_cast<const float4*>(splats + i_b)[0], b1 = reinterpret_cast<const float4*>(splats + i_b)[1];
+        const uint32_t z_a = __float_as_uint(reinterpret_cast<const float*>(splats + i_a)[13]);
+        const uint32_t z_b = __float_as_uint(reinterpret_cast<const float*>(splats + i_b)[13]);
+        BinG g_a, g_b;
+        const bool h_a = v_a && r_a > 0 && bing_of_record(p, a0, a1, z_a, r_a, g_a) && tile_visible(g_a, tcol, trow);
+        const bool h_b = v_b && r_b > 0 && bing_of_record(p, b0, b1, z_b, r_b, g_b) && tile_visible(g_b, tcol, trow);
+        const unsigned long long bal_a = __builtin_amdgcn_ballot_w64(h_a), bal_b = __builtin_amdgcn_ballot_w64(h_b);
+        if ((bal_a | bal_b) == 0ull) continue;
+        const uint32_t n_a = (uint32_t)__popcll(bal_a);
+        uint32_t at = 0u;
+        if (lane == 0) at = atomicAdd(&s_gn[1], n_a + (uint32_t)__popcll(bal_b));
+        at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+        const uint32_t at_a = at + (uint32_t)__popcll(bal_a & lt_mask), at_b = at + n_a + (uint32_t)__popcll(bal_b & lt_mask);
+        if (h_a && at_a < (uint32_t)FSORT_CAP) g_keys[at_a] = ((unsigned long long)z_a << 32) | (unsigned long long)(uint32_t)i_a;
+        if (h_b && at_b < (uint32_t)FSORT_CAP) g_keys[at_b] = ((unsigned long long)z_b << 32) | (unsigned long long)(uint32_t)i_b;
+      }
+      if (again) {
+        __syncthreads();      // the candidates are consumed
+        if (tid == 0) s_gn[0] = 0u;
+        __syncthreads();
+      }
+    };
+    uint32_t ent[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) ent[k] = nb > 0 ? band[min(k * BLOCK + tid, nb - 1)] : 0u;      // (clamped, not predicated)
+    if (tid == 0) { s_gn[0] = 0u; s_gn[1] = 0u; }
+    __syncthreads();
+    int held = 0;      // entries scanned since the last flush: a bound on the candidates held
+    for (int b0 = 0; b0 < nb; b0 += GATHER_CHUNK) {
+      uint32_t nxt[K];
+      const bool more = b0 + GATHER_CHUNK < nb;
+#pragma unroll
+      for (int k = 0; k < K; ++k) nxt[k] = more ? band[min(b0 + GATHER_CHUNK + k * BLOCK + tid, nb - 1)] : 0u;
+      if (held + GATHER_CHUNK > GATHER_CAND) { flush(true); held = 0; }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const uint32_t e = ent[k];
+        const bool m = b0 + k * BLOCK + tid < nb && (int)(e & 0xffu) <= tcol && tcol < (int)((e >> 8) & 0xffu);
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(m);
+        if (bal == 0ull) continue;
+        uint32_t at = 0u;
+        if (lane == 0) at = atomicAdd(&s_gn[0], (uint32_t)__popcll(bal));
+        at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+        if (m) s_cand[at + (uint32_t)__popcll(bal & lt_mask)] = (uint16_t)(e >> 16);
+      }
+      held += GATHER_CHUNK;
+#pragma unroll
+      for (int k = 0; k < K; ++k) ent[k] = nxt[k];
+    }
+    if (held > 0) flush(false);
+    __syncthreads();
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_gn[1]);
+    range.y = range.x + total;
+    n = total <= (uint32_t)FSORT_CAP ? (int)total : 0;
+    if (tid == 0) tg.tile_count[tile] = total;
+  }
 
   // ---- FSORT: the tile's list is sorted HERE, in the arena nothing has been staged into yet, instead of by the three sort
   // launches in front of the blend (raster_bin.hip; same device functions, keys are unique: the same list).  Five other
@@ -427,23 +555,23 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
       if (fs.ranges_out) fs.ranges_out[tile] = range;      // segments: what the first sort launch wrote for the backward
       if (COUNT && fs.tile_class) {
         const uint32_t len = range.y - range.x;
-        const uint32_t cls = len > (uint32_t)SLICE_MAX_LIST ? FSORT_PASS2 : len > (uint32_t)FSORT_CAP ? FSORT_LAUNCH :
+        const uint32_t cls = len > (uint32_t)(GATHER ? FSORT_CAP : SLICE_MAX_LIST) ? FSORT_PASS2 : len > (uint32_t)FSORT_CAP ? FSORT_LAUNCH :
                              len > (uint32_t)FSORT_BITONIC ? FSORT_RADIX : len > 1u ? FSORT_BITONIC_CLS : len == 1u ? FSORT_SINGLE : FSORT_EMPTY;
         fs.tile_class[tile] = (cls << 28) | min(len, 0x0fffffffu);
       }
     }
     if (n >= 1 && n <= FSORT_CAP) {
-      const unsigned long long* const src = fs.bucket + range.x;
       unsigned long long* const kA = reinterpret_cast<unsigned long long*>(s_arena);
+      const unsigned long long* const src = GATHER ? kA : fs.bucket + range.x;      // (GATHER: the keys are in kA already)
       if (n == 1) {
         // no sort: thread 0 holds the only key (and stages it, as position 0 of the first batch)
-        if (tid == 0) { id_mine = (uint32_t)(fs.count ? key_first : src[0]); fs.list_out[range.x] = id_mine; }
+        if (tid == 0) { id_mine = (uint32_t)((fs.count && !GATHER) ? key_first : src[0]); fs.list_out[range.x] = id_mine; }
       } else if (n <= FSORT_BITONIC) {
         // one key per thread: thread t ends with the id of list position t - the first batch stages it from the register;
         // later batches read s_ids behind the barriers of the batch loop.  (The sort returns behind its last barrier.)
         int n2 = 2;
         while (n2 < n) n2 <<= 1;
-        const unsigned long long key = tid < n ? (fs.count ? key_first : src[tid]) : ~0ull;
+        const unsigned long long key = tid < n ? ((fs.count && !GATHER) ? key_first : src[tid]) : ~0ull;
         id_mine = (uint32_t)tile_sort_bitonic_reg<BLOCK>(kA, key, n2);
         if (tid < n) { s_ids[tid] = id_mine; fs.list_out[range.x + tid] = id_mine; }
       } else {
@@ -784,6 +912,33 @@ __global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
   }
 }
 #undef RI
+template <int OCC, bool STAMP, bool COUNT, bool ASMW, bool FSORT>
+__global__ void __launch_bounds__(256, OCC) blend_fwd_kernel(
+    RasterParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+    const Splat* __restrict__ splats, float* __restrict__ out_color, float* __restrict__ out_depth,
+    int32_t* __restrict__ out_cidx, int32_t* __restrict__ out_didx, float* __restrict__ out_cw,
+    float* __restrict__ out_dw, float* __restrict__ out_T, uint32_t* __restrict__ n_contrib,
+    unsigned long long* __restrict__ counters, SlicePass sp, uint32_t* __restrict__ tile_mode,
+    uint32_t* __restrict__ depth_pos, uint32_t* __restrict__ tile_last, int walk, uint32_t* __restrict__ aux_zero,
+    TileCache tc, unsigned long long* __restrict__ stamps, uint32_t seg, FusedSort fs) {
+  blend_fwd_body<STAMP, COUNT, ASMW, FSORT, false>(
+      p, ranges, point_list, splats, out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T, n_contrib, counters, sp, tile_mode,
+      depth_pos, tile_last, walk, aux_zero, tc, stamps, seg, fs, TileGather{nullptr, nullptr, 0u, nullptr, nullptr, nullptr});
+}
+// the near slice of a speculative kind-1 forward that gathers its lists (hand-scheduled walk, fused sort; no stamped twin)
+template <int OCC, bool COUNT>
+__global__ void __launch_bounds__(256, OCC) blend_fwd_gather_kernel(
+    RasterParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+    const Splat* __restrict__ splats, float* __restrict__ out_color, float* __restrict__ out_depth,
+    int32_t* __restrict__ out_cidx, int32_t* __restrict__ out_didx, float* __restrict__ out_cw,
+    float* __restrict__ out_dw, float* __restrict__ out_T, uint32_t* __restrict__ n_contrib,
+    unsigned long long* __restrict__ counters, SlicePass sp, uint32_t* __restrict__ tile_mode,
+    uint32_t* __restrict__ depth_pos, uint32_t* __restrict__ tile_last, int walk, uint32_t* __restrict__ aux_zero,
+    TileCache tc, unsigned long long* __restrict__ stamps, uint32_t seg, FusedSort fs, TileGather tg) {
+  blend_fwd_body<false, COUNT, true, true, true>(
+      p, ranges, point_list, splats, out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T, n_contrib, counters, sp, tile_mode,
+      depth_pos, tile_last, walk, aux_zero, tc, stamps, seg, fs, tg);
+}
 
 
 static int g_f1_occ = [] { const char* e = getenv("RTGS_F1_OCC"); const int v = e ? atoi(e) : 6; return v == 5 ? 5 : 6; }();
@@ -803,7 +958,7 @@ void launch_preprocess_fwd(const RasterParams& p, const float* means, const floa
   hipLaunchKernelGGL(preprocess_fwd_kernel<0>, dim3((p.P + 255) / 256), dim3(256), 0, st, p, means, opac, shs, scales,
                      rots, normal_w, sat, splats, tiles_touched, radii, clamped, out_radii, zero_words, zero_n, zbin,
                      (float2*)nullptr, SliceList{nullptr, nullptr}, SliceSel{0, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr},
-                     (uint32_t*)nullptr, 0);
+                     (uint32_t*)nullptr, 0, RowBands{nullptr, nullptr, 0u});
 }
 // two-pass forward, stage 1: geometry of every Gaussian
 void launch_preprocess_cull(const RasterParams& p, const float* means, const float* scales, const float* rots,
@@ -814,18 +969,19 @@ void launch_preprocess_cull(const RasterParams& p, const float* means, const flo
                      (const float*)nullptr, scales, rots, (const float*)nullptr, (const int32_t*)nullptr, (Splat*)nullptr,
                      tiles_touched, radii, (uint8_t*)nullptr, out_radii, zero_words, zero_n, zbin, uv,
                      SliceList{nullptr, nullptr}, SliceSel{0, nullptr, nullptr, 0u, 0u, nullptr, nullptr, nullptr},
-                     hist_words, hist_words ? CULL_HIST_WORDS : 0);
+                     hist_words, hist_words ? CULL_HIST_WORDS : 0, RowBands{nullptr, nullptr, 0u});
 }
 // two-pass forward, stage 2: Splat records of the work list (max_items bounds its length), or of everything else
 void launch_preprocess_shade(const RasterParams& p, const float* means, const float* opac, const float* shs,
                              const float* scales, const float* rots, const float* normal_w, Splat* splats,
                              int32_t* radii, uint8_t* clamped, float2* uv, SliceList list, SliceSel sel, size_t max_items,
-                             hipStream_t st) {
+                             hipStream_t st, RowBands rb) {
   if (p.P == 0) return;
   const size_t n = list.ids ? (max_items < (size_t)p.P ? max_items : (size_t)p.P) : (size_t)p.P;
   hipLaunchKernelGGL(preprocess_fwd_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, means, opac, shs,
                      scales, rots, normal_w, (const int32_t*)nullptr, splats, (uint32_t*)nullptr, radii, clamped,
-                     (int32_t*)nullptr, (uint32_t*)nullptr, 0, (uint8_t*)nullptr, uv, list, sel, (uint32_t*)nullptr, 0);
+                     (int32_t*)nullptr, (uint32_t*)nullptr, 0, (uint8_t*)nullptr, uv, list, sel, (uint32_t*)nullptr, 0,
+                     list.ids ? rb : RowBands{nullptr, nullptr, 0u});
 }
 // ---------------------------------------------------------------------------------------------
 // recull_rows: what a cache hit launches in place of the cull (MODE 1) and slice_hist (raster_api.hip: the cull cache).
@@ -1003,7 +1159,7 @@ __global__ void __launch_bounds__(256) slice_publish_kernel(int ntiles, const in
                                                             uint32_t* __restrict__ host, uint32_t seq,
                                                             uint32_t* __restrict__ spec_fail,
                                                             const uint32_t* __restrict__ seg_count) {
-  int left = 0, fin = 0, inst = 0;
+  int left = 0, fin = 0, inst = 0, lmax = 0;       // lmax: the longest slice list (per-tile segments: the counts are here anyway)
   constexpr int PUB_IT = 16;                         // up to 4 096 tiles: a thread's loads all leave before the first is used
   if (ntiles <= 256 * PUB_IT) {
     // (as a loop this was one memory round trip per iteration - 13 dependent ones at 1200x680 for 40 KB, 7.6 us)
@@ -1025,19 +1181,22 @@ __global__ void __launch_bounds__(256) slice_publish_kernel(int ntiles, const in
       left += l ? 1 : 0;
       fin += (on && !l) ? 1 : 0;
       inst += (in && seg_count) ? (int)sc[j] : 0;
+      lmax = max(lmax, (in && seg_count) ? (int)sc[j] : 0);
     }
   } else {
     for (int t = threadIdx.x; t < ntiles; t += 256) {
       const bool on = user_mask[t] != 0, l = mask2[t] != 0;
       left += l ? 1 : 0;
       fin += (on && !l) ? 1 : 0;
-      if (seg_count) inst += (int)seg_count[t];      // one-pass placement: nobody scanned the counts, the total is summed here
+      if (seg_count) { inst += (int)seg_count[t]; lmax = max(lmax, (int)seg_count[t]); }      // one-pass placement: nobody scanned the counts, the total is summed here
     }
   }
-  __shared__ int s_l[4], s_f[4], s_i[4];
+  __shared__ int s_l[4], s_f[4], s_i[4], s_m[4];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { left += __shfl_xor(left, off); fin += __shfl_xor(fin, off); inst += __shfl_xor(inst, off); }
-  if ((threadIdx.x & 63) == 0) { s_l[threadIdx.x >> 6] = left; s_f[threadIdx.x >> 6] = fin; s_i[threadIdx.x >> 6] = inst; }
+  for (int off = 32; off > 0; off >>= 1) {
+    left += __shfl_xor(left, off); fin += __shfl_xor(fin, off); inst += __shfl_xor(inst, off); lmax = max(lmax, __shfl_xor(lmax, off));
+  }
+  if ((threadIdx.x & 63) == 0) { s_l[threadIdx.x >> 6] = left; s_f[threadIdx.x >> 6] = fin; s_i[threadIdx.x >> 6] = inst; s_m[threadIdx.x >> 6] = lmax; }
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t L = (uint32_t)(s_l[0] + s_l[1] + s_l[2] + s_l[3]), F = (uint32_t)(s_f[0] + s_f[1] + s_f[2] + s_f[3]);
@@ -1045,7 +1204,8 @@ __global__ void __launch_bounds__(256) slice_publish_kernel(int ntiles, const in
     // speculative forward: the host assumed the slice finishes every tile (recull_rows may have raised the word before)
     if (spec_fail) *spec_fail = (L != 0u || *spec_fail != 0u) ? 1u : 0u;
     const uint32_t R1 = seg_count ? (uint32_t)(s_i[0] + s_i[1] + s_i[2] + s_i[3]) : r1[0];
-    const uint32_t w[7] = {ctr[2], 0u, L, F, R1, ctr[7], 0u};     // [0]: length of the slice's work list  [5]: the view moved under a cached cull
+    const uint32_t LM = (uint32_t)max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
+    const uint32_t w[7] = {ctr[2], LM, L, F, R1, ctr[7], 0u};     // [0]: length of the slice's work list  [1]: its longest tile list (segments)  [5]: the view moved under a cached cull
     publish_to_host(host, w, seq);
   }
 }
@@ -1059,20 +1219,31 @@ void launch_blend_fwd(const RasterParams& p, const uint2* ranges, const uint32_t
                       float* out_color, float* out_depth, int32_t* out_cidx, int32_t* out_didx, float* out_cw,
                       float* out_dw, float* out_T, uint32_t* n_contrib, unsigned long long* counters,
                       SlicePass sp, uint32_t* tile_mode, uint32_t* depth_pos, uint32_t* tile_last, int walk, uint32_t* aux_zero,
-                      TileCache tc, uint32_t seg, hipStream_t st, FusedSort fs) {
+                      TileCache tc, uint32_t seg, hipStream_t st, FusedSort fs, TileGather tg) {
 #define RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, FS) hipLaunchKernelGGL((blend_fwd_kernel<OCC, STAMP, COUNT, ASMW, FS>), dim3(p.gx, p.gy), dim3(BLOCK), 0, st, p, ranges, point_list, splats, \
                        out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T, n_contrib, counters, sp, tile_mode, \
                        depth_pos, tile_last, walk, aux_zero, tc, g_fwd_stamps, seg, fs)
-  // the sorting prologue is a template parameter: the main pass, forwards without a slice and RTGS_F1_ASM=0 run the kernel without it
-#define RTGS_FWD1(OCC, STAMP, COUNT, ASMW) do { if (fs.bucket) RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, true); else RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, false); } while (0)
+#define RTGS_FWD1G(OCC, COUNT) hipLaunchKernelGGL((blend_fwd_gather_kernel<OCC, COUNT>), dim3(p.gx, p.gy), dim3(BLOCK), 0, st, p, ranges, point_list, splats, \
+                       out_color, out_depth, out_cidx, out_didx, out_cw, out_dw, out_T, n_contrib, counters, sp, tile_mode, \
+                       depth_pos, tile_last, walk, aux_zero, tc, g_fwd_stamps, seg, fs, tg)
+  // the sorting prologue is a template parameter: the main pass, forwards without a slice and RTGS_F1_ASM=0 run the kernel without it;
+  // so is the gathering one in front of it (the near slice without bin_place)
+#define RTGS_FWD1(OCC, STAMP, COUNT, ASMW) do { if (fs.bucket && tg.band_count && !STAMP) RTGS_FWD1G(OCC, COUNT); \
+    else if (fs.bucket) RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, true); else RTGS_FWD1F(OCC, STAMP, COUNT, ASMW, false); } while (0)
   if (fs.bucket && (g_f1_asm == 0 || sp.mode != 1)) abort();      // the caller asks blend_fwd_fuses_sort() first
+  // the gather stands on the fused sort over per-tile segments; its stamped twin is not built (the caller asks blend_fwd_gathers())
+  if (tg.band_count && (!(fs.bucket && fs.count && seg != 0u) || g_fwd_stamps)) abort();
   if (g_f1_asm == 0) RTGS_FWD1F(6, false, true, false, false);      // the compiler's walk loop (A-B, tests): RTGS_F1_ASM=0
   else if (counters) RTGS_FWD1(6, false, true, true);        // work counters asked for (bench.py's roofline, tests): the accounting variant
   else if (g_fwd_stamps) RTGS_FWD1(6, true, false, true);
   else if (g_f1_occ == 5) RTGS_FWD1(5, false, false, true); else RTGS_FWD1(6, false, false, true);   // (7 / 8 waves: 79.6 / 79.0 us against 80.3 in round 5; the walk's named registers need 80 VGPRs)
 #undef RTGS_FWD1
 #undef RTGS_FWD1F
+#undef RTGS_FWD1G
 }
 bool blend_fwd_fuses_sort() { return g_f1_asm != 0; }
+// (no stamped variant of the gathering prologue: the backend rejects it - "illegal VGPR to SGPR copy" - so a run with
+// tools/fwd_stamps.py set keeps bin_place)
+bool blend_fwd_gathers() { return g_f1_asm != 0 && g_fwd_stamps == nullptr; }
 
 }  // namespace rtgs

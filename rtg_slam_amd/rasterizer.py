@@ -91,6 +91,18 @@ class RasterContext:
         names = ("empty", "single", "bitonic", "radix", "launch", "pass2")
         return {n: dict(tiles=int(out[3 * k]), shortest=int(out[3 * k + 1]), longest=int(out[3 * k + 2])) for k, n in enumerate(names)}
 
+    def set_tile_gather(self, mode: int):
+        """Speculative near-slice forward: the blend's workgroups gather their lists from row bands, no bin_place
+        (include/rtgs_debug.h).  0 = off, 1 = automatic (default), 2 = forced (tests).  Same lists, same outputs."""
+        _lib.load().rtgs_raster_set_tile_gather_ctx(self.ptr, int(mode))
+
+    def tile_gather_stats(self):
+        """Counts since the context was made, and the two constants the kernel was built with."""
+        out = (C.c_int64 * 6)()
+        _lib.check(_lib.load().rtgs_raster_tile_gather_stats_ctx(self.ptr, out), "rtgs_raster_tile_gather_stats")
+        return dict(gathered=int(out[0]), fell_back_listed=int(out[1]), fell_back_longest=int(out[2]), fell_back_layout=int(out[3]),
+                    chunk=int(out[4]), capacity=int(out[5]))
+
     def set_loss_signs(self, enable: bool):
         """Map step: the loss leaves one sign byte per pixel and the entry walk rebuilds the image gradients from it (default
         on, where the SSIM term is off and every tile takes the entry walk); off = the float planes.  Same gradients."""
