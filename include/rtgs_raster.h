@@ -13,6 +13,20 @@
  * are dense row-major float32 / int32; inputs are borrowed and never written; the call is
  * enqueued on `stream` (a hipStream_t passed as void*).  Return value 0 = success, negative =
  * error (see RTGS_E_*); nothing throws across the boundary.
+ *
+ * The Python binding (rtg_slam_amd/_cdecl.py) READS this header, rtgs_debug.h, rtgs_icp.h and rtgs_slam.h: a new entry
+ * point, struct member or constant is declared here and nowhere else.  The reader understands this C subset and stops the
+ * import on anything outside it:
+ *   - preprocessor: #ifndef / #define / #include / #endif, and the `#ifdef __cplusplus ... #endif` guards, nothing else;
+ *     `#define RTGS_NAME <integer>` (decimal, optionally in parentheses, optionally with an LL suffix) becomes a constant,
+ *     a #define with any other value is refused;
+ *   - types: int, int32_t, int64_t, uint8_t, uint16_t, uint32_t, uint64_t, size_t, float, double, the structs and the callback
+ *     typedef declared here, each written as one word with `const` only in front; pointers to those, to void and to
+ *     the opaque rtgs_ctx; `const char*` as a result only;
+ *   - `typedef struct rtgs_x { ... } rtgs_x;` with plain members (several declarators or several members on a line are fine;
+ *     no bit-fields, arrays, unions or anonymous members), `typedef struct rtgs_x rtgs_x;`, and a callback typedef
+ *     `typedef R (*name)(params);`;
+ *   - functions `R rtgs_name(params);` whose parameter list holds no parenthesis (callbacks go through their typedef).
  */
 #ifndef RTGS_RASTER_H
 #define RTGS_RASTER_H

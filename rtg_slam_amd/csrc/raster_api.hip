@@ -3,6 +3,7 @@
 #include "../../include/rtgs_raster.h"
 #include "../../include/rtgs_debug.h"
 #include "raster_common.h"
+#include "raster_launch.h"
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -11,74 +12,6 @@
 #include <new>
 #include <stdlib.h>
 #include <string.h>
-
-namespace rtgs {
-void launch_mask_sat(const int32_t*, int, int, int32_t*, hipStream_t);
-void launch_preprocess_fwd(const RasterParams&, const float*, const float*, const float*, const float*, const float*,
-                           const float*, const int32_t*, Splat*, uint32_t*, int32_t*, uint8_t*, int32_t*, uint32_t*, int,
-                           uint8_t*, hipStream_t);
-void launch_emit_keys(const RasterParams&, const Splat*, const int32_t*, const uint32_t*, const int32_t*, uint64_t*,
-                      uint32_t*, hipStream_t);
-void launch_tile_ranges(int64_t, const uint64_t*, uint2*, hipStream_t);
-void set_fwd_stamps(void* dev);
-void set_bwd_debug(int bits);
-void set_bwd_stamps(void* dev);
-void launch_blend_fwd(const RasterParams&, const uint2*, const uint32_t*, const Splat*, float*, float*, int32_t*,
-                      int32_t*, float*, float*, float*, uint32_t*, unsigned long long*, SlicePass, uint32_t*, uint32_t*, uint32_t*, int, uint32_t*,
-                      TileCache, uint32_t, hipStream_t, FusedSort fs = FusedSort{nullptr, nullptr, nullptr, nullptr, nullptr},
-                      TileGather tg = TileGather{nullptr, nullptr, 0u, nullptr, nullptr, nullptr});
-bool blend_fwd_fuses_sort();
-bool blend_fwd_gathers();
-void launch_blend_bwd(const RasterParams&, const uint2*, const uint32_t*, const Splat*, const float*, const float*,
-                      const uint32_t*, const int32_t*, const float*, const float*, const uint32_t*, uint32_t*,
-                      const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, int, uint32_t, uint32_t, hipStream_t);
-void launch_blend_bwd_entry(const RasterParams&, const uint2*, const uint32_t*, const Splat*, const float*, const uint32_t*,
-                            const int32_t*, const uint32_t*, const uint32_t*, const float*, const float*, const uint32_t*, uint32_t*,
-                            const BwdInfo*, SplatGrad*, uint8_t*, const uint32_t*, uint32_t, uint32_t, TileCache, uint32_t, hipStream_t,
-                            const LossSigns* signs = nullptr);
-void launch_grad_reduce(int, const uint8_t*, const uint32_t*, uint32_t*, const BwdInfo*, SplatGrad*, const uint32_t*, hipStream_t);
-void launch_preprocess_bwd(const RasterParams&, const float*, const float*, const float*, const float*, const float*,
-                           const float*, const int32_t*, const uint8_t*, SplatGrad*, uint8_t*, uint8_t*, float*, float*,
-                           float*, float*, float*, float*, hipStream_t);
-
-size_t bin_lds_limit_tiles();
-int bin_sort_capacity();
-size_t bin_block_counts_bytes(int, int);
-int launch_bin_count(const RasterParams&, const Splat*, const int32_t*, const int32_t*, uint32_t*, uint16_t*, SliceSel,
-                     SliceList, size_t, hipStream_t);
-size_t bin_slice_block_counts_bytes(int, size_t, int);
-size_t bin_list_block_counts_bytes(int, int);
-void launch_visible_compact(int, const uint8_t*, uint32_t*, uint32_t*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, hipStream_t,
-                            const SliceSel* = nullptr, int32_t* = nullptr, uint32_t* = nullptr);
-void launch_slice_compact(int, SliceSel, uint32_t*, uint32_t*, const uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t*, hipStream_t);
-void launch_slice_publish(int, const int32_t*, const int32_t*, const uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t*, hipStream_t,
-                          const uint32_t* seg_count = nullptr);
-void launch_preprocess_cull(const RasterParams&, const float*, const float*, const float*, uint32_t*, int32_t*, int32_t*,
-                            uint32_t*, int, uint8_t*, float2*, uint32_t*, hipStream_t);
-void launch_recull_rows(const RasterParams&, const float*, const float*, const float*, uint32_t*, int32_t*, int32_t*, uint32_t*,
-                        int, uint8_t*, float2*, uint32_t*, unsigned long long*, uint8_t*, const float*, int, BwdInfoInit,
-                        hipStream_t);
-void launch_cull_check(int, const uint32_t*, const uint32_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-                       const uint8_t*, const uint8_t*, const float2*, const float2*, const uint32_t*, const uint32_t*,
-                       const uint32_t*, unsigned long long*, hipStream_t);
-void launch_preprocess_shade(const RasterParams&, const float*, const float*, const float*, const float*, const float*,
-                             const float*, Splat*, int32_t*, uint8_t*, float2*, SliceList, SliceSel, size_t, hipStream_t,
-                             RowBands rb = RowBands{nullptr, nullptr, 0u});
-void launch_bin_tilescan(int, const uint32_t*, uint2*, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*,
-                         const uint32_t*, const uint32_t*, uint32_t, SpecCaps, hipStream_t);
-void launch_bin_scatter(const RasterParams&, const Splat*, const int32_t*, const int32_t*, const uint16_t*, uint32_t*,
-                        unsigned long long*, SliceSel, SliceList, size_t, hipStream_t);
-void launch_slice_hist(int, const uint8_t*, const uint32_t*, const int32_t*, uint32_t*, unsigned long long*, hipStream_t,
-                       BwdInfoInit bi = BwdInfoInit{nullptr, nullptr, 0u, 0u});
-void launch_bin_tilesort(int, uint32_t, const uint2*, const unsigned long long*, uint32_t*, const uint32_t*, hipStream_t,
-                         const uint32_t* seg_count = nullptr, uint32_t seg = 0, uint2* ranges_out = nullptr,
-                         const BinFinish* finish = nullptr);
-void launch_bin_tilesort_long(int, const uint2*, const unsigned long long*, uint32_t*, const uint32_t*, hipStream_t,
-                              const uint32_t*, uint32_t);
-void launch_bin_place(const RasterParams&, const Splat*, const int32_t*, const int32_t*, uint32_t*, unsigned long long*, uint32_t,
-                      uint32_t*, SliceSel, SliceList, size_t, hipStream_t);
-
-}  // namespace rtgs
 
 // Everything a forward / backward remembers between calls lives in a context (include/rtgs_raster.h: rtgs_ctx).  The
 // plain entry points use one process-wide default context; callers that render from several threads create one

@@ -20,6 +20,7 @@
 // blend_fwd, so removing it changes no output.  The test is the minimum of the conic form over
 // the tile's pixel-centre box against 2 ln(255 o), with a safety margin far above float rounding.
 #include "raster_common.h"
+#include "raster_launch.h"
 #include "raster_tilesort.h"
 #include <mutex>
 

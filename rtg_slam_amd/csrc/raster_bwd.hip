@@ -3,6 +3,7 @@
 // and the per-Gaussian chain rule back to {means3D, opacities, shs, scales, rotations, normal_w}.
 // Math: SURVEY.md Appendix B "Backward"; checked against autograd of oracle/raster_oracle.py.
 #include "raster_common.h"
+#include "raster_launch.h"
 #include "adam_common.h"
 #include "raster_chain.h"
 

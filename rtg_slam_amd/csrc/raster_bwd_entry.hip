@@ -40,6 +40,7 @@
 // its own wave from the block masks (no cross-wave step); one barrier, then the walk.  List positions >= TILE_RECS (a tile
 // walked deeper than 256 entries) and forwards that left no cache (RTGS_FWD_NO_BACKWARD) take the gather path.
 #include "raster_common.h"
+#include "raster_launch.h"
 #include <stdlib.h>
 
 namespace rtgs {

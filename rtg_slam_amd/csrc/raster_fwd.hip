@@ -5,6 +5,7 @@
 // own CUDA sources are an un-vendored submodule (/root/reference/.gitmodules:1-4), its call
 // contract is /root/reference/SLAM/render.py:68-128.
 #include "raster_common.h"
+#include "raster_launch.h"
 #include "raster_tilesort.h"
 #include <stdlib.h>
 

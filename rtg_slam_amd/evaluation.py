@@ -37,11 +37,12 @@ from . import _lib
 from .io_formats import metrics_mean_row
 
 # layout of rtgs_eval_picture's result vector (include/rtgs_slam.h)
-OUT_PSNR, OUT_COLOR_L1, OUT_DEPTH_L1, OUT_VALID_RATIO, OUT_MS_SSIM, OUT_VALID_COUNT = 0, 1, 2, 3, 4, 5
-OUT_MSE, OUT_CS, OUT_SSIM = 6, 9, 24            # [3], [5 levels][3 channels], [5][3]
-PICTURE_OUT = 39
-MS_SSIM_MIN_SIDE = 160                          # pytorch_msssim asserts the smaller side is > 160
-MAX_THRESHOLDS = 16
+OUT_PSNR, OUT_COLOR_L1, OUT_DEPTH_L1, OUT_VALID_RATIO, OUT_MS_SSIM, OUT_VALID_COUNT, OUT_MSE, OUT_CS, OUT_SSIM = (
+    _lib.CONSTANTS["RTGS_EVAL_OUT_" + n] for n in ("PSNR", "COLOR_L1", "DEPTH_L1", "VALID_RATIO", "MS_SSIM", "VALID_COUNT",
+                                                   "MSE", "CS", "SSIM"))    # the last three: [3], [5 levels][3 channels], [5][3]
+PICTURE_OUT = _lib.CONSTANTS["RTGS_EVAL_PICTURE_OUT"]
+MS_SSIM_MIN_SIDE = _lib.CONSTANTS["RTGS_EVAL_MS_SSIM_MIN_SIDE"]      # pytorch_msssim asserts the smaller side is > 160
+MAX_THRESHOLDS = _lib.CONSTANTS["RTGS_EVAL_MAX_THRESHOLDS"]
 
 
 def _dev(*ts):
@@ -51,12 +52,7 @@ def _dev(*ts):
     return ts[0].device
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_p, _stream = _lib.ptr, _lib.stream
 
 
 def picture_metrics(render: torch.Tensor, gt_color: torch.Tensor, depth: torch.Tensor, gt_depth: torch.Tensor,
@@ -477,7 +473,7 @@ class VisibilityCull:
 MESH_RENDER_NEAR = 0.05
 # Boxes of more than this many pixels go to the wave path of csrc/mesh_render.hip (DESIGN.md §4h has the measurement).
 MESH_RENDER_SMALL_MAX = 16
-MESH_TEXTURE_MAX_SIDE = 16384                    # RTGS_MESH_TEXTURE_MAX_SIDE of include/rtgs_slam.h
+MESH_TEXTURE_MAX_SIDE = _lib.CONSTANTS["RTGS_MESH_TEXTURE_MAX_SIDE"]
 
 
 class MeshRenderer:

@@ -28,14 +28,14 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
-def _vp(t: torch.Tensor):
-    return C.c_void_p(t.data_ptr())
-
+_vp = _lib.ptr
 
 _scratch = {}
 _builds = {}            # pyramid builds per scratch: the min / max set alternates (include/rtgs_icp.h)
-FLAG_PERSISTENT, FLAG_CLUSTER, FLAG_SCRATCH_READY, FLAG_FROM_IDENTITY, FLAG_F32_SOLVE, FLAG_LAST_ARRIVER = 1, 2, 4, 8, 16, 32
-PYR_SCRATCH_READY, PYR_SECOND_SET = 1, 2
+FLAG_PERSISTENT, FLAG_CLUSTER, FLAG_SCRATCH_READY, FLAG_FROM_IDENTITY, FLAG_F32_SOLVE, FLAG_LAST_ARRIVER = (
+    _lib.CONSTANTS["RTGS_ICP_FLAG_" + n] for n in ("PERSISTENT", "CLUSTER", "SCRATCH_READY", "FROM_IDENTITY", "F32_SOLVE",
+                                                   "LAST_ARRIVER"))
+PYR_SCRATCH_READY, PYR_SECOND_SET = (_lib.CONSTANTS["RTGS_ICP_PYR_" + n] for n in ("SCRATCH_READY", "SECOND_SET"))
 
 
 def _scratch_key(dev):

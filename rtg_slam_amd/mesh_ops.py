@@ -29,30 +29,25 @@ import torch
 
 from . import _lib
 
-MAX_CELLS = 1 << 21                  # RTGS_MESH_MAX_CELLS: cells per axis, so that a key fits int64
-DECIMATE_MIN_VALENCE = 4             # RTGS_MESH_DECIMATE_MIN_VALENCE
-DECIMATE_MAX_VALENCE = 32            # RTGS_MESH_DECIMATE_MAX_VALENCE
-DECIMATE_MAX_ROUNDS = 1000           # RTGS_MESH_DECIMATE_MAX_ROUNDS
+_K = _lib.CONSTANTS                  # the limits below are the header's (include/rtgs_slam.h)
+MAX_CELLS = _K["RTGS_MESH_MAX_CELLS"]          # cells per axis, so that a key fits int64
+DECIMATE_MIN_VALENCE = _K["RTGS_MESH_DECIMATE_MIN_VALENCE"]
+DECIMATE_MAX_VALENCE = _K["RTGS_MESH_DECIMATE_MAX_VALENCE"]
+DECIMATE_MAX_ROUNDS = _K["RTGS_MESH_DECIMATE_MAX_ROUNDS"]
 _DECIMATE_HASH = 2654435761          # h(u) = u * this mod 2^32: the tie-break between equal costs
-DISTANCE_BLOCK = 4                   # RTGS_MESH_DISTANCE_BLOCK
-DISTANCE_SUPER = 4                   # RTGS_MESH_DISTANCE_SUPER
-DISTANCE_MAX_DIM = 65536             # RTGS_MESH_DISTANCE_MAX_DIM: cells per axis
+DISTANCE_BLOCK = _K["RTGS_MESH_DISTANCE_BLOCK"]
+DISTANCE_SUPER = _K["RTGS_MESH_DISTANCE_SUPER"]
+DISTANCE_MAX_DIM = _K["RTGS_MESH_DISTANCE_MAX_DIM"]      # cells per axis
 DISTANCE_MAX_COORD = float(2 ** 20)  # the largest |coordinate| of a vertex pair_d2 is finite for
 DISTANCE_LARGE_MAX = 64              # cell boxes of more cells go to the wave path of csrc/mesh_distance.hip
 DISTANCE_CELL_EDGES = 2.0            # the default cell in mean edge lengths ("mesh distance", has the measurement)
 DISTANCE_MIN_CELL_SHARE = 512        # ... but not below the mesh's extent / this
 DISTANCE_SORT = True                 # sort the queries by cell first (same section: 6 to 14 times faster)
-REGISTER_OUT = 30                    # RTGS_MESH_REGISTER_OUT: 21 of J J^T, 6 of J r, r r, d2, the count
+REGISTER_OUT = _K["RTGS_MESH_REGISTER_OUT"]    # 21 of J J^T, 6 of J r, r r, d2, the count
 REGISTER_MIN_INLIERS = 6             # fewer correspondences do not determine a rigid motion
 REGISTER_STOP = 1e-6                 # radians and metres: an update below both ends register_to_mesh
 
-
-def _p(t):
-    return C.c_void_p(None if t is None else t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_p, _stream = _lib.ptr0, _lib.stream
 
 
 def _check(vertices, faces, colors=None):

@@ -25,15 +25,9 @@ from . import _lib
 
 MAX_BYTES = 16 << 30                 # default cap of a volume's planes (20 B per voxel)
 BYTES_PER_VOXEL = 20
-BRICK_BYTES = 10240                  # RTGS_TSDF_BRICK_BYTES: 5 planes of 8 x 8 x 8 float32
+BRICK_BYTES = _lib.CONSTANTS["RTGS_TSDF_BRICK_BYTES"]     # 5 planes of 8 x 8 x 8 float32
 
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_p, _stream = _lib.ptr, _lib.stream
 
 
 def _intrinsics(K) -> Tuple[float, float, float, float]:
@@ -445,8 +439,8 @@ _cull_unseen = cull_unseen                        # mesh_from_map has a flag of 
 # texture: a per-face atlas baked from colour views
 # ---------------------------------------------------------------------------------------------------------------------
 
-TEXTURE_MAX_LEVEL = 6                 # RTGS_MESH_TEXTURE_MAX_LEVEL: blocks of 2 .. 64 texels a side
-TEXTURE_MAX_SIDE = 16384              # RTGS_MESH_TEXTURE_MAX_SIDE
+TEXTURE_MAX_LEVEL = _lib.CONSTANTS["RTGS_MESH_TEXTURE_MAX_LEVEL"]     # blocks of 2 .. 64 texels a side
+TEXTURE_MAX_SIDE = _lib.CONSTANTS["RTGS_MESH_TEXTURE_MAX_SIDE"]
 
 
 def texture_atlas_size(T: int) -> Tuple[int, int]:

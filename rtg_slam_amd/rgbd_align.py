@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 
-OUT = 31
+OUT = _lib.CONSTANTS["RTGS_RGBD_ALIGN_OUT"]
 STOP = 1e-6
 MIN_INLIERS = 6
 RANK_TOL = 1e-9
@@ -39,12 +39,7 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
-def _vp(t: torch.Tensor):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_vp, _stream = _lib.ptr, _lib.stream
 
 
 def intensity_pyramid(color: torch.Tensor, levels: int = 3) -> List[torch.Tensor]:

@@ -11,7 +11,6 @@ and signatures so that its callers bind unchanged:
 torch supplies device memory and the current HIP stream; there is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -25,12 +24,7 @@ def _dev(t: torch.Tensor):
     return t.device
 
 
-def _p(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_p, _stream = _lib.ptr0, _lib.stream
 
 
 def _u8(mask: torch.Tensor) -> torch.Tensor:
