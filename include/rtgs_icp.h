@@ -145,6 +145,31 @@ int rtgs_rgbd_align_accumulate(const float* vertex_src, const float* normal_src,
                                float photo_weight, float huber, double* sums_out, void* scratch, void* stream);
 size_t rtgs_rgbd_align_scratch_bytes(int32_t H, int32_t W);
 
+/* Exposure compensation (csrc/rgbd_exposure.hip; tests/rgbd_exposure_reference.py is the definition, matched bit for bit).
+ * A gain alpha and an offset beta take the source frame's intensity into the target's exposure and are unknowns 7 and 8 of the
+ * same normal equations: Ic = alpha I_src, Ic = Ic + beta (two rounded float32 steps), r_I = I_tgt(u, v) - Ic, the Huber weight
+ * on that r_I, J8 = (J_I, -I_src, -1). */
+#define RTGS_RGBD_EXPOSURE_OUT 48
+/* sums_out[48] (device, float64): H upper triangle of the 8 x 8 matrix row-major (36), b (8), sum r_G^2, geometric count,
+ * sum w r_I^2, photometric count; the geometric part enters the 6 x 6 pose block alone.  Arguments, launches and order of
+ * summation are rtgs_rgbd_align_accumulate's; scratch: device, >= rtgs_rgbd_align_exposure_scratch_bytes(H, W).
+ * -1 before anything is launched: what rtgs_rgbd_align_accumulate refuses, and a NaN alpha or beta. */
+int rtgs_rgbd_align_accumulate_exposure(const float* vertex_src, const float* normal_src, const float* intensity_src,
+                                        const float* vertex_tgt, const float* normal_tgt, const float* intensity_tgt, int32_t H,
+                                        int32_t W, const float* K, const float* pose, float distance_threshold,
+                                        float cos_threshold, float photo_weight, float huber, float alpha, float beta,
+                                        double* sums_out, void* scratch, void* stream);
+size_t rtgs_rgbd_align_exposure_scratch_bytes(int32_t H, int32_t W);
+
+/* The intensity pyramid of a composite target, levels as rtgs_rgbd_intensity_pyramid's: per pixel of the full-resolution frame,
+ * where depth_filled != depth_rendered (float32; the model's depth was filled from the frame there) the frame's grey taken
+ * into the map's exposure, alpha grey + beta in two rounded steps, elsewhere the grey of the rendered colour.  render_color,
+ * frame_color [3,H,W]; depth_rendered, depth_filled [H,W].  One launch for the finest level, one per coarser level.
+ * -1: what rtgs_rgbd_intensity_pyramid refuses, or a null pointer. */
+int rtgs_rgbd_target_intensity(const float* render_color, const float* frame_color, const float* depth_rendered,
+                               const float* depth_filled, float alpha, float beta, int32_t H, int32_t W, int32_t levels,
+                               float* const* out_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,9 @@ the tracker's drift, the aligned figures the shape.
 `slam --rgbd-refine [--rgbd-refine-photo-weight L] [--rgbd-refine-huber D]` refines every ICP pose with the joint photometric and
 geometric RGB-D alignment (rtg_slam_amd.rgbd_align) against the previous frame's colour; the keys go into config.yaml only when
 given and run_report.json gains `rgbd_refine` (mean iterations, photometric inliers and ms per frame).
+`--rgbd-refine-target model` takes the map's rendered colour as that target instead, and `--rgbd-refine-exposure` adds a gain
+and an offset between the frame and its target to the unknowns; both need --rgbd-refine, and the report gains `target`,
+`exposure` and the gain / offset statistics only when they are given.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -128,7 +131,15 @@ def cmd_slam(opts) -> int:
         if value is not None and not opts.rgbd_refine:
             log(f"{flag} needs --rgbd-refine")
             return 2
+    for flag, given in (("--rgbd-refine-target", opts.rgbd_refine_target is not None), ("--rgbd-refine-exposure", opts.rgbd_refine_exposure)):
+        if given and not opts.rgbd_refine:
+            log(f"{flag} needs --rgbd-refine")
+            return 2
     if opts.rgbd_refine:
+        if opts.rgbd_refine_target is not None:
+            args.rgbd_refine_target = opts.rgbd_refine_target
+        if opts.rgbd_refine_exposure:
+            args.rgbd_refine_exposure = True
         args.rgbd_refine = True
         if opts.rgbd_refine_photo_weight is not None:
             args.rgbd_refine_photo_weight = float(opts.rgbd_refine_photo_weight)
@@ -148,6 +159,9 @@ def cmd_slam(opts) -> int:
         from . import rgbd_align
         log(f"rgbd refine: on (photo weight {getattr(args, 'rgbd_refine_photo_weight', rgbd_align.DEFAULT_PHOTO_WEIGHT):g}, "
             f"huber {getattr(args, 'rgbd_refine_huber', rgbd_align.DEFAULT_HUBER):g})")
+        if hasattr(args, "rgbd_refine_target") or getattr(args, "rgbd_refine_exposure", False):
+            log(f"rgbd refine: target {getattr(args, 'rgbd_refine_target', 'frame')}, "
+                f"exposure {'on' if getattr(args, 'rgbd_refine_exposure', False) else 'off'}")
     if "device_list" in vars(args):
         log(f"device_list {args.device_list} ignored; running on {opts.device}")
     device = torch.device(opts.device)
@@ -668,6 +682,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="metres per unit of intensity (default 0.25, derived from nominal noise levels, not measured)")
     s.add_argument("--rgbd-refine-huber", type=float, default=None, metavar="D",
                    help="Huber threshold of the intensity residual (default 0.05, a choice, not measured)")
+    s.add_argument("--rgbd-refine-target", choices=("frame", "model"), default=None,
+                   help="photometric target of --rgbd-refine: the previous frame's colour (default) or the map's rendered colour")
+    s.add_argument("--rgbd-refine-exposure", action="store_true",
+                   help="--rgbd-refine also solves for a gain and an offset between the frame's and the target's intensity")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)

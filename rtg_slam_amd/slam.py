@@ -32,6 +32,16 @@ class Tracker:
         self._intensity_t1 = None
         self._K_host = None
         self.rgbd_reports = []
+        # rgbd_refine_target "model": the next frame's photometric target is the map's rendered colour (update_last_status);
+        # rgbd_refine_exposure: the refinement also solves for the gain and offset between source and target
+        self.rgbd_target = str(getattr(args, "rgbd_refine_target", "frame"))
+        self.rgbd_exposure = (1.0, 0.0)                                       # of the frame last refined, into its target's
+        self._color_t1 = None
+        if self.rgbd_target not in ("frame", "model"):
+            raise ValueError(f"rgbd_refine_target must be 'frame' or 'model', not {self.rgbd_target!r}")
+        if not bool(getattr(args, "rgbd_refine", False)):
+            if self.rgbd_target != "frame" or bool(getattr(args, "rgbd_refine_exposure", False)):
+                raise ValueError("rgbd_refine_target: model and rgbd_refine_exposure need rgbd_refine: they are options of that stage")
         if bool(getattr(args, "rgbd_refine", False)):
             from .rgbd_align import RgbdRefiner
             self.rgbd_refiner = RgbdRefiner(args)
@@ -66,6 +76,8 @@ class Tracker:
         self.icp_tracker.move_last_status()
         if self.rgbd_refiner is not None and not self.args.use_gt_pose:
             self.intensity_pyramid_t0 = self._intensity_pyramid(frame_map)       # the next frame's target
+            if self.rgbd_target == "model":
+                self._color_t1 = frame_map["color_chw"]                          # for the composite of update_last_status
         self.pose_es.append(pose)
         frame.updatePose(pose)
         c2w = frame.get_c2w                                                   # transform_map, SLAM/utils.py:56-63; tracker.py:283-288
@@ -91,15 +103,39 @@ class Tracker:
         if self._K_host is None:
             self._K_host = self.curr_frame["K"].detach().cpu().numpy()        # one read per sequence: the tracker's K is fixed
         t0 = time.perf_counter()
-        refined, rep = self.rgbd_refiner.refine(rel, it.vertex_pyramid_t1, it.normal_pyramid_t1, self._intensity_pyramid(frame_map),
-                                                it.vertex_pyramid_t0, it.normal_pyramid_t0, self.intensity_pyramid_t0,
-                                                self._K_host, it.icp_downscales)
+        if self.rgbd_refiner.exposure:
+            # against the previous frame every pair has its own exposure; the map's does not change between frames
+            start = self.rgbd_exposure if self.rgbd_target == "model" else (1.0, 0.0)
+            refined, rep = self.rgbd_refiner.refine(rel, it.vertex_pyramid_t1, it.normal_pyramid_t1, self._intensity_pyramid(frame_map),
+                                                    it.vertex_pyramid_t0, it.normal_pyramid_t0, self.intensity_pyramid_t0,
+                                                    self._K_host, it.icp_downscales, exposure=start)
+            self.rgbd_exposure = rep["exposure"]
+        else:
+            refined, rep = self.rgbd_refiner.refine(rel, it.vertex_pyramid_t1, it.normal_pyramid_t1, self._intensity_pyramid(frame_map),
+                                                    it.vertex_pyramid_t0, it.normal_pyramid_t0, self.intensity_pyramid_t0,
+                                                    self._K_host, it.icp_downscales)
         rep["wall_s"] = time.perf_counter() - t0                  # the source pyramid, the launches, the host reads and solves
         self.rgbd_reports.append(rep)
         return refined
 
-    def update_last_status(self, frame, render_depth, frame_depth, render_normal, frame_normal):
+    @property
+    def wants_render_color(self):
+        """True when update_last_status uses the map's rendered colour (rgbd_refine_target: model)."""
+        return self.rgbd_refiner is not None and self.rgbd_target == "model" and not self.args.use_gt_pose
+
+    def update_last_status(self, frame, render_depth, frame_depth, render_normal, frame_normal, render_color=None):
+        """render_color ([H,W,3] or [3,H,W], the map rendered at this frame's pose) is used in model mode only: the next
+        frame's photometric target becomes the composite of rgbd_align.target_intensity_pyramid - the render's grey, and this
+        frame's own, taken into the map's exposure, where fill_model_depth replaces the model's depth by the frame's."""
+        if render_color is None or not self.wants_render_color or self._color_t1 is None:
+            self.icp_tracker.update_last_status(frame, render_depth, frame_depth, render_normal, frame_normal)
+            return
+        from .rgbd_align import target_intensity_pyramid
+        unfilled = render_depth.clone()
         self.icp_tracker.update_last_status(frame, render_depth, frame_depth, render_normal, frame_normal)
+        alpha, beta = self.rgbd_exposure
+        self.intensity_pyramid_t0 = target_intensity_pyramid(render_color, self._color_t1, unfilled, render_depth, alpha, beta,
+                                                             len(self.icp_tracker.icp_downscales))
 
     def get_new_poses(self):
         """tracker.py:69-74: the trajectory as a back end (ORB-SLAM2 in the reference, out of scope here) has corrected it,
@@ -151,8 +187,12 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         mapper.mapping(frame, frame_map, frame_id)
         mm = mapper.get_render_output(frame)
         # update_last_status fills holes of the model depth IN PLACE (icp.py:397-415): hand it a copy, the render is cached
-        tracker.update_last_status(frame, mm["render_depth"].clone(), frame_map["depth_map"],
-                                   mm["render_normal"].contiguous(), frame_map["normal_map_w"])
+        if tracker.wants_render_color:                          # rgbd_refine_target: model - the render's colour is the next target
+            tracker.update_last_status(frame, mm["render_depth"].clone(), frame_map["depth_map"],
+                                       mm["render_normal"].contiguous(), frame_map["normal_map_w"], mm["render_color"])
+        else:
+            tracker.update_last_status(frame, mm["render_depth"].clone(), frame_map["depth_map"],
+                                       mm["render_normal"].contiguous(), frame_map["normal_map_w"])
         torch.cuda.synchronize(device)                          # the mapper's frame is over when its kernels are
         t2 = time.perf_counter()
         t_track += t1 - t0
@@ -205,4 +245,11 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
             "device_ms_mean": 1e3 * sum(r["device_s"] for r in reps) / k,
             "ms_mean": 1e3 * sum(r["wall_s"] for r in reps) / k,
             "photo_weight": tracker.rgbd_refiner.photo_weight, "huber": tracker.rgbd_refiner.huber}
+        if hasattr(args, "rgbd_refine_target"):
+            report["rgbd_refine"]["target"] = tracker.rgbd_target
+        if tracker.rgbd_refiner.exposure:
+            al = [r["exposure"][0] for r in reps] or [1.0]
+            be = [r["exposure"][1] for r in reps] or [0.0]
+            report["rgbd_refine"].update(exposure=True, alpha_mean=sum(al) / len(al), beta_mean=sum(be) / len(be),
+                                         alpha_min=min(al), alpha_max=max(al))
     return mapper, tracker, report
