@@ -690,6 +690,38 @@ int rtgs_mesh_texture_finish(const int32_t* texel_face, int32_t Wt, int32_t Ht, 
                              const int32_t* origin, const float* colors, const float* acc, uint8_t* image, uint8_t* flags,
                              void* stream);
 
+/* ---- map exposure: every frame's colour in the map's exposure (rtg_slam_amd/map_exposure.py, off by default) ---------------- */
+/* A gain alpha and an offset beta per frame take the frame's colour into the exposure of the map, which frame 0 defines.  They are
+ * fitted on the pixels where the frame and the map rendered at the frame's pose see the same surface; tests/map_exposure_reference.py
+ * is the definition, matched bit for bit.  state: RTGS_MAP_EXPOSURE_STATE doubles on the device, owned by the caller and
+ * initialised to (1, 0, 1, 0, 0, ...): alpha, beta, the (alpha, beta) the current frame started from, the code of its fit (0
+ * accepted, 1 fewer than min_valid valid pixels, 2 no weight, 3 no variance of intensity, 4 not finite, 5 outside
+ * 0.25 <= alpha <= 4, |beta| <= 0.5), the iterations accepted for it, two spare, and at RTGS_MAP_EXPOSURE_SUMS_AT the eight sums of
+ * the last iteration that ran: sum w, w I, w R, w I I, w I R, w r r, the valid pixels, those with |r| <= huber.
+ * fit.  ONE iteration: colours [3][H][W], depths and T_map [H][W] float32.  A pixel is valid when (float32, false for NaN) frame
+ *   depth > 0, render depth > 0, |difference| <= depth_gate, T <= t_gate, lo <= every frame channel <= hi, every render channel
+ *   finite.  I, R = (0.299 r + 0.587 g) + 0.114 b of frame and render; Ic = (float)alpha I, Ic = Ic + (float)beta, r = Ic - R,
+ *   a = |r|; w = 1 when a <= huber else huber / a, and from iteration 1 on 0 where a > cut huber.  The sums are float64 in a fixed
+ *   order (chunks of 1024 pixels, a shuffle / LDS tree, the chunk sums in index order: two runs give the same bits); the solve
+ *   det = S0 S3 - S1 S1, alpha = (S0 S4 - S1 S2) / det, beta = (S2 - alpha S1) / S0 and the tests S6 >= min_valid, S0 > 0,
+ *   det > var_min S0 S0, finite, in range run at the tail of the second launch.  iteration 0 begins a frame: it records the state
+ *   as the frame's start and clears the code.  A rejected iteration restores the start and keeps its code; later iterations of the
+ *   frame (iteration > 0) then change nothing.  scratch: device, at least scratch_bytes(H, W), which is 0 for a size that is refused.
+ * apply.  out = fminf(fmaxf((float)alpha c + (float)beta, 0), 1), two rounded steps, written as [3][H][W] AND as [H][W][3] in one
+ *   launch; the outputs must not be the input.
+ * No host read, no atomics.  Return 0, -1 without a launch (null pointer, H or W <= 0, H W >= 2^31, iteration < 0, huber <= 0,
+ * cut < 1, depth_gate < 0, lo > hi, var_min < 0, min_valid < 1, a NaN), -2 on a launch failure. */
+#define RTGS_MAP_EXPOSURE_STATE 16
+#define RTGS_MAP_EXPOSURE_SUMS 8
+#define RTGS_MAP_EXPOSURE_SUMS_AT 8
+size_t rtgs_map_exposure_scratch_bytes(int32_t H, int32_t W);
+int rtgs_map_exposure_fit(const float* frame_color_chw, const float* frame_depth, const float* render_color_chw,
+                          const float* render_depth, const float* T_map, int32_t H, int32_t W, int32_t iteration, float huber,
+                          float cut, float depth_gate, float t_gate, float lo, float hi, double var_min, int64_t min_valid,
+                          double* state, void* scratch, void* stream);
+int rtgs_map_exposure_apply(const float* color_chw, int32_t H, int32_t W, const double* state, float* out_chw, float* out_hwc,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

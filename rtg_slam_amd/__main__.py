@@ -43,6 +43,10 @@ given and run_report.json gains `rgbd_refine` (mean iterations, photometric inli
 `--rgbd-refine-target model` takes the map's rendered colour as that target instead, and `--rgbd-refine-exposure` adds a gain
 and an offset between the frame and its target to the unknowns; both need --rgbd-refine, and the report gains `target`,
 `exposure` and the gain / offset statistics only when they are given.
+`slam --map-exposure` brings every frame's colour into the map's exposure before the mapper sees it (rtg_slam_amd.map_exposure: a
+gain and an offset per frame, fitted on the device against the map rendered at the frame's pose; frame 0 defines the map's
+exposure); the key goes into config.yaml only when given and run_report.json gains `map_exposure` (the gains and offsets, the
+frames fitted, those that fell back and why, the settings in force).
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -115,6 +119,12 @@ def _apply_resolution_scale(args, opts) -> None:
         args.resolution_scales = scales
 
 
+def _apply_map_exposure(args, opts) -> None:
+    """--map-exposure turns the mapper's exposure stage on (the config's `map_exposure`, absent from every preset)."""
+    if getattr(opts, "map_exposure", False):
+        args.map_exposure = True
+
+
 def cmd_slam(opts) -> int:
     import torch
     from . import config, datasets, io_formats as iof
@@ -145,6 +155,7 @@ def cmd_slam(opts) -> int:
             args.rgbd_refine_photo_weight = float(opts.rgbd_refine_photo_weight)
         if opts.rgbd_refine_huber is not None:
             args.rgbd_refine_huber = float(opts.rgbd_refine_huber)
+    _apply_map_exposure(args, opts)
     save_path = args.save_path
     if os.path.isdir(save_path) and os.listdir(save_path):
         if not opts.overwrite:
@@ -162,6 +173,8 @@ def cmd_slam(opts) -> int:
         if hasattr(args, "rgbd_refine_target") or getattr(args, "rgbd_refine_exposure", False):
             log(f"rgbd refine: target {getattr(args, 'rgbd_refine_target', 'frame')}, "
                 f"exposure {'on' if getattr(args, 'rgbd_refine_exposure', False) else 'off'}")
+    if getattr(args, "map_exposure", False):
+        log("map exposure: on (every frame's colour is fitted to the map's exposure)")
     if "device_list" in vars(args):
         log(f"device_list {args.device_list} ignored; running on {opts.device}")
     device = torch.device(opts.device)
@@ -686,6 +699,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="photometric target of --rgbd-refine: the previous frame's colour (default) or the map's rendered colour")
     s.add_argument("--rgbd-refine-exposure", action="store_true",
                    help="--rgbd-refine also solves for a gain and an offset between the frame's and the target's intensity")
+    s.add_argument("--map-exposure", action="store_true",
+                   help="fit every frame's gain and offset to the map and feed the mapper the corrected colour")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)

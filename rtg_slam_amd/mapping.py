@@ -393,6 +393,11 @@ class Mapping:
         self.stats = dict(added=0, fixed=0, deleted_unstable=0, deleted_stable=0, released=0, local_opts=0, global_opts=0,
                           iterations=0, renders=0, renders_reused=0)
         self.prof = {} if __import__("os").environ.get("RTGS_MAP_PROFILE") else None
+        # extension (off by default): every frame's colour is brought into the map's exposure before it reaches the map
+        self.map_exposure = None
+        if bool(getattr(args, "map_exposure", False)):
+            from .map_exposure import MapExposure
+            self.map_exposure = MapExposure(args, device)
         self.weights = SimpleNamespace(color_weight=args.color_weight, depth_weight=args.depth_weight,
                                        ssim_weight=args.ssim_weight, add_depth_thres=args.add_depth_thres,
                                        normal_weight=float(getattr(args, "normal_weight", 0.0)))
@@ -564,9 +569,18 @@ class Mapping:
                 return self.ops.sample_new_points(fm["vertex_map_w"], fm["normal_map_w"], fm["color_map"], n, m, same)
             return self.ops.sample_pixels(fm["vertex_map_w"], fm["normal_map_w"], fm["color_map"], n, m)
         if self.time == 0:
+            if self.map_exposure is not None:                               # frame 0 defines the map's exposure: nothing to fit
+                fm["color_raw_chw"] = fm["color_chw"]
+                self.map_exposure.skip()
             mask = fm["depth_map"] > 0
             return self._new_points([draw(a.uniform_sample_num, mask)])
         out = self._render(frame, "all")                                    # get_render_output (:727): the model at the new pose
+        if self.map_exposure is not None:
+            # the render and the frame see the same surface: fit the frame's gain and offset against the map on the device, and
+            # from here on - masks, new Gaussians, optimisation targets, keyframe copy, error counters - use the corrected colour
+            fm["color_raw_chw"] = fm["color_chw"]
+            self.map_exposure.fit(fm["color_raw_chw"], fm["depth_map"], out)
+            fm["color_chw"], fm["color_map"] = self.map_exposure.apply(fm["color_raw_chw"])
         # transmission mask / error mask of :728-768 and their sizes in ONE pass over the frame (rtgs_add_masks)
         tmask, emask, counts = self.ops.add_masks(out["T_map"], fm["depth_map"], out["depth"], out["render"], fm["color_chw"],
                                                   out["depth_index_map"], a.add_transmission_thres, a.add_depth_thres,

@@ -252,4 +252,6 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
             be = [r["exposure"][1] for r in reps] or [0.0]
             report["rgbd_refine"].update(exposure=True, alpha_mean=sum(al) / len(al), beta_mean=sum(be) / len(be),
                                          alpha_min=min(al), alpha_max=max(al))
+    if getattr(mapper, "map_exposure", None) is not None:
+        report["map_exposure"] = mapper.map_exposure.report()             # one host read, after the sequence
     return mapper, tracker, report
