@@ -722,6 +722,47 @@ int rtgs_map_exposure_fit(const float* frame_color_chw, const float* frame_depth
 int rtgs_map_exposure_apply(const float* color_chw, int32_t H, int32_t W, const double* state, float* out_chw, float* out_hwc,
                             void* stream);
 
+/* ---- white balance: a gain and an offset per colour channel from one picture to another (csrc/white_balance.hip) ------------- */
+/* The map exposure fit above, four regressions at once: k = 0 on the greys (0.299 r + 0.587 g) + 0.114 b exactly as above, k = 1..3
+ * on the red, green and blue channels themselves.  It serves the mapper (source = frame, target = the map's render;
+ * map_exposure_channels: rgb) and the exposure-aware evaluation (source = the map's render, target = the frame).
+ * tests/white_balance_reference.py is the definition, matched bit for bit.
+ * state: RTGS_WHITE_BALANCE_STATE doubles on the device, owned by the caller.  Regression k owns the RTGS_WHITE_BALANCE_REG doubles
+ * from RTGS_WHITE_BALANCE_REG k: alpha, beta, the (alpha, beta) the current frame started from, its code (the codes above; 3 reads
+ * "no variance of the source"), the iterations accepted for it, two spare; the caller initialises each to (1, 0, 1, 0, 0, ...).  At
+ * RTGS_WHITE_BALANCE_FRAME_AT the frame's code and seven spare; at RTGS_WHITE_BALANCE_SUMS_AT the RTGS_WHITE_BALANCE_SUMS sums of the
+ * last iteration that ran: at 7 k + j of regression k sum w, w s, w t, w s s, w s t, w r r and the pixels with |r| <= huber, at 28 the
+ * valid pixels, then three that stay +0.
+ * fit.  ONE iteration: colours [3][H][W], depths and T_map [H][W] float32.  A pixel is valid when (float32, false for NaN) source
+ *   depth > 0, target depth > 0, |difference| <= depth_gate, T <= t_gate, src_lo <= every source channel <= src_hi, dst_lo <= every
+ *   target channel <= dst_hi, all six finite (the bounds may be infinite).  Per regression, with s and t its source and target
+ *   value: r = ((float)alpha_k s + (float)beta_k) - t in two rounded steps, a = |r|, w = 1 when a <= huber else huber / a, and from
+ *   iteration 1 on 0 where a > cut huber.  The sums are float64 in the fixed order of the map exposure fit; the solve and its tests
+ *   run per regression as above, S28 >= min_valid first.  iteration 0 begins a frame: every regression records its state as the
+ *   frame's start, all codes are cleared.  The frame rule: a refused grey regression (too few valid pixels refuses all four) ends
+ *   the frame's fit - all four return to the frame's start, the frame's code is the grey's, a channel without a code takes its own
+ *   of this iteration, and later iterations of the frame (iteration > 0) change nothing.  Otherwise a channel whose own
+ *   regression is refused takes the grey's (alpha, beta) of this iteration, keeps its code and follows the grey, unsolved, for the
+ *   rest of the frame; the frame's code stays 0.  scratch: device, at least scratch_bytes(H, W), 0 for a size that is refused.
+ * apply.  out_c = fminf(fmaxf((float)alpha_c c + (float)beta_c, 0), 1) for c = 1..3 (the grey regression is not used), written as
+ *   [3][H][W] AND as [H][W][3] in one launch; the outputs must not be the input.
+ * No host read, no atomics.  Return 0, -1 without a launch (null pointer, H or W <= 0, H W >= 2^31, iteration < 0, huber <= 0,
+ * cut < 1, depth_gate < 0, src_lo > src_hi, dst_lo > dst_hi, var_min < 0, min_valid < 1, a NaN), -2 on a launch failure. */
+#define RTGS_WHITE_BALANCE_REGRESSIONS 4
+#define RTGS_WHITE_BALANCE_REG 8
+#define RTGS_WHITE_BALANCE_FRAME_AT 32
+#define RTGS_WHITE_BALANCE_SUMS_AT 40
+#define RTGS_WHITE_BALANCE_SUMS 32
+#define RTGS_WHITE_BALANCE_VALID 28
+#define RTGS_WHITE_BALANCE_STATE 72
+size_t rtgs_white_balance_scratch_bytes(int32_t H, int32_t W);
+int rtgs_white_balance_fit(const float* src_color_chw, const float* src_depth, const float* dst_color_chw, const float* dst_depth,
+                           const float* T_map, int32_t H, int32_t W, int32_t iteration, float huber, float cut, float depth_gate,
+                           float t_gate, float src_lo, float src_hi, float dst_lo, float dst_hi, double var_min, int64_t min_valid,
+                           double* state, void* scratch, void* stream);
+int rtgs_white_balance_apply(const float* color_chw, int32_t H, int32_t W, const double* state, float* out_chw, float* out_hwc,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

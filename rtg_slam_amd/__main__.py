@@ -46,7 +46,10 @@ and an offset between the frame and its target to the unknowns; both need --rgbd
 `slam --map-exposure` brings every frame's colour into the map's exposure before the mapper sees it (rtg_slam_amd.map_exposure: a
 gain and an offset per frame, fitted on the device against the map rendered at the frame's pose; frame 0 defines the map's
 exposure); the key goes into config.yaml only when given and run_report.json gains `map_exposure` (the gains and offsets, the
-frames fitted, those that fell back and why, the settings in force).
+frames fitted, those that fell back and why, the settings in force).  `--map-exposure-channels rgb` fits a gain and an offset per
+colour channel (white balance) instead of one on the grey values; it needs map_exposure to be on and is written only when given.
+`metric --exposure-aware` also scores every render in the frame's own exposure and white balance (an affine correction per
+channel, fitted on the device): eval_metric/exposure_frame_F_iter_I.csv and exposure_report.json, nothing else changes.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
 end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
@@ -125,6 +128,18 @@ def _apply_map_exposure(args, opts) -> None:
         args.map_exposure = True
 
 
+def _apply_map_exposure_channels(args, opts) -> str | None:
+    """--map-exposure-channels sets the config's `map_exposure_channels` (absent from every preset), only when given; -> what is
+    wrong with it, or None.  Call it after _apply_map_exposure."""
+    ch = getattr(opts, "map_exposure_channels", None)
+    if ch is None:
+        return None
+    if not getattr(args, "map_exposure", False):
+        return "--map-exposure-channels needs --map-exposure (or map_exposure: true in the config)"
+    args.map_exposure_channels = ch
+    return None
+
+
 def cmd_slam(opts) -> int:
     import torch
     from . import config, datasets, io_formats as iof
@@ -156,6 +171,10 @@ def cmd_slam(opts) -> int:
         if opts.rgbd_refine_huber is not None:
             args.rgbd_refine_huber = float(opts.rgbd_refine_huber)
     _apply_map_exposure(args, opts)
+    wrong = _apply_map_exposure_channels(args, opts)
+    if wrong is not None:
+        log(wrong)
+        return 2
     save_path = args.save_path
     if os.path.isdir(save_path) and os.listdir(save_path):
         if not opts.overwrite:
@@ -175,6 +194,8 @@ def cmd_slam(opts) -> int:
                 f"exposure {'on' if getattr(args, 'rgbd_refine_exposure', False) else 'off'}")
     if getattr(args, "map_exposure", False):
         log("map exposure: on (every frame's colour is fitted to the map's exposure)")
+        if hasattr(args, "map_exposure_channels"):
+            log(f"map exposure: channels {args.map_exposure_channels}")
     if "device_list" in vars(args):
         log(f"device_list {args.device_list} ignored; running on {opts.device}")
     device = torch.device(opts.device)
@@ -253,6 +274,9 @@ GT_CULL_PLY = "gt_mesh_culled.ply"
 GT_CULL_REPORT = "gt_cull_report.json"
 MESH_DEPTH_REPORT = "mesh_depth_report.json"
 MESH_COLOR_REPORT = "mesh_color_report.json"
+EXPOSURE_REPORT = "exposure_report.json"
+EXPOSURE_COLUMNS = ("frame", "psnr", "psnr_ea", "ssim_ea", "color_l1_ea", "gain_r", "gain_g", "gain_b", "offset_r", "offset_g",
+                    "offset_b", "code")
 MESH_COLOR_DIR = "mesh_color"
 
 
@@ -553,7 +577,20 @@ def cmd_metric(opts) -> int:
     res = evaluation.evaluate_sequence(mapper, info.camera(), source, poses=poses, args=args, gt_points=gt_points,
                                        dist_thres=[0.03], transform=transform, sample_nums=1_000_000, rec_points=rec_points,
                                        gt_cull=gt_cull, mesh_renderer=mesh_renderer, gt_mesh_renderer=gt_mesh_renderer,
-                                       gt_cull_depth=opts.cull_depth, **color_kw)
+                                       gt_cull_depth=opts.cull_depth, exposure_aware=bool(opts.exposure_aware), **color_kw)
+    if opts.exposure_aware:
+        os.makedirs(md_dir, exist_ok=True)
+        ea_path = os.path.join(md_dir, f"exposure_frame_{mapper.time}_iter_{test_iter}.csv")
+        rows = res["exposure_rows"]
+        with open(ea_path, "w") as fo:
+            fo.write(",".join(EXPOSURE_COLUMNS) + "\n")
+            fo.write("".join(",".join(repr(r[k]) for k in EXPOSURE_COLUMNS) + "\n" for r in rows))
+        ea = dict(res["exposure_mean"])
+        ea.update(frames=len(rows), gates=evaluation.exposure_settings(info.height, info.width), device_s=res["exposure_seconds"])
+        with open(os.path.join(md_dir, EXPOSURE_REPORT), "w") as fo:
+            json.dump(ea, fo, indent=1, default=float)
+        log(f"exposure-aware: PSNR {ea.get('psnr', float('nan')):.3f} -> {ea.get('psnr_ea', float('nan')):.3f} dB over {len(rows)} "
+            f"frames, {ea['frames_refused']} refused -> {ea_path}")
     if gt_cull is not None:
         cull_dir = os.path.join(args.save_path, "eval_metric")
         os.makedirs(cull_dir, exist_ok=True)
@@ -701,6 +738,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--rgbd-refine also solves for a gain and an offset between the frame's and the target's intensity")
     s.add_argument("--map-exposure", action="store_true",
                    help="fit every frame's gain and offset to the map and feed the mapper the corrected colour")
+    s.add_argument("--map-exposure-channels", choices=("grey", "rgb"), default=None,
+                   help="with --map-exposure: one gain and offset on the grey values (default) or one per colour channel (white balance)")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)
@@ -745,6 +784,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --surface-distance: ask only for the nearest face within D metres (D > 0.03) - bounded time against "
                         "an un-culled GT; a distance beyond D counts as D in accuracy and completion, P / R / F1 are unchanged, and "
                         "the JSON gains max_distance, beyond_acc and beyond_comp (the samples beyond D)")
+    m.add_argument("--exposure-aware", action="store_true",
+                   help="also score every render after an affine colour correction per channel towards the frame (a robust fit on "
+                        "the device, rtg_slam_amd.evaluation.exposure_aware_picture): eval_metric/exposure_frame_F_iter_I.csv and "
+                        "eval_metric/exposure_report.json; every other file is what it is without the flag")
     m.add_argument("--align", action="store_true",
                    help="after the evaluation, register the scored geometry (the mesh samples with --mesh, else pcd_densify.ply's "
                         "points, else the Gaussian centres) rigidly to the FULL GT surface by point-to-plane ICP on exact nearest "

@@ -86,6 +86,10 @@ def eval_picture(render_output: Dict[str, torch.Tensor], gt_color: torch.Tensor,
     255 * original_depth).  Keys as the reference's `losses`, plus color_l1 (its l1_loss of the colour, logged there)."""
     v = picture_metrics(render_output["render"], gt_color, render_output["depth"], gt_depth, render_output["depth_index_map"],
                         min_depth, max_depth, with_ms_ssim).cpu().tolist()
+    return _picture_result(v, with_ms_ssim)
+
+
+def _picture_result(v, with_ms_ssim: bool) -> Dict:
     return {
         "valid_pixel_ratio": v[OUT_VALID_RATIO],
         "depth_loss": v[OUT_DEPTH_L1],
@@ -95,6 +99,77 @@ def eval_picture(render_output: Dict[str, torch.Tensor], gt_color: torch.Tensor,
         "lpips": None,                                                # needs pretrained AlexNet weights: not computed
         "color_l1": v[OUT_COLOR_L1],
     }
+
+
+# ---- exposure-aware picture metrics: the render brought into the frame's own exposure and white balance before it is scored ----
+
+EXPOSURE_DST_LO, EXPOSURE_DST_HI = 4.0 / 255.0, 251.0 / 255.0        # a clamped frame pixel obeys no affine law
+EXPOSURE_ROW_KEYS = ("psnr_ea", "ssim_ea", "color_l1_ea", "gain_r", "gain_g", "gain_b", "offset_r", "offset_g", "offset_b", "code")
+EXPOSURE_GATES = ("iters", "huber", "cut", "depth_gate", "t_gate", "var_min", "min_valid")
+
+
+def exposure_settings(H: int, W: int, **gates) -> Dict:
+    """The settings of the exposure-aware fit in force: map_exposure's defaults (its depth gate, its schedule) unless given."""
+    from . import map_exposure as me
+    unknown = sorted(set(gates) - set(EXPOSURE_GATES))
+    if unknown:
+        raise ValueError(f"rtg_slam_amd.evaluation: unknown exposure gate(s) {', '.join(unknown)}; known: {', '.join(EXPOSURE_GATES)}")
+    g = {k: gates.get(k, me.DEFAULTS["map_exposure_" + k]) for k in EXPOSURE_GATES}
+    if g["min_valid"] is None:
+        g["min_valid"] = me.min_valid_default(H, W)
+    g.update(dst_lo=EXPOSURE_DST_LO, dst_hi=EXPOSURE_DST_HI)
+    return g
+
+
+def _exposure_aware_vector(render_output: Dict[str, torch.Tensor], gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: float,
+                           max_depth: float, with_ms_ssim: bool = True, **gates) -> torch.Tensor:
+    """-> [PICTURE_OUT + RTGS_WHITE_BALANCE_STATE] float64 on the device, no synchronisation: picture_metrics of the corrected render,
+    then the state of the fit."""
+    from . import map_exposure as me
+    render = render_output["render"]
+    H, W = int(render.shape[-2]), int(render.shape[-1])
+    dev = _dev(render, gt_color, gt_depth)
+    g = exposure_settings(H, W, **gates)
+    lib = _lib.load()
+    maps = [me._f32c(t.detach()) for t in (render, render_output["depth"], gt_color, gt_depth, render_output["T_map"])]
+    for t, k in zip(maps, (3, 1, 3, 1, 1)):
+        if t.numel() != k * H * W:
+            raise ValueError(f"rtg_slam_amd.evaluation: colours must be [3,{H},{W}] and depths / T_map {H * W} values")
+    state = me.white_balance_state(dev)                                   # identity: every frame is fitted on its own
+    scratch = torch.empty(max(lib.rtgs_white_balance_scratch_bytes(H, W) // 8, 1), dtype=torch.float64, device=dev)
+    fit_gates = (g["huber"], g["cut"], g["depth_gate"], g["t_gate"], float("-inf"), float("inf"), g["dst_lo"], g["dst_hi"])
+    for k in range(int(g["iters"])):
+        me.white_balance_fit(lib, maps, H, W, k, fit_gates, g["var_min"], g["min_valid"], state, scratch, dev)
+    chw = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+    hwc = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_white_balance_apply(_p(maps[0]), H, W, _p(state), _p(chw), _p(hwc), _stream(dev))
+    _lib.check(rc, "rtgs_white_balance_apply")
+    corrected = torch.where(state[me.WB_FRAME_AT] != 0, maps[0].reshape(3, H, W), chw)      # a refused fit leaves the render alone
+    v = picture_metrics(corrected, gt_color, render_output["depth"], gt_depth, render_output["depth_index_map"], min_depth,
+                        max_depth, with_ms_ssim)
+    return torch.cat([v, state])
+
+
+def _exposure_aware_result(v, with_ms_ssim: bool) -> Dict:
+    from . import map_exposure as me
+    st = v[PICTURE_OUT:]
+    ab = lambda c, i: st[me.WB_REG * c + i]
+    return {"psnr_ea": v[OUT_PSNR], "ssim_ea": v[OUT_MS_SSIM] if with_ms_ssim else None, "color_l1_ea": v[OUT_COLOR_L1],
+            "gain_r": ab(1, 0), "gain_g": ab(2, 0), "gain_b": ab(3, 0), "offset_r": ab(1, 1), "offset_g": ab(2, 1),
+            "offset_b": ab(3, 1), "code": int(st[me.WB_FRAME_AT])}
+
+
+def exposure_aware_picture(render_output: Dict[str, torch.Tensor], gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: float,
+                           max_depth: float, with_ms_ssim: bool = True, **gates) -> Dict:
+    """The picture metrics of a `Renderer.render` result after an affine colour correction per channel: a state at identity, the
+    four-iteration schedule of rtgs_white_balance_fit with source = the render, target = the frame, T = the render's T_map (the
+    depth gate is map_exposure's, the render's channels unbounded, the frame's within 4/255 .. 251/255), rtgs_white_balance_apply
+    on the render, picture_metrics of the result.  -> psnr_ea, ssim_ea (MS-SSIM; None without it), color_l1_ea, gain_r/g/b,
+    offset_r/g/b and the frame's code; a refused fit (code != 0) leaves the render alone, so the figures are the plain ones.
+    gates: iters, huber, cut, depth_gate, t_gate, var_min, min_valid.  One host read."""
+    v = _exposure_aware_vector(render_output, gt_color, gt_depth, min_depth, max_depth, with_ms_ssim, **gates).cpu().tolist()
+    return _exposure_aware_result(v, with_ms_ssim)
 
 
 def nn_stats(dist2: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
@@ -715,11 +790,13 @@ def mesh_color_metrics(color: torch.Tensor, gt_color: torch.Tensor, face: torch.
 def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, min_depth: Optional[float] = None,
                max_depth: Optional[float] = None, renderer=None, run_picture: bool = True, run_pcd: bool = False,
                gt_points=None, dist_thres: Sequence[float] = (0.03,), sample_nums: int = 1_000_000, transform=None,
-               generator: Optional[torch.Generator] = None, with_ms_ssim: bool = True) -> Dict:
+               generator: Optional[torch.Generator] = None, with_ms_ssim: bool = True, exposure_aware: bool = False,
+               exposure_gates: Optional[Dict] = None, exposure_events: Optional[List] = None) -> Dict:
     """SLAM/eval.py:225-270: the map (mapper.global_params) rendered at `frame` under no_grad, then eval_picture; eval_pcd
     on the map's Gaussian centres when run_pcd and gt_points are given.  renderer=None renders with the mapper's own
     renderer, as slam.py does, through Mapping._render: a full render of the same frame, pose and map made just before
-    (get_render_output) is reused, not redone."""
+    (get_render_output) is reused, not redone.  With exposure_aware the row gains exposure_aware_picture's keys (gates from
+    exposure_gates) in the same single host read; exposure_events, a list, receives the pair of HIP events around that stage."""
     a = mapper.args
     min_depth = a.min_depth if min_depth is None else min_depth
     max_depth = a.max_depth if max_depth is None else max_depth
@@ -727,7 +804,20 @@ def eval_frame(mapper, frame, gt_color: torch.Tensor, gt_depth: torch.Tensor, mi
     with torch.no_grad():
         if run_picture:
             out = mapper._render(frame, "all") if renderer is None else renderer.render(frame, mapper.global_params)
-            losses.update(eval_picture(out, gt_color, gt_depth, min_depth, max_depth, with_ms_ssim))
+            if not exposure_aware:
+                losses.update(eval_picture(out, gt_color, gt_depth, min_depth, max_depth, with_ms_ssim))
+            else:
+                plain = picture_metrics(out["render"], gt_color, out["depth"], gt_depth, out["depth_index_map"], min_depth,
+                                        max_depth, with_ms_ssim)
+                if exposure_events is not None:
+                    exposure_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                    exposure_events[-1][0].record()
+                ea = _exposure_aware_vector(out, gt_color, gt_depth, min_depth, max_depth, with_ms_ssim, **(exposure_gates or {}))
+                if exposure_events is not None:
+                    exposure_events[-1][1].record()
+                v = torch.cat([plain, ea]).cpu().tolist()                                    # the one host read
+                losses.update(_picture_result(v[:PICTURE_OUT], with_ms_ssim))
+                losses.update(_exposure_aware_result(v[PICTURE_OUT:], with_ms_ssim))
         if run_pcd and gt_points is not None:
             losses.update(eval_pcd(mapper.opt.gaussian_data("all")["xyz"], gt_points, dist_thres, transform, sample_nums,
                                    generator))
@@ -740,7 +830,7 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
                       gt_cull: Optional["VisibilityCull"] = None, mesh_renderer: Optional["MeshRenderer"] = None,
                       gt_mesh_renderer: Optional["MeshRenderer"] = None, gt_cull_depth: str = "sensor",
                       mesh_color: Optional[str] = None, mesh_texture_renderer: Optional["MeshRenderer"] = None,
-                      mesh_color_hook=None) -> Dict:
+                      mesh_color_hook=None, exposure_aware: bool = False, exposure_gates: Optional[Dict] = None) -> Dict:
     """metric.py:137-219 over a finished map.  `stream` yields (depth [H,W] metres, colour [3,H,W], GT c2w) as run_sequence's
     does; frame i is rendered at poses[i] (the estimated trajectory, e.g. tracker.pose_es) or, without poses, at its GT pose,
     by a Renderer whose opaque threshold is args.renderer_opaque_threshold_eval (metric.py:138).  With gt_points, the
@@ -762,6 +852,10 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
     need not be the mesh whose depth is scored), else by mesh_renderer.  These rows come under "mesh_color_rows" and
     "mesh_color_mean", read from the device once, after the last frame; everything else is what it is without mesh_color.
     mesh_color_hook(i, source, color) receives every colour render ([3,H,W] on the device) as it is made.
+    With exposure_aware every frame's render is also scored in the frame's own exposure and white balance
+    (exposure_aware_picture, gates from exposure_gates), in the frame's one host read.  These rows come apart, under
+    "exposure_rows" (frame, psnr, psnr_ea, ssim_ea, color_l1_ea, gain_r/g/b, offset_r/g/b, code) and "exposure_mean" (with
+    "frames_refused"), with "exposure_seconds", the device time of the stage; "rows" and "mean" are what they are without it.
     Returns {"rows": one dict per frame (with "frame" and "iter"), "mean": the mean row of metric.py:205-211}."""
     if gt_cull_depth not in ("sensor", "mesh"):
         raise ValueError(f"rtg_slam_amd.evaluation: gt_cull_depth must be 'sensor' or 'mesh', got {gt_cull_depth!r}")
@@ -780,6 +874,8 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
     eval_args.renderer_opaque_threshold = float(getattr(args, "renderer_opaque_threshold_eval", 0.5))
     renderer = Renderer(eval_args)
     rows: List[Dict] = []
+    exposure_rows: List[Dict] = []
+    exposure_events: List = []
     mesh_sums: List[torch.Tensor] = []
     for i, (depth, color, gt_c2w) in enumerate(stream):
         frame = Frame(cam, gt_c2w, mapper.device, uid=i)
@@ -806,7 +902,10 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
             if per_source:
                 color_vectors.append(torch.stack(per_source))
         row = eval_frame(mapper, frame, color, depth, args.min_depth, args.max_depth, renderer=renderer,
-                         with_ms_ssim=with_ms_ssim)
+                         with_ms_ssim=with_ms_ssim, exposure_aware=exposure_aware, exposure_gates=exposure_gates,
+                         exposure_events=exposure_events)
+        if exposure_aware:
+            exposure_rows.append({"frame": i, "psnr": row["psnr"], **{k: row.pop(k) for k in EXPOSURE_ROW_KEYS}})
         row["frame"] = i
         row["iter"] = int(getattr(mapper, "iter", 0))
         rows.append(row)
@@ -821,6 +920,12 @@ def evaluate_sequence(mapper, cam, stream: Iterable, poses=None, args=None, gt_p
             rec = mapper.opt.gaussian_data("all")["xyz"] if rec_points is None else rec_points
             rows[-1].update(eval_pcd(rec, gt_points, dist_thres, transform, sample_nums, generator))
     res = {"rows": rows, "mean": metrics_mean_row(rows)}
+    if exposure_aware:
+        keys = [k for k in ("psnr",) + EXPOSURE_ROW_KEYS if k != "code" and exposure_rows and exposure_rows[0][k] is not None]
+        res["exposure_rows"] = exposure_rows
+        res["exposure_mean"] = {k: float(np.mean([r[k] for r in exposure_rows])) for k in keys}
+        res["exposure_mean"]["frames_refused"] = sum(1 for r in exposure_rows if r["code"] != 0)
+        res["exposure_seconds"] = sum(a.elapsed_time(b) for a, b in exposure_events) * 1e-3    # every frame's host read is behind
     if mesh_renderer is not None:
         n_pixels = int(cam.H) * int(cam.W)
         mesh_rows = []
