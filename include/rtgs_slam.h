@@ -763,6 +763,28 @@ int rtgs_white_balance_fit(const float* src_color_chw, const float* src_depth, c
 int rtgs_white_balance_apply(const float* color_chw, int32_t H, int32_t W, const double* state, float* out_chw, float* out_hwc,
                              void* stream);
 
+/* ---- loop closure: the map moves with its frames (no counterpart in the reference, whose ORB back end corrects poses only;
+ * csrc/map_deform.hip).  tests/map_deform_reference.py restates it in numpy float32; the kernel matches it bit for bit.
+ *
+ * rtgs_map_deform.  xyz [N][3] and raw8 [N][8] (raw opacity | 3 log scales | rotation quaternion w x y z) float32, updated IN
+ *   PLACE; tick [N] = the frame that added the row, int32 (tick_kind 0) or int64 (tick_kind 1); table [n_frames][16] float32,
+ *   16-B aligned: per frame the correction D(f) as the 3 rows of its 3 x 4 matrix (r00 r01 r02 t0 | r10 .. | r20 ..), then its
+ *   unit quaternion (w, x, y, z) - built on the host in float64 and rounded.  Per row, one lane, float32:
+ *     1  f = tick clamped to [0, n_frames - 1]; the 16 values of table[f]
+ *     2  if all 16 compare equal to the identity's (1 0 0 0 | 0 1 0 0 | 0 0 1 0 | 1 0 0 0) the row is NOT written: it stays
+ *        bit-identical, -0.0 included
+ *     3  x' = fmaf(r00, x, fmaf(r01, y, fmaf(r02, z, t0))), y' and z' likewise from rows 1 and 2
+ *     4  q' = q_D (x) q_raw, the Hamilton product, a = q_D, b = q_raw:
+ *          w' = fmaf(-az, bz, fmaf(-ay, by, fmaf(-ax, bx, aw bw)))     x' = fmaf(-az, by, fmaf(ay, bz, fmaf(ax, bw, aw bx)))
+ *          y' = fmaf(az, bx, fmaf(ay, bw, fmaf(-ax, bz, aw by)))       z' = fmaf(az, bw, fmaf(-ay, bx, fmaf(ax, by, aw bz)))
+ *        not normalised: the raw quaternion keeps its norm up to the rounding of a unit q_D
+ *   Opacity, scales and the SH block are not touched (the higher SH bands are NOT rotated).  No atomics, no host read, two runs
+ *   are bit-equal.  Returns 0 (also, without a launch, for N == 0), -1 on a null or misaligned pointer, N < 0 or above
+ *   RTGS_MAP_DEFORM_MAX_ROWS, n_frames < 1 or an unknown tick_kind, -2 on a launch failure. */
+#define RTGS_MAP_DEFORM_MAX_ROWS 2147483647LL
+int rtgs_map_deform(float* xyz, float* raw8, const void* tick, int32_t tick_kind, int64_t N, const float* table,
+                    int32_t n_frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

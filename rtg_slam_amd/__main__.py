@@ -48,11 +48,17 @@ gain and an offset per frame, fitted on the device against the map rendered at t
 exposure); the key goes into config.yaml only when given and run_report.json gains `map_exposure` (the gains and offsets, the
 frames fitted, those that fell back and why, the settings in force).  `--map-exposure-channels rgb` fits a gain and an offset per
 colour channel (white balance) instead of one on the grey values; it needs map_exposure to be on and is written only when given.
+`slam --loop-closure [--loop-closure-min-gap N ...]` closes loops once, after the last frame and before the final global
+optimisation (rtg_slam_amd.loop_closure): keyframe pairs whose estimated poses lie close are registered with the RGB-D alignment,
+the accepted ones join a keyframe pose graph, and the trajectory, the keyframes and the map's Gaussians move with the optimum.
+save_traj/pose_es.npy is then the corrected trajectory, save_traj/pose_es_before_loop_closure.npy the tracked one, and
+run_report.json gains `loop_closure`; the keys go into config.yaml only when given.  Not with use_gt_pose.
 `metric --exposure-aware` also scores every render in the frame's own exposure and white balance (an affine correction per
 channel, fitted on the device): eval_metric/exposure_frame_F_iter_I.csv and exposure_report.json, nothing else changes.
 
 What the reference's configs ask for and this package does not do: device_list (the device is --device), the ORB-SLAM2 back
-end (use_orb_backend: the trajectory is tracked with ICP only) and rendered pictures."""
+end (use_orb_backend: the trajectory is tracked with ICP only; --loop-closure stands in for its loop closing) and rendered
+pictures."""
 from __future__ import annotations
 
 import argparse
@@ -140,6 +146,42 @@ def _apply_map_exposure_channels(args, opts) -> str | None:
     return None
 
 
+LOOP_CLOSURE_FLAGS = (("min_gap", int, "N", "keyframes between the two ends of a loop edge (default 10)"),
+                      ("max_trans", float, "M", "metres between the estimated poses of a candidate pair (default 0.5)"),
+                      ("max_rot_deg", float, "DEG", "degrees between them (default 30)"),
+                      ("max_per_keyframe", int, "N", "candidates registered per keyframe, nearest first (default 2)"),
+                      ("min_inlier_ratio", float, "R", "geometric inliers / valid source pixels an edge needs (default 0.3)"),
+                      ("max_rms", float, "M", "point-to-plane rms an edge may have, metres (default 0.02)"),
+                      ("max_correction_trans", float, "M", "metres a registration may move the estimate (default 0.2)"),
+                      ("max_correction_rot_deg", float, "DEG", "degrees a registration may turn it (default 5)"),
+                      ("odometry_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the odometry edges (default 1 1)"),
+                      ("loop_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the loop edges (default 1 1)"))
+
+
+def _apply_loop_closure(args, opts) -> str | None:
+    """--loop-closure and its --loop-closure-* values set the config's `loop_closure*` keys (absent from every preset), only when
+    given; -> what is wrong with them, or None."""
+    given = [(name, getattr(opts, "loop_closure_" + name, None)) for name, *_ in LOOP_CLOSURE_FLAGS]
+    if getattr(opts, "loop_closure", False):
+        args.loop_closure = True
+    for name, value in given:
+        if value is None:
+            continue
+        if not getattr(args, "loop_closure", False):
+            return f"--loop-closure-{name.replace('_', '-')} needs --loop-closure (or loop_closure: true in the config)"
+        setattr(args, "loop_closure_" + name, list(value) if isinstance(value, (list, tuple)) else value)
+    if not getattr(args, "loop_closure", False):
+        return None
+    if getattr(args, "use_gt_pose", False):
+        return "loop_closure with use_gt_pose: there is no estimated trajectory to correct"
+    try:
+        from .loop_closure import LoopCloser
+        LoopCloser(args)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
 def cmd_slam(opts) -> int:
     import torch
     from . import config, datasets, io_formats as iof
@@ -175,6 +217,10 @@ def cmd_slam(opts) -> int:
     if wrong is not None:
         log(wrong)
         return 2
+    wrong = _apply_loop_closure(args, opts)
+    if wrong is not None:
+        log(wrong)
+        return 2
     save_path = args.save_path
     if os.path.isdir(save_path) and os.listdir(save_path):
         if not opts.overwrite:
@@ -196,6 +242,8 @@ def cmd_slam(opts) -> int:
         log("map exposure: on (every frame's colour is fitted to the map's exposure)")
         if hasattr(args, "map_exposure_channels"):
             log(f"map exposure: channels {args.map_exposure_channels}")
+    if getattr(args, "loop_closure", False):
+        log("loop closure: on (once, after the last frame: keyframe pose graph, corrected trajectory, deformed map)")
     if "device_list" in vars(args):
         log(f"device_list {args.device_list} ignored; running on {opts.device}")
     device = torch.device(opts.device)
@@ -228,6 +276,14 @@ def cmd_slam(opts) -> int:
         return 1
     _save_model(mapper, save_path, mapper.time)
     iof.save_trajectories(save_path, tracker.pose_es, tracker.pose_gt)
+    if "loop_closure" in report:
+        lc = report["loop_closure"]
+        np.save(os.path.join(save_path, "save_traj", POSE_ES_BEFORE_LOOP_CLOSURE),
+                np.stack([np.asarray(p) for p in tracker.pose_es_before_loop_closure], axis=0))
+        log(f"loop closure: {lc['edges']} edges of {len(lc['candidates'])} candidates over {lc['keyframes']} keyframes, correction "
+            f"max {100 * lc.get('correction_max_m', 0.0):.2f} cm / mean {100 * lc.get('correction_mean_m', 0.0):.2f} cm, ATE "
+            f"{100 * lc['ate_rmse_m_before']:.3f} -> {100 * lc['ate_rmse_m']:.3f} cm (aligned "
+            f"{100 * lc['ate_rmse_aligned_m_before']:.3f} -> {100 * lc['ate_rmse_aligned_m']:.3f} cm) in {lc['seconds']['total']:.3f} s")
     ates = prefix_ates(tracker.pose_es, tracker.pose_gt)
     with open(os.path.join(save_path, "save_traj", "ate.txt"), "w") as f:
         f.write("".join(f"{a!r}\n" for a in ates))
@@ -265,6 +321,7 @@ def cmd_slam(opts) -> int:
     return 0
 
 
+POSE_ES_BEFORE_LOOP_CLOSURE = "pose_es_before_loop_closure.npy"
 DENSIFY_PLY = "pcd_densify.ply"
 MESH_PLY = "mesh_tsdf.ply"
 MESH_REPORT = "mesh_report.json"
@@ -740,6 +797,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="fit every frame's gain and offset to the map and feed the mapper the corrected colour")
     s.add_argument("--map-exposure-channels", choices=("grey", "rgb"), default=None,
                    help="with --map-exposure: one gain and offset on the grey values (default) or one per colour channel (white balance)")
+    s.add_argument("--loop-closure", action="store_true",
+                   help="close loops once, after the last frame: keyframe pose graph, corrected trajectory, deformed map "
+                        "(rtg_slam_amd.loop_closure); the defaults of its values are derived, not measured")
+    for name, typ, meta, text in LOOP_CLOSURE_FLAGS:
+        if isinstance(typ, tuple):
+            s.add_argument("--loop-closure-" + name.replace("_", "-"), type=float, nargs=2, default=None, metavar=meta, help=text)
+        else:
+            s.add_argument("--loop-closure-" + name.replace("_", "-"), type=typ, default=None, metavar=meta, help=text)
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)

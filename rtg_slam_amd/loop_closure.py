@@ -1,0 +1,290 @@
+"""Loop closure at the end of a run: keyframe pose graph, corrected trajectory, deformed map ("Loop closure").
+
+    find_candidates     keyframe pairs far apart in time whose ESTIMATED poses lie close (host, deterministic)
+    register_pair       one candidate through rgbd_align.RgbdRefiner.refine from the estimated relative pose -> an edge or a refusal
+    frame_corrections   the keyframes' corrections T'_k T_k^-1 spread over all frames along SE(3) geodesics
+    deform_table        those corrections as the float32 table of rtgs_map_deform (include/rtgs_slam.h)
+    LoopCloser.close    candidates -> edges -> pose_graph.optimize -> trajectory, keyframes and map moved
+
+The option (`loop_closure: True`) is off by default and runs once, after the last frame and before the final global optimisation
+(slam.run_sequence).  Candidates come from the estimated poses alone - there is no place recognition - so a loop whose drift exceeds
+loop_closure_max_trans is not found.  The defaults below are derived from the ICP's gates (icp_distance_threshold 0.1 m,
+icp_normal_threshold 20 degrees) and the drift the README quotes (5 cm over 2 000 frames); none has been measured on real data."""
+from __future__ import annotations
+
+import time
+from types import SimpleNamespace
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import pose_graph
+from .rgbd_align import se3_exp, se3_log
+
+DEFAULTS = {
+    "loop_closure_min_gap": 10,                    # keyframes between the two ends of a loop edge
+    "loop_closure_max_trans": 0.5,                 # metres between the estimated positions: ten times the quoted drift
+    "loop_closure_max_rot_deg": 30.0,              # the views must overlap: half a 60-degree field of view
+    "loop_closure_max_per_keyframe": 2,
+    "loop_closure_min_inlier_ratio": 0.3,          # geometric inliers / valid source pixels at the last level evaluated
+    "loop_closure_max_rms": 0.02,                  # metres, point to plane: a fifth of the ICP's distance gate
+    "loop_closure_max_correction_trans": 0.2,      # metres a registration may move the estimate: four times the quoted drift
+    "loop_closure_max_correction_rot_deg": 5.0,
+    "loop_closure_odometry_weights": (1.0, 1.0),   # (per rad^2, per m^2)
+    "loop_closure_loop_weights": (1.0, 1.0),
+    "loop_closure_huber": None,                    # weighted residual norm beyond which a loop edge pulls linearly; None = off
+}
+
+
+def _angle_deg(R) -> float:
+    return float(np.rad2deg(np.arccos(min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0)))))
+
+
+def find_candidates(poses, frame_ids: Sequence[int], min_gap: int, max_trans: float, max_rot_deg: float,
+                    max_per_keyframe: int) -> List[Tuple[int, int, float, float]]:
+    """For keyframe b (index into `poses`, c2w 4x4 each) the keyframes a with b - a >= min_gap whose pose lies within max_trans
+    metres and max_rot_deg degrees of b's, nearest first (ties: the smaller angle, then the older keyframe), at most
+    max_per_keyframe of them.  -> [(a, b, metres, degrees)] in ascending b.  `frame_ids` (one per keyframe, ascending) only
+    has to match `poses` in length: the gap is counted in keyframes."""
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if len(frame_ids) != P.shape[0]:
+        raise ValueError("find_candidates: one frame id per keyframe pose")
+    if int(min_gap) < 1 or int(max_per_keyframe) < 1 or not (max_trans >= 0 and max_rot_deg >= 0):
+        raise ValueError("find_candidates: min_gap and max_per_keyframe must be >= 1, the bounds not negative")
+    out = []
+    for b in range(P.shape[0]):
+        near = []
+        for a in range(0, b - int(min_gap) + 1):
+            d = float(np.linalg.norm(P[a, :3, 3] - P[b, :3, 3]))
+            ang = _angle_deg(P[a, :3, :3].T @ P[b, :3, :3])
+            if d <= max_trans and ang <= max_rot_deg:
+                near.append((d, ang, a))
+        near.sort()
+        out.extend((a, b, d, ang) for d, ang, a in near[:int(max_per_keyframe)])
+    return out
+
+
+def frame_corrections(keyframe_ids: Sequence[int], poses_old, poses_new, n_frames: int) -> np.ndarray:
+    """[n_frames, 4, 4] float64.  D_k = T'_k T_k^-1 at keyframe k; for f_a <= f < f_b between neighbouring keyframes the SE(3)
+    geodesic D_a exp(s log(D_a^-1 D_b)), s = (f - f_a) / (f_b - f_a); D of the last keyframe for every later frame.  Frame 0
+    is always a keyframe.  A keyframe whose pose did not change gets the identity exactly."""
+    ids = [int(i) for i in keyframe_ids]
+    old = np.asarray(poses_old, dtype=np.float64).reshape(-1, 4, 4)
+    new = np.asarray(poses_new, dtype=np.float64).reshape(-1, 4, 4)
+    if not ids or ids[0] != 0 or any(b <= a for a, b in zip(ids, ids[1:])) or len(ids) != len(old) or len(old) != len(new):
+        raise ValueError("frame_corrections: keyframe ids must ascend from 0, one old and one new pose each")
+    if int(n_frames) <= ids[-1]:
+        raise ValueError("frame_corrections: a keyframe lies beyond the trajectory")
+    D = [np.eye(4) if np.array_equal(n, o) else n @ pose_graph.inverse(o) for o, n in zip(old, new)]
+    out = np.empty((int(n_frames), 4, 4), dtype=np.float64)
+    for k, fa in enumerate(ids):
+        last = k + 1 == len(ids)
+        fb = int(n_frames) if last else ids[k + 1]
+        out[fa] = D[k]
+        if fb - fa > 1:
+            if last or np.array_equal(D[k], D[k + 1]):
+                out[fa + 1:fb] = D[k]
+            else:
+                x = se3_log(pose_graph.inverse(D[k]) @ D[k + 1])
+                for f in range(fa + 1, fb):
+                    out[f] = D[k] @ se3_exp(x * ((f - fa) / (fb - fa)))
+    return out
+
+
+def rotmat_to_quat(R) -> np.ndarray:
+    """Unit quaternion (w, x, y, z), w >= 0, of a rotation matrix, float64 (Shepperd's choice of the largest pivot)."""
+    R = np.asarray(R, dtype=np.float64)
+    t = np.trace(R)
+    if t > 0:
+        s = np.sqrt(t + 1.0) * 2.0
+        q = np.array([0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0) * 2.0
+        q = np.empty(4)
+        q[0] = (R[k, j] - R[j, k]) / s
+        q[1 + i] = 0.25 * s
+        q[1 + j] = (R[j, i] + R[i, j]) / s
+        q[1 + k] = (R[k, i] + R[i, k]) / s
+    q = q / np.sqrt(np.dot(q, q))
+    return -q if q[0] < 0 else q
+
+
+def deform_table(corrections) -> np.ndarray:
+    """[n, 4, 4] float64 -> the table of rtgs_map_deform, float32 [n, 16]: the 3 x 4 matrix row by row, then the rotation's unit
+    quaternion; computed in float64 and rounded once.  An identity correction gives the identity row exactly."""
+    D = np.asarray(corrections, dtype=np.float64).reshape(-1, 4, 4)
+    out = np.empty((D.shape[0], 16), dtype=np.float64)
+    out[:, :12] = D[:, :3, :].reshape(-1, 12)
+    for f in range(D.shape[0]):
+        out[f, 12:] = (1.0, 0.0, 0.0, 0.0) if np.array_equal(D[f, :3, :3], np.eye(3)) else rotmat_to_quat(D[f, :3, :3])
+    return out.astype(np.float32)
+
+
+def register_pair(refiner, src: Dict, tgt: Dict, init_pose, K, downscales, cfg) -> Dict:
+    """One candidate: source keyframe b onto target keyframe a from init_pose = T_a^-1 T_b (source -> target camera).  `src` /
+    `tgt`: {"vertex", "normal", "intensity"} pyramids, coarsest first (LoopCloser._pyramids).  -> {"accepted", "reason", "Z"
+    (4x4 float64, the measured T_a^-1 T_b), the gates' figures}.  The edge is accepted only if the loop ended with reason "done",
+    every solve had full rank (6, or 8 with the exposure unknowns), the geometric inliers of the last evaluation are at least
+    min_inlier_ratio of the valid (z > 0) source pixels of its level, rms_geometric_after <= max_rms, and the correction
+    init_pose^-1 Z stays within max_correction_trans / max_correction_rot_deg."""
+    init = np.asarray(init_pose, dtype=np.float64).reshape(4, 4)
+    Z, rep = refiner.refine(init, src["vertex"], src["normal"], src["intensity"], tgt["vertex"], tgt["normal"], tgt["intensity"],
+                            K, downscales)
+    full = 8 if refiner.exposure else 6
+    levels = [l for l, n in enumerate(rep["iterations"]) if n > 0]
+    out = {"accepted": False, "reason": None, "Z": Z, "refine_reason": rep["reason"], "iterations": list(rep["iterations"]),
+           "rank_min": min(rep["rank"]) if rep["rank"] else 0, "rms_geometric_before": rep["rms_geometric_before"],
+           "rms_geometric_after": rep["rms_geometric_after"], "device_s": rep["device_s"]}
+    inliers = rep["inliers_geometric"][-1] if rep["inliers_geometric"] else 0
+    if levels:
+        valid = int((src["vertex"][levels[-1]][..., 2] > 0).sum().item())
+    else:
+        valid = 0
+    out["inliers"], out["valid_source_pixels"] = int(inliers), valid
+    out["inlier_ratio"] = inliers / valid if valid else 0.0
+    C = pose_graph.inverse(init) @ Z
+    out["correction_trans"] = float(np.linalg.norm(C[:3, 3]))
+    out["correction_rot_deg"] = _angle_deg(C[:3, :3])
+    if rep["reason"] != "done":
+        out["reason"] = "refinement stopped: " + rep["reason"]
+    elif not rep["rank"] or min(rep["rank"]) < full:
+        out["reason"] = f"a solve had rank {out['rank_min']} of {full}"
+    elif out["inlier_ratio"] < cfg.min_inlier_ratio:
+        out["reason"] = f"inlier ratio {out['inlier_ratio']:.3f} below {cfg.min_inlier_ratio:g}"
+    elif not rep["rms_geometric_after"] <= cfg.max_rms:
+        out["reason"] = f"geometric rms {rep['rms_geometric_after']:.4f} m above {cfg.max_rms:g}"
+    elif out["correction_trans"] > cfg.max_correction_trans or out["correction_rot_deg"] > cfg.max_correction_rot_deg:
+        out["reason"] = (f"correction {out['correction_trans']:.3f} m / {out['correction_rot_deg']:.2f} degrees beyond "
+                         f"{cfg.max_correction_trans:g} m / {cfg.max_correction_rot_deg:g} degrees")
+    else:
+        out["accepted"], out["reason"] = True, "accepted"
+    return out
+
+
+def _pair(value, name):
+    try:
+        a, b = (float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be two numbers: (rotation weight, translation weight)") from None
+    if not (a >= 0 and b >= 0 and a + b > 0):
+        raise ValueError(f"{name} must not be negative, and not both zero")
+    return a, b
+
+
+class LoopCloser:
+    """Reads the loop_closure_* keys of `args` with getattr and DEFAULTS, and of the run rgbd_refine_exposure / map_exposure
+    (either selects the eight-unknown registration), icp_downscales and the RGB-D refiner's own keys.  `close` is meant for
+    the end of a run: the tracker's ICP state and the mapper's window of recent frame maps are not corrected."""
+
+    def __init__(self, args):
+        get = lambda k: getattr(args, k, DEFAULTS[k])
+        self.args = args
+        self.cfg = cfg = SimpleNamespace(
+            min_gap=int(get("loop_closure_min_gap")), max_trans=float(get("loop_closure_max_trans")),
+            max_rot_deg=float(get("loop_closure_max_rot_deg")), max_per_keyframe=int(get("loop_closure_max_per_keyframe")),
+            min_inlier_ratio=float(get("loop_closure_min_inlier_ratio")), max_rms=float(get("loop_closure_max_rms")),
+            max_correction_trans=float(get("loop_closure_max_correction_trans")),
+            max_correction_rot_deg=float(get("loop_closure_max_correction_rot_deg")),
+            odometry_weights=_pair(get("loop_closure_odometry_weights"), "loop_closure_odometry_weights"),
+            loop_weights=_pair(get("loop_closure_loop_weights"), "loop_closure_loop_weights"),
+            huber=None if get("loop_closure_huber") is None else float(get("loop_closure_huber")))
+        if cfg.min_gap < 1 or cfg.max_per_keyframe < 1:
+            raise ValueError("loop_closure_min_gap and loop_closure_max_per_keyframe must be >= 1")
+        for k in ("max_trans", "max_rot_deg", "max_rms", "max_correction_trans", "max_correction_rot_deg"):
+            if not getattr(cfg, k) >= 0:
+                raise ValueError(f"loop_closure_{k} must not be negative")
+        if not 0 <= cfg.min_inlier_ratio <= 1:
+            raise ValueError("loop_closure_min_inlier_ratio must lie in [0, 1]")
+        if cfg.huber is not None and not cfg.huber > 0:
+            raise ValueError("loop_closure_huber must be positive")
+        from .rgbd_align import RgbdRefiner
+        exposure = bool(getattr(args, "rgbd_refine_exposure", False)) or bool(getattr(args, "map_exposure", False))
+        ref_args = SimpleNamespace(**{k: v for k, v in vars(args).items() if k.startswith(("rgbd_refine_", "icp_"))})
+        ref_args.rgbd_refine_exposure = exposure
+        self.refiner = RgbdRefiner(ref_args)
+        self.downscales = list(getattr(args, "icp_downscales", (0.25, 0.5, 1.0)))
+
+    def _pyramids(self, keymap, K, cache, key):
+        from . import icp
+        from .rgbd_align import intensity_pyramid
+        hit = cache.get(key)
+        if hit is None:
+            depth = keymap["depth_chw"]
+            v, n = icp.build_pyramids(depth.reshape(depth.shape[-2], depth.shape[-1]), K, len(self.downscales))
+            hit = {"vertex": v, "normal": n, "intensity": intensity_pyramid(keymap["color_chw"], len(self.downscales))}
+            if len(cache) >= 4:                                                # a keyframe's pyramids are 4/3 of 28 B a pixel
+                cache.pop(next(iter(cache)))
+            cache[key] = hit
+        return hit
+
+    def close(self, mapper, tracker) -> Dict:
+        """-> the report (JSON-able).  Without an accepted edge nothing is changed: poses, keyframes and map stay bit-identical."""
+        from . import slam_ops
+        from .slam import ate_rmse
+        cfg, dev = self.cfg, mapper.device
+        if mapper.opt.world != 1:
+            raise RuntimeError("loop closure runs on one rank")
+        n = len(tracker.pose_es)
+        ids = [int(i) for i in mapper.keyframe_ids]
+        t0 = time.perf_counter()
+        rep = {"keyframes": len(ids), "frames": n, "options": {k: (list(v) if isinstance(v, tuple) else v) for k, v in vars(cfg).items()},
+               "exposure_unknowns": bool(self.refiner.exposure), "candidates": [], "edges": 0, "changed": False, "seconds": {}}
+        if not ids or n == 0:
+            return rep
+        if ids[0] != 0 or ids[-1] >= n or int(mapper.time) != n:
+            raise RuntimeError("loop closure: the keyframes, the trajectory and the map's ticks do not belong to one run")
+        gt = tracker.pose_gt if len(tracker.pose_gt) == n else None
+        old = [np.array(tracker.pose_es[i], dtype=np.float64) for i in ids]
+        cands = find_candidates(old, ids, cfg.min_gap, cfg.max_trans, cfg.max_rot_deg, cfg.max_per_keyframe)
+        t1 = time.perf_counter()
+        K = mapper.keyframe_list[0].K
+        cache, loop_edges = {}, []
+        for a, b, dist, ang in cands:
+            init = pose_graph.inverse(old[a]) @ old[b]
+            r = register_pair(self.refiner, self._pyramids(mapper.keymap_list[b], K, cache, b),
+                              self._pyramids(mapper.keymap_list[a], K, cache, a), init, K, self.downscales, cfg)
+            Z = r.pop("Z")
+            r.update(a=a, b=b, frame_a=ids[a], frame_b=ids[b], distance_m=dist, angle_deg=ang)
+            rep["candidates"].append(r)
+            if r["accepted"]:
+                loop_edges.append((a, b, Z, cfg.loop_weights[0], cfg.loop_weights[1], True))
+        del cache
+        t2 = time.perf_counter()
+        rep["edges"] = len(loop_edges)
+        rep["seconds"].update(candidates=t1 - t0, registration=t2 - t1)
+        if gt is not None:
+            rep["ate_rmse_m_before"] = rep["ate_rmse_m"] = ate_rmse(tracker.pose_es, gt)
+            rep["ate_rmse_aligned_m_before"] = rep["ate_rmse_aligned_m"] = ate_rmse(tracker.pose_es, gt, True)
+        if not loop_edges:
+            rep["seconds"]["total"] = time.perf_counter() - t0
+            return rep
+        edges = [(k - 1, k, pose_graph.inverse(old[k - 1]) @ old[k], cfg.odometry_weights[0], cfg.odometry_weights[1])
+                 for k in range(1, len(ids))] + loop_edges
+        new, graph = pose_graph.optimize(old, edges, fixed=0, huber=cfg.huber)
+        t3 = time.perf_counter()
+        D = frame_corrections(ids, old, new, n)
+        moved = np.linalg.norm(D[:, :3, 3] + np.einsum("fij,fj->fi", D[:, :3, :3] - np.eye(3),
+                                                       np.stack([p[:3, 3] for p in tracker.pose_es])), axis=1)
+        rep["graph"] = graph
+        rep["correction_max_m"], rep["correction_mean_m"] = float(moved.max()), float(moved.mean())
+        rep["correction_max_deg"] = max(_angle_deg(d[:3, :3]) for d in D)
+        poses = [D[f] @ np.asarray(tracker.pose_es[f], dtype=np.float64) for f in range(n)]
+        tracker.pose_es[:] = poses
+        mapper.update_poses(poses)
+        for k, km in enumerate(mapper.keymap_list):
+            if "normal_map_w" in km and not np.array_equal(D[ids[k]][:3, :3], np.eye(3)):
+                rot = np.eye(4, dtype=np.float32)
+                rot[:3, :3] = D[ids[k]][:3, :3]
+                km["normal_map_w"] = slam_ops.transform_map(km["normal_map_w"], torch.from_numpy(rot))
+        table = torch.from_numpy(deform_table(D)).to(dev)
+        mapper.opt.deform_rows(table)
+        torch.cuda.synchronize(dev)
+        t4 = time.perf_counter()
+        rep["changed"] = True
+        if gt is not None:
+            rep["ate_rmse_m"], rep["ate_rmse_aligned_m"] = ate_rmse(poses, gt), ate_rmse(poses, gt, True)
+        rep["seconds"].update(graph=t3 - t2, apply=t4 - t3, total=t4 - t0)
+        return rep

@@ -744,6 +744,46 @@ class ShardedMapOptimizer:
         _lib.check(rc, "rtgs_history_merge")
         self._act_valid = False            # scaling and rotation moved outside the step's tail
 
+    def deform_rows(self, table: torch.Tensor, tick: Optional[torch.Tensor] = None):
+        """Move every row - frozen and trainable - by the rigid correction of the frame that added it (rtgs_map_deform,
+        include/rtgs_slam.h): `table` float32 [n_frames, 16] on the device (loop_closure.deform_table), `tick` int32 or int64
+        [>= N] or [>= N, 1], default aux["add_tick"].  A row a release moved back to the unstable cloud carries the tick of its
+        RELEASE (Mapping.gaussians_release), not of its creation, and moves with that frame: accepted.  Only between
+        optimisations: it raises inside a global optimisation and on several ranks, and a local optimisation that was still
+        open loses its snapshots, so that its history_merge() refuses instead of blending the old positions back in.
+        Everything derived from the old rows is dropped: the activated copies, the attach and history snapshots, and - through
+        `version`, `_frozen_version` and the map epoch - the renders, neighbour structures and per-row cull results others keep."""
+        from . import _lib
+        if self._scope != "local" or self.world != 1:
+            raise RuntimeError("deform_rows(): one rank, local scope (not inside a global optimisation)")
+        tick = self.aux.get("add_tick") if tick is None else tick
+        if tick is None:
+            raise RuntimeError("deform_rows() needs the rows' frames: aux['add_tick'] or tick=")
+        if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2
+                and table.shape[1] == 16 and table.shape[0] >= 1 and table.is_contiguous() and table.device == self.device):
+            raise ValueError("deform_rows(): table must be a contiguous float32 [n_frames, 16] on the map's device")
+        if tick.dtype not in (torch.int32, torch.int64) or tick.device != self.device or not tick.is_contiguous():
+            raise ValueError("deform_rows(): tick must be a contiguous int32 or int64 array on the map's device")
+        if tick.numel() != tick.shape[0] or tick.shape[0] < self.N:
+            raise ValueError("deform_rows(): tick must hold one value per row")
+        self.flush()
+        if self.N == 0:
+            return
+        lib = _lib.load()
+        st, dev = self.state, self.device
+        self.version += 1
+        self._frozen_version += 1
+        self._map_epoch += 1                # no kept cull survives, whatever _next_map_epoch would conclude
+        self._epoch_seen = None
+        with torch.cuda.device(dev):
+            rc = lib.rtgs_map_deform(_lib.ptr(st["xyz"]["p"]), _lib.ptr(st["raw8"]["p"]), _lib.ptr(tick),
+                                     0 if tick.dtype == torch.int32 else 1, int(self.N), _lib.ptr(table), int(table.shape[0]),
+                                     _lib.stream(dev))
+        _lib.check(rc, "rtgs_map_deform")
+        self._act_valid = False             # rotations and the normals derived from them moved
+        self.attach_init = None             # snapshots of the old positions: the next begin_local_optimization() retakes them
+        self._history = None
+
     def attach_loss(self) -> torch.Tensor:
         """Value of the attach regulariser at the current parameters (mapper.py:384-401; `scale_loss` of the
         reference's report) - a device scalar.  The one-call step applies its gradient without evaluating it."""

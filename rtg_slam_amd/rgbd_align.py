@@ -229,6 +229,38 @@ def se3_exp(x) -> np.ndarray:
     return T
 
 
+def se3_log(T) -> np.ndarray:
+    """The twist x = (w, v) with se3_exp(x) = T, float64, |w| <= pi: the inverse of `se3_exp` in its conventions (rotation
+    first, translation = J_l v).  The axis comes from the skew part of R, and near pi from the symmetric part of R, where the skew
+    part vanishes."""
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    R, t = T[:3, :3], T[:3, 3]
+    c = min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))
+    s = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])      # sin(th) axis
+    sn = np.sqrt(np.dot(s, s))
+    th = np.arctan2(sn, c)
+    if th <= 1e-8:
+        w = s                                                                         # sin(th) / th = 1 to rounding
+    elif c > -0.99:
+        w = s * (th / sn)
+    else:
+        B = ((R + R.T) / 2.0 - c * np.eye(3)) / (1.0 - c)                             # a a^T: (R + R^T) / 2 = cos I + (1 - cos) a a^T
+        k = int(np.argmax(np.diag(B)))
+        a = B[:, k] / np.sqrt(B[k, k])
+        a = a / np.sqrt(np.dot(a, a))
+        if np.dot(a, s) < 0:
+            a = -a
+        w = a * th
+    Wh = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    W2 = Wh @ Wh
+    I = np.eye(3)
+    if th <= 1e-8:
+        Jl = I
+    else:
+        Jl = I + Wh * ((1.0 - np.cos(th)) / (th * th)) + W2 * ((th - np.sin(th)) / (th * th * th))
+    return np.concatenate([w, np.linalg.solve(Jl, t)])
+
+
 def level_K(K, downscale) -> np.ndarray:
     Kl = np.asarray(K, dtype=np.float32).reshape(3, 3) * np.float32(downscale)
     Kl[2, 2] = np.float32(1)

@@ -139,7 +139,8 @@ class Tracker:
 
     def get_new_poses(self):
         """tracker.py:69-74: the trajectory as a back end (ORB-SLAM2 in the reference, out of scope here) has corrected it,
-        or None without one - Mapping.update_poses(None) then leaves every frame where it is."""
+        or None without one - Mapping.update_poses(None) then leaves every frame where it is.  While the run goes on there is
+        none: the loop closure (`loop_closure`, rtg_slam_amd.loop_closure) corrects the trajectory once, after the last frame."""
         return None
 
 
@@ -168,10 +169,20 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
     eval_every (the reference's save_step, slam.py:98-110, 130-138): evaluate the map (rtg_slam_amd.evaluation.eval_frame)
     at mapper.time 0 and whenever (time + 1) % eval_every == 0, after the frame's mapping clock stops and on the full render
     get_render_output just made; with final_global, once more after the final global optimisation on the last keyframe and
-    its raw colour / depth.  The rows are report["eval"].  None (default): no evaluation, the report as without it."""
+    its raw colour / depth.  The rows are report["eval"].  None (default): no evaluation, the report as without it.
+
+    args.loop_closure (absent = off): after the last frame and before the final global optimisation the loop closure runs once
+    (loop_closure.LoopCloser.close): report["loop_closure"] is its report, the trajectory, the keyframes and the map are the
+    corrected ones, and tracker.pose_es_before_loop_closure keeps the trajectory as it was tracked."""
     from . import evaluation
     mapper = mapper if mapper is not None else Mapping(args, device, capacity=capacity, lr_scale=lr_scale)
     tracker = Tracker(args, device)
+    closer = None
+    if bool(getattr(args, "loop_closure", False)):
+        from .loop_closure import LoopCloser
+        if mapper.opt.world != 1:
+            raise RuntimeError("loop_closure runs on one rank: the map deformation is not exchanged between ranks")
+        closer = LoopCloser(args)                               # a bad option stops the run before its first frame
     t_track, t_map, per_frame = 0.0, 0.0, []
     evals, last_kf = [], None
     n = 0
@@ -209,6 +220,10 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
             on_frame(frame_id, frame, frame_map, mapper, tracker)
         mapper.time += 1
         n += 1
+    closure = None
+    if closer is not None and n > 0:
+        tracker.pose_es_before_loop_closure = [np.array(p, dtype=np.float64) for p in tracker.pose_es]
+        closure = closer.close(mapper, tracker)
     if final_global and n > 0:
         mapper.global_optimization(select_keyframe_num=-1, is_end=True)
         torch.cuda.synchronize(device)
@@ -235,6 +250,8 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
     }
     if eval_every:
         report["eval"] = evals
+    if closure is not None:
+        report["loop_closure"] = closure
     if tracker.rgbd_refiner is not None:
         reps = tracker.rgbd_reports
         k = max(len(reps), 1)
