@@ -242,7 +242,7 @@ class HipOps:
         pick = idx[:n_cand][torch.randperm(n_cand, device=idx.device, generator=self.gen)[:k]].long()
         if k == 3:                                       # the reference's torch.cross quirk (compute_rot): keep the torch form
             nrm = normal.reshape(-1, 3)[pick]
-            nrm = nrm / (torch.norm(nrm, p=2, dim=-1, keepdim=True) + 1e-8)
+            nrm = unit_normals(nrm)
             if identity_rot:
                 rot = torch.zeros(3, 4, device=nrm.device)
                 rot[:, 0] = 1
@@ -278,7 +278,7 @@ class HipOps:
             pick = idx[:n_cand][torch.randperm(n_cand, device=idx.device, generator=self.gen)[:k]].long()
             if k == 3:                                   # the reference's torch.cross quirk (compute_rot): keep the torch form
                 nrm = normal.reshape(-1, 3)[pick]
-                nrm = nrm / (torch.norm(nrm, p=2, dim=-1, keepdim=True) + 1e-8)
+                nrm = unit_normals(nrm)
                 if identity_rot:
                     rot = torch.zeros(3, 4, device=nrm.device)
                     rot[:, 0] = 1
@@ -343,7 +343,23 @@ class HipOps:
 
 
 def RGB2SH(rgb):
-    return (rgb - 0.5) / SH_C0
+    """(rgb - 0.5) / C0 as a TRUE float32 division on every device.  `tensor / python scalar` is one on the CPU, but on the GPU
+    torch multiplies by the reciprocal 1 / C0 instead - one ulp away from the CPU form and from rtgs_new_rows, which divides -
+    so the divisor is handed over as a tensor on the colours' own device."""
+    return (rgb - 0.5) / torch.full((), SH_C0, dtype=rgb.dtype, device=rgb.device)
+
+
+def unit_normals(n):
+    """n / (|n| + 1e-8) (gaussian_pointcloud.py:315-318).  torch.norm rounds its sum of three squares differently from device to
+    device - one ulp of the unit normal on about 8 % of a frame's points - and on a wall that faces the camera (|n_z| -> 1) the
+    rotation's angle acos(n_z) turns that ulp into up to 1e-5 of the quaternion.  So ON THE DEVICE |n| is spelled out as
+    sqrt((x x + y y) + z z), one rounding per operation: what rtgs_gather_new_points evaluates, so that a pass of three points
+    and the tensor form of the add start from the very normals the kernel's passes do.  On the CPU (test doubles only) it stays
+    torch.norm, the call the reference's own CPU run made: its recorded states are sensitive to that ulp."""
+    if not n.is_cuda:
+        return n / (torch.norm(n, p=2, dim=-1, keepdim=True) + 1e-8)
+    x, y, z = n[..., 0:1], n[..., 1:2], n[..., 2:3]
+    return n / (torch.sqrt((x * x + y * y) + z * z) + 1e-8)
 
 
 def inverse_sigmoid(x):
@@ -546,7 +562,7 @@ class Mapping:
         # normals and rotations PER sampling pass, as add_empty_points is called (mapper.py:754, 794)
         normals, rot_parts = [], []
         for p in parts:
-            nrm = p[1] / (torch.norm(p[1], p=2, dim=-1, keepdim=True) + 1e-8)
+            nrm = unit_normals(p[1])
             normals.append(nrm)
             if same:
                 r = torch.zeros(nrm.shape[0], 4, device=nrm.device)
