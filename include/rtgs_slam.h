@@ -785,6 +785,43 @@ int rtgs_white_balance_apply(const float* color_chw, int32_t H, int32_t W, const
 int rtgs_map_deform(float* xyz, float* raw8, const void* tick, int32_t tick_kind, int64_t N, const float* table,
                     int32_t n_frames, void* stream);
 
+/* ---- loop closure: place recognition by appearance (no counterpart in the reference, whose ORB back end recognises places by a
+ * trained vocabulary; csrc/place.hip).  tests/place_reference.py is the definition, in numpy; both kernels match it bit for bit.
+ * Every float64 sum is taken in THE WAVE ORDER over a flat list v[0 .. n - 1]: lane l of 64 adds v[l], v[l + 64], ... in that
+ * order onto +0.0, then six butterfly steps o = 32, 16, .. 1 replace each lane's value by its own plus that of lane l ^ o
+ * (the tree t[:o] = t[:o] + t[o:2o]); a missing or gated-out element counts as +0.0.
+ *
+ * rtgs_place_describe.  One keyframe: color_chw [3][H][W] and depth [H][W] float32 -> one row of tw th cells, row by row, of each
+ *   of the caller's descriptor arrays.  Cell (i, j) covers rows floor(i H / th) .. floor((i + 1) H / th) - 1 and columns
+ *   floor(j W / tw) .. floor((j + 1) W / tw) - 1, n pixels; its flat list runs over them row by row.
+ *     intensity = (float)(sum(grey) / n), grey = (0.299f r + 0.587f g) + 0.114f b in float32, not contracted
+ *     depth     = (float)(sum(z over z > 0) / count(z > 0)), 0 without such a pixel
+ *     valid     = (float)((double)count / (double)n); a cell is depth-valid when valid >= 0.5f
+ *   One wave per cell.  Returns 0, -1 without a launch (null pointer, H or W < 1, H W >= 2^31, tw or th < 1, tw > W, th > H,
+ *   tw th > RTGS_PLACE_MAX_CELLS), -2 on a launch failure.
+ *
+ * rtgs_place_scores.  intensity, depth, valid [M][th tw] float32; score, depth_rel float32 and shift int32 [M][M], indexed
+ *   [b][a]: row b holds keyframe b against every older keyframe a.  Rows b_begin <= b < b_end are written in full, no other
+ *   row is touched: for a <= b - min_gap the pair's figures, for every other a the sentinels -2, 0, +inf.
+ *   A pair at the shift s, |s| <= S: column x of a against column x + s of b, x0 = max(0, -s) <= x < x0 + ow, ow = tw - |s|,
+ *   all rows; the flat list runs over the overlap row by row, n = th ow cells.  A, B the grey cells as float64:
+ *     SA, SB, SAA, SBB, SAB = sums of A, B, A A, B B, A B       ma = SA / n, mb = SB / n
+ *     va = SAA / n - ma ma, vb = SBB / n - mb mb, cov = SAB / n - ma mb       (float64, not contracted)
+ *     zncc = -1 if va <= 1e-12 or vb <= 1e-12, else cov / sqrt(va vb)
+ *   The shifts are visited as 0, -1, +1, -2, +2, ..; a later one wins only if strictly greater.  score = (float)best.  At that
+ *   shift, over the same list and the cells depth-valid in both: depth_rel = (float)(sum|da - db| / (0.5 sum(da + db))), +inf
+ *   when 4 count < n.  One wave per pair; both grey thumbnails are read once, into LDS, for all shifts.
+ *   Returns 0 (also, without a launch, for b_begin == b_end), -1 without a launch (null pointer, M < 1 or above
+ *   RTGS_PLACE_MAX_KEYFRAMES, tw or th < 1, tw th > RTGS_PLACE_MAX_CELLS, S < 0, 2 S >= tw, min_gap < 1, b_begin < 0,
+ *   b_begin > b_end, b_end > M), -2 on a launch failure.
+ * No atomics, no host read, two runs are bit-equal.  No alignment beyond float's is required. */
+#define RTGS_PLACE_MAX_CELLS 2048
+#define RTGS_PLACE_MAX_KEYFRAMES 16384
+int rtgs_place_describe(const float* color_chw, const float* depth, int32_t H, int32_t W, int32_t tw, int32_t th,
+                        float* intensity_out, float* depth_out, float* valid_out, void* stream);
+int rtgs_place_scores(const float* intensity, const float* depth, const float* valid, int32_t M, int32_t tw, int32_t th, int32_t S,
+                      int32_t min_gap, int32_t b_begin, int32_t b_end, float* score, int32_t* shift, float* depth_rel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

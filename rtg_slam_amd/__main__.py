@@ -53,6 +53,12 @@ optimisation (rtg_slam_amd.loop_closure): keyframe pairs whose estimated poses l
 the accepted ones join a keyframe pose graph, and the trajectory, the keyframes and the map's Gaussians move with the optimum.
 save_traj/pose_es.npy is then the corrected trajectory, save_traj/pose_es_before_loop_closure.npy the tracked one, and
 run_report.json gains `loop_closure`; the keys go into config.yaml only when given.  Not with use_gt_pose.
+`--loop-closure-candidates appearance` (or `both`) finds the pairs by what the keyframes look like instead of (or besides) where
+the trajectory puts them (rtg_slam_amd.place_recognition: thumbnails compared by ZNCC over a horizontal shift, depth thumbnails
+as a second witness), so that a loop whose drift exceeds --loop-closure-max-trans is still found; --loop-closure-thumb-width,
+--loop-closure-max-shift, --loop-closure-min-score and --loop-closure-max-depth-rel set it up.  All five need --loop-closure,
+are written only when given, and the report's candidates gain `source` (and `score`, `shift`, `depth_rel`) and the report
+`appearance` only then.
 `metric --exposure-aware` also scores every render in the frame's own exposure and white balance (an affine correction per
 channel, fitted on the device): eval_metric/exposure_frame_F_iter_I.csv and exposure_report.json, nothing else changes.
 
@@ -155,7 +161,14 @@ LOOP_CLOSURE_FLAGS = (("min_gap", int, "N", "keyframes between the two ends of a
                       ("max_correction_trans", float, "M", "metres a registration may move the estimate (default 0.2)"),
                       ("max_correction_rot_deg", float, "DEG", "degrees a registration may turn it (default 5)"),
                       ("odometry_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the odometry edges (default 1 1)"),
-                      ("loop_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the loop edges (default 1 1)"))
+                      ("loop_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the loop edges (default 1 1)"),
+                      ("candidates", str, None, "where the candidate pairs come from: the estimated poses (default), the "
+                                                "keyframes' thumbnails (rtg_slam_amd.place_recognition), or both"),
+                      ("thumb_width", int, "N", "columns of a keyframe's thumbnail (default 40)"),
+                      ("max_shift", int, "N", "thumbnail columns searched to either side, the yaw of the first guess (default 4)"),
+                      ("min_score", float, "R", "ZNCC two thumbnails need at their best shift (default 0.9)"),
+                      ("max_depth_rel", float, "R", "relative difference their depth thumbnails may have (default 0.1)"))
+LOOP_CLOSURE_CHOICES = {"candidates": ("pose", "appearance", "both")}
 
 
 def _apply_loop_closure(args, opts) -> str | None:
@@ -803,6 +816,8 @@ def build_parser() -> argparse.ArgumentParser:
     for name, typ, meta, text in LOOP_CLOSURE_FLAGS:
         if isinstance(typ, tuple):
             s.add_argument("--loop-closure-" + name.replace("_", "-"), type=float, nargs=2, default=None, metavar=meta, help=text)
+        elif name in LOOP_CLOSURE_CHOICES:
+            s.add_argument("--loop-closure-" + name.replace("_", "-"), choices=LOOP_CLOSURE_CHOICES[name], default=None, help=text)
         else:
             s.add_argument("--loop-closure-" + name.replace("_", "-"), type=typ, default=None, metavar=meta, help=text)
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")

@@ -1,15 +1,23 @@
 """Loop closure at the end of a run: keyframe pose graph, corrected trajectory, deformed map ("Loop closure").
 
     find_candidates     keyframe pairs far apart in time whose ESTIMATED poses lie close (host, deterministic)
+    (place_recognition) keyframe pairs far apart in time that LOOK alike, whatever the poses say (loop_closure_candidates)
     register_pair       one candidate through rgbd_align.RgbdRefiner.refine from the estimated relative pose -> an edge or a refusal
     frame_corrections   the keyframes' corrections T'_k T_k^-1 spread over all frames along SE(3) geodesics
     deform_table        those corrections as the float32 table of rtgs_map_deform (include/rtgs_slam.h)
     LoopCloser.close    candidates -> edges -> pose_graph.optimize -> trajectory, keyframes and map moved
 
 The option (`loop_closure: True`) is off by default and runs once, after the last frame and before the final global optimisation
-(slam.run_sequence).  Candidates come from the estimated poses alone - there is no place recognition - so a loop whose drift exceeds
-loop_closure_max_trans is not found.  The defaults below are derived from the ICP's gates (icp_distance_threshold 0.1 m,
-icp_normal_threshold 20 degrees) and the drift the README quotes (5 cm over 2 000 frames); none has been measured on real data."""
+(slam.run_sequence).  By default (loop_closure_candidates "pose") candidates come from the estimated poses alone, so a loop whose
+drift exceeds loop_closure_max_trans is not found.  "appearance" takes them from the keyframes' thumbnails instead
+(place_recognition.py: ZNCC of grey thumbnails over a horizontal shift, depth thumbnails as a second witness) and starts each
+registration from the shift's yaw alone, so neither trusts the trajectory; "both" registers the pose candidates first and then
+the appearance pairs not among them, each source with its own loop_closure_max_per_keyframe.  register_pair and its gates are
+the same for both: max_correction_* then bounds the correction measured from the appearance guess, so a revisit must lie
+within 0.2 m and about 5 degrees plus the shift's yaw of the earlier view.  Two places that look and measure alike pass both
+witnesses; only those gates and loop_closure_huber stand against such an edge.  The defaults below are derived from the ICP's
+gates (icp_distance_threshold 0.1 m, icp_normal_threshold 20 degrees) and the drift the README quotes (5 cm over 2 000 frames),
+the appearance thresholds chosen on the synthetic box room; none has been measured on real data."""
 from __future__ import annotations
 
 import time
@@ -34,7 +42,15 @@ DEFAULTS = {
     "loop_closure_odometry_weights": (1.0, 1.0),   # (per rad^2, per m^2)
     "loop_closure_loop_weights": (1.0, 1.0),
     "loop_closure_huber": None,                    # weighted residual norm beyond which a loop edge pulls linearly; None = off
+    # where the candidates come from: "pose" (find_candidates), "appearance" (place_recognition) or "both".  The four values
+    # below are read only when it is not "pose"; 40 / 0.9 / 0.1 were chosen on the synthetic box room, not measured on real data
+    "loop_closure_candidates": "pose",
+    "loop_closure_thumb_width": 40,                # thumbnail columns; the rows follow the image's aspect
+    "loop_closure_max_shift": 4,                   # columns searched to either side: 4 of 40 at a 90-degree view are about 11 degrees
+    "loop_closure_min_score": 0.9,                 # ZNCC of the grey thumbnails at the best shift
+    "loop_closure_max_depth_rel": 0.1,             # mean |depth difference| over the mean depth of the two thumbnails
 }
+CANDIDATE_SOURCES = ("pose", "appearance", "both")
 
 
 def _angle_deg(R) -> float:
@@ -200,6 +216,21 @@ class LoopCloser:
             raise ValueError("loop_closure_min_inlier_ratio must lie in [0, 1]")
         if cfg.huber is not None and not cfg.huber > 0:
             raise ValueError("loop_closure_huber must be positive")
+        # kept apart from cfg: the report's "options" are cfg's, key for key what they were before there was a choice
+        self.place = pl = SimpleNamespace(
+            candidates=str(get("loop_closure_candidates")), thumb_width=int(get("loop_closure_thumb_width")),
+            max_shift=int(get("loop_closure_max_shift")), min_score=float(get("loop_closure_min_score")),
+            max_depth_rel=float(get("loop_closure_max_depth_rel")))
+        if pl.candidates not in CANDIDATE_SOURCES:
+            raise ValueError(f"loop_closure_candidates must be one of {', '.join(CANDIDATE_SOURCES)}")
+        if pl.thumb_width < 1:
+            raise ValueError("loop_closure_thumb_width must be >= 1")
+        if pl.max_shift < 0 or 2 * pl.max_shift >= pl.thumb_width:
+            raise ValueError("loop_closure_max_shift must not be negative and twice it must stay below loop_closure_thumb_width")
+        if not -1 <= pl.min_score <= 1:
+            raise ValueError("loop_closure_min_score must lie in [-1, 1]")
+        if not pl.max_depth_rel >= 0:
+            raise ValueError("loop_closure_max_depth_rel must not be negative")
         from .rgbd_align import RgbdRefiner
         exposure = bool(getattr(args, "rgbd_refine_exposure", False)) or bool(getattr(args, "map_exposure", False))
         ref_args = SimpleNamespace(**{k: v for k, v in vars(args).items() if k.startswith(("rgbd_refine_", "icp_"))})
@@ -220,6 +251,34 @@ class LoopCloser:
             cache[key] = hit
         return hit
 
+    def _appearance_candidates(self, mapper, old, taken, rep) -> List[Tuple]:
+        """The pairs of place_recognition that are not in `taken`, as (a, b, metres, degrees between the ESTIMATED poses, {"init",
+        "score", "shift", "depth_rel"}); init is appearance_init, which does not look at the poses.  Fills rep["appearance"]."""
+        from . import place_recognition as pr
+        cfg, pl, dev = self.cfg, self.place, mapper.device
+        t0 = time.perf_counter()
+        desc = pr.describe_all(mapper.keymap_list, pl.thumb_width)
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        score, shift, rel = pr.score_pairs(desc, cfg.min_gap, pl.max_shift)
+        found = pr.find_appearance_candidates(score, shift, rel, cfg.min_gap, pl.min_score, pl.max_depth_rel, cfg.max_per_keyframe)
+        t2 = time.perf_counter()
+        M, th, tw = (int(x) for x in desc["intensity"].shape)
+        W, fx = int(mapper.keymap_list[0]["color_chw"].shape[-1]), float(mapper.keyframe_list[0].fx)
+        out = []
+        for a, b, sc, sh, dr in found:
+            if (a, b) in taken:
+                continue
+            rel_pose = pose_graph.inverse(old[a]) @ old[b]
+            out.append((a, b, float(np.linalg.norm(old[a][:3, 3] - old[b][:3, 3])), _angle_deg(rel_pose[:3, :3]),
+                        {"init": pr.appearance_init(sh, fx, W, tw), "score": sc, "shift": sh, "depth_rel": dr}))
+        rep["appearance"] = {"mode": pl.candidates, "thumbnail": [tw, th], "max_shift": pl.max_shift, "min_score": pl.min_score,
+                             "max_depth_rel": pl.max_depth_rel,
+                             "pairs_scored": sum(max(0, b - cfg.min_gap + 1) for b in range(M)),
+                             "candidates": len(found), "candidates_new": len(out)}
+        rep["seconds"].update(describe=t1 - t0, scores=t2 - t1)
+        return out
+
     def close(self, mapper, tracker) -> Dict:
         """-> the report (JSON-able).  Without an accepted edge nothing is changed: poses, keyframes and map stay bit-identical."""
         from . import slam_ops
@@ -238,16 +297,25 @@ class LoopCloser:
             raise RuntimeError("loop closure: the keyframes, the trajectory and the map's ticks do not belong to one run")
         gt = tracker.pose_gt if len(tracker.pose_gt) == n else None
         old = [np.array(tracker.pose_es[i], dtype=np.float64) for i in ids]
-        cands = find_candidates(old, ids, cfg.min_gap, cfg.max_trans, cfg.max_rot_deg, cfg.max_per_keyframe)
+        mode = self.place.candidates
+        cands = [] if mode == "appearance" else [
+            (a, b, dist, ang, None) for a, b, dist, ang in
+            find_candidates(old, ids, cfg.min_gap, cfg.max_trans, cfg.max_rot_deg, cfg.max_per_keyframe)]
+        if mode != "pose":
+            cands += self._appearance_candidates(mapper, old, {(a, b) for a, b, *_ in cands}, rep)
         t1 = time.perf_counter()
         K = mapper.keyframe_list[0].K
         cache, loop_edges = {}, []
-        for a, b, dist, ang in cands:
-            init = pose_graph.inverse(old[a]) @ old[b]
+        for a, b, dist, ang, seen in cands:
+            init = pose_graph.inverse(old[a]) @ old[b] if seen is None else seen.pop("init")
             r = register_pair(self.refiner, self._pyramids(mapper.keymap_list[b], K, cache, b),
                               self._pyramids(mapper.keymap_list[a], K, cache, a), init, K, self.downscales, cfg)
             Z = r.pop("Z")
             r.update(a=a, b=b, frame_a=ids[a], frame_b=ids[b], distance_m=dist, angle_deg=ang)
+            if mode != "pose":
+                r["source"] = "pose" if seen is None else "appearance"
+                r.update(seen or {})
+                r["Z"] = np.asarray(Z).tolist()                               # the measured T_a^-1 T_b, whatever became of it
             rep["candidates"].append(r)
             if r["accepted"]:
                 loop_edges.append((a, b, Z, cfg.loop_weights[0], cfg.loop_weights[1], True))
