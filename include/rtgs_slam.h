@@ -822,6 +822,51 @@ int rtgs_place_describe(const float* color_chw, const float* depth, int32_t H, i
 int rtgs_place_scores(const float* intensity, const float* depth, const float* valid, int32_t M, int32_t tw, int32_t th, int32_t S,
                       int32_t min_gap, int32_t b_begin, int32_t b_end, float* score, int32_t* shift, float* depth_rel, void* stream);
 
+/* ---- loop closure: a relative pose for a wide-baseline revisit from matched keypoints (the reference gets it from its ORB back
+ * end, use_orb_backend; csrc/keypoints.hip).  tests/keypoint_reference.py is the definition, in numpy; after the grey value
+ * everything is integer arithmetic and the three kernels match it bit for bit.
+ *
+ * rtgs_keypoint_detect.  One keyframe: color_chw [3][H][W] and depth [H][W] float32 ->
+ *     g8    [H][W] uint8:  clamp(floor(grey 255 + 0.5), 0, 255), grey = (0.299f r + 0.587f g) + 0.114f b in float32, not contracted;
+ *     box5  [H][W] int32:  the 5 x 5 sum of g8 around the pixel, pixels outside the image counting as 0;
+ *     slots [ceil(H / cell) ceil(W / cell)][4] int32, cells row by row: x, y, score of the cell's keypoint and -1; 0, 0, 0, -1
+ *           for a cell without one.
+ *   score is the FAST-9 score on the circle of radius 3 (the largest threshold at which the pixel is still a corner); a pixel is
+ *   eligible when score > threshold, RTGS_KEYPOINT_MARGIN <= x < W - RTGS_KEYPOINT_MARGIN, the same for y, and its depth is
+ *   finite and > 0, and counts as 0 otherwise; it survives the 3 x 3 suppression when its score is strictly greater than those
+ *   of the four neighbours earlier in raster order and at least those of the four later; a cell keeps the survivor of the
+ *   highest score, on a tie the one with the lowest row-major pixel index.  One block per cell.
+ *   Returns 0, -1 without a launch (null pointer, H or W < 1, H W >= 2^31, cell outside RTGS_KEYPOINT_MIN_CELL ..
+ *   RTGS_KEYPOINT_MAX_CELL, threshold outside 0 .. 255, more than 65535 rows of cells), -2 on a launch failure.
+ *
+ * rtgs_keypoint_describe.  g8, box5 and slots of rtgs_keypoint_detect (n_slots of them) -> slots[.][3] = the orientation bin and
+ *   desc [n_slots][8] uint32; -1 and zeros for an empty slot.  m10 = sum dx g8, m01 = sum dy g8 over dx^2 + dy^2 <= 169;
+ *   bin = argmax_k (dirs[k][0] m10 + dirs[k][1] m01) over k = 0 .. 31 in int64, ties to the lowest k; bin 0 when oriented == 0.
+ *   Bit i of the descriptor (word i / 32, position i % 32) is box5(keypoint + P1) < box5(keypoint + P2) with
+ *   tables[bin][i] = the four int8 x1, y1, x2, y2 packed into one word, lowest byte first.  dirs [32][2] int32 and tables
+ *   [32][256] uint32 are device buffers the host builds once (rtg_slam_amd/keypoints.py), so that the kernel and the definition
+ *   read the same numbers.  One wave per slot.
+ *   Returns 0 (also, without a launch, for n_slots == 0), -1 (null pointer, H or W < 1, H W >= 2^31, n_slots < 0), -2.
+ *
+ * rtgs_keypoint_match.  desc [n_desc][8] uint32, 16-byte aligned, holds the descriptors of all keyframes; pairs [n_pairs][5] int32
+ *   (device) = first query row, query count, first reference row, reference count, first row of `out`; out [n_out][3] int32.
+ *   For query q of a pair, out[first + q] = the reference index (within its set) of the least Hamming distance, ties to the
+ *   lowest index; that distance; the least distance over all other indices of the set, 257 when there is none.  An empty
+ *   reference set gives -1, 257, 257.  max_queries is the largest query count (it sizes the grid); a pair whose rows do not lie
+ *   inside the buffers is skipped.  One launch for the whole batch, one wave per query.
+ *   Returns 0 (also, without a launch, for n_pairs == 0 or max_queries == 0), -1 (null or misaligned pointer, a negative count,
+ *   n_pairs > 65535, n_desc or n_out >= 2^31), -2.
+ * No atomics, no host read, two runs are bit-equal. */
+#define RTGS_KEYPOINT_MARGIN 16
+#define RTGS_KEYPOINT_MIN_CELL 8
+#define RTGS_KEYPOINT_MAX_CELL 32
+int rtgs_keypoint_detect(const float* color_chw, const float* depth, int32_t H, int32_t W, int32_t cell, int32_t threshold,
+                         uint8_t* g8, int32_t* box5, int32_t* slots, void* stream);
+int rtgs_keypoint_describe(const uint8_t* g8, const int32_t* box5, int32_t H, int32_t W, int32_t n_slots, int32_t oriented,
+                           const int32_t* dirs, const uint32_t* tables, int32_t* slots, uint32_t* desc, void* stream);
+int rtgs_keypoint_match(const uint32_t* desc, int64_t n_desc, const int32_t* pairs, int32_t n_pairs, int32_t max_queries,
+                        int32_t* out, int64_t n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

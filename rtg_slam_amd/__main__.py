@@ -59,6 +59,13 @@ as a second witness), so that a loop whose drift exceeds --loop-closure-max-tran
 --loop-closure-max-shift, --loop-closure-min-score and --loop-closure-max-depth-rel set it up.  All five need --loop-closure,
 are written only when given, and the report's candidates gain `source` (and `score`, `shift`, `depth_rel`) and the report
 `appearance` only then.
+`--loop-closure-appearance-init keypoints` (with candidates appearance or both) starts each appearance candidate's registration
+from a relative pose computed from the two keyframes alone (rtg_slam_amd.keypoints: FAST-9 corners, 256-bit descriptors, a
+brute-force Hamming match on the device, a 3-D - 3-D RANSAC over the matches' depth on the host) wherever that pose has
+--loop-closure-keypoint-min-inliers inliers, and from the thumbnail shift's yaw otherwise, so that a revisit from 0.5 m and 12
+degrees away registers; `keypoints_strict` refuses the candidate instead of falling back.  The --loop-closure-keypoint-* values
+set it up; the candidates then gain `init_source`, `init` and `keypoints`, the report's `seconds` the three keypoints_* stages.
+Single scale, pixel-centre corners, thresholds chosen on a synthetic room.
 `metric --exposure-aware` also scores every render in the frame's own exposure and white balance (an affine correction per
 channel, fitted on the device): eval_metric/exposure_frame_F_iter_I.csv and exposure_report.json, nothing else changes.
 
@@ -167,8 +174,20 @@ LOOP_CLOSURE_FLAGS = (("min_gap", int, "N", "keyframes between the two ends of a
                       ("thumb_width", int, "N", "columns of a keyframe's thumbnail (default 40)"),
                       ("max_shift", int, "N", "thumbnail columns searched to either side, the yaw of the first guess (default 4)"),
                       ("min_score", float, "R", "ZNCC two thumbnails need at their best shift (default 0.9)"),
-                      ("max_depth_rel", float, "R", "relative difference their depth thumbnails may have (default 0.1)"))
-LOOP_CLOSURE_CHOICES = {"candidates": ("pose", "appearance", "both")}
+                      ("max_depth_rel", float, "R", "relative difference their depth thumbnails may have (default 0.1)"),
+                      ("appearance_init", str, None, "first guess of an appearance candidate: the thumbnail shift's yaw (default), "
+                                                     "the pose from matched keypoints where it has its inliers "
+                                                     "(rtg_slam_amd.keypoints), or that pose or no registration at all"),
+                      ("keypoint_threshold", int, "N", "FAST-9 score a corner must exceed, of 255 grey levels (default 20)"),
+                      ("keypoint_cell", int, "N", "pixels: one keypoint per N x N cell, 8 .. 32 (default 16)"),
+                      ("keypoint_oriented", str, None, "turn the descriptor with the patch's intensity centroid (default true)"),
+                      ("keypoint_max_hamming", int, "N", "bits of 256 two matched descriptors may differ in (default 64)"),
+                      ("keypoint_ratio", float, "R", "best distance <= R x second best (default 0.8)"),
+                      ("keypoint_ransac_iters", int, "N", "triplets drawn (default 512)"),
+                      ("keypoint_inlier_dist", float, "M", "metres a match may miss the hypothesis by (default 0.05)"),
+                      ("keypoint_min_inliers", int, "N", "inliers the keypoint pose needs to be used (default 8)"))
+LOOP_CLOSURE_CHOICES = {"candidates": ("pose", "appearance", "both"), "appearance_init": ("yaw", "keypoints", "keypoints_strict"),
+                        "keypoint_oriented": ("true", "false")}
 
 
 def _apply_loop_closure(args, opts) -> str | None:
@@ -182,6 +201,8 @@ def _apply_loop_closure(args, opts) -> str | None:
             continue
         if not getattr(args, "loop_closure", False):
             return f"--loop-closure-{name.replace('_', '-')} needs --loop-closure (or loop_closure: true in the config)"
+        if name == "keypoint_oriented":
+            value = value == "true"
         setattr(args, "loop_closure_" + name, list(value) if isinstance(value, (list, tuple)) else value)
     if not getattr(args, "loop_closure", False):
         return None

@@ -1,0 +1,291 @@
+"""A relative pose for a candidate pair of keyframes from the two frames alone (csrc/keypoints.hip; the definition is
+tests/keypoint_reference.py): what the reference gets from its ORB back end, in its smallest sound form.
+
+    detect_and_describe   a keyframe's colour and depth -> its keypoints (rtgs_keypoint_detect, rtgs_keypoint_describe)
+    match_pairs           a batch of (query keyframe, reference keyframe) pairs in ONE launch (rtgs_keypoint_match)
+    filter_matches        mutual best, Hamming bound, ratio test (host)
+    ransac_rigid          3-D - 3-D RANSAC over the matches' back-projected points (host, numpy float64, deterministic)
+    relative_pose         the four together for one pair -> T = T_a^-1 T_b with its count of geometric witnesses, or a refusal
+
+FAST-9 corners on the 8-bit grey image, one per cell of the image, oriented by the intensity centroid in 32 bins, described by
+256 comparisons of 5 x 5 box sums.  Single scale, pixel-centre localisation, no vocabulary.  After the grey value everything on
+the device is integer arithmetic, so the kernels match the definition bit for bit.  There is no fallback: a CPU tensor or a
+missing kernel is an error."""
+from __future__ import annotations
+
+from types import SimpleNamespace
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .keypoint_pattern import PATTERN
+
+MARGIN = _lib.CONSTANTS["RTGS_KEYPOINT_MARGIN"]
+MIN_CELL, MAX_CELL = _lib.CONSTANTS["RTGS_KEYPOINT_MIN_CELL"], _lib.CONSTANTS["RTGS_KEYPOINT_MAX_CELL"]
+BINS = 32
+# the loop closure's loop_closure_keypoint_* keys (loop_closure.DEFAULTS takes them from here); chosen on the synthetic textured
+# box room, none measured on real data
+DEFAULTS = {
+    "threshold": 20,            # FAST-9 score a corner must exceed: an absolute contrast of the 8-bit grey image
+    "cell": 16,                 # pixels: one keypoint per cell x cell pixels
+    "oriented": True,           # False: bin 0 for every keypoint (no in-plane rotation between the views)
+    "max_hamming": 64,          # of 256 bits
+    "ratio": 0.8,               # best distance <= ratio x second best
+    "ransac_iters": 512,
+    "inlier_dist": 0.05,        # metres: half of icp_distance_threshold - the dense registration only needs to start inside its gates
+    "min_inliers": 8,           # three define the hypothesis; wrong pairs of the textured room end with at most 2, right ones with 18+
+}
+
+
+def config(**over) -> SimpleNamespace:
+    """The keypoint options as a namespace, validated.  Raises ValueError."""
+    unknown = set(over) - set(DEFAULTS)
+    if unknown:
+        raise ValueError(f"keypoints: unknown option {sorted(unknown)[0]}")
+    v = dict(DEFAULTS, **over)
+    cfg = SimpleNamespace(threshold=int(v["threshold"]), cell=int(v["cell"]), oriented=bool(v["oriented"]), max_hamming=int(v["max_hamming"]),
+                          ratio=float(v["ratio"]), ransac_iters=int(v["ransac_iters"]), inlier_dist=float(v["inlier_dist"]),
+                          min_inliers=int(v["min_inliers"]))
+    if not 0 <= cfg.threshold <= 255:
+        raise ValueError("loop_closure_keypoint_threshold must lie in 0 .. 255")
+    if not MIN_CELL <= cfg.cell <= MAX_CELL:
+        raise ValueError(f"loop_closure_keypoint_cell must lie in {MIN_CELL} .. {MAX_CELL}")
+    if not 0 <= cfg.max_hamming <= 256:
+        raise ValueError("loop_closure_keypoint_max_hamming must lie in 0 .. 256")
+    if not 0 < cfg.ratio <= 1:
+        raise ValueError("loop_closure_keypoint_ratio must lie in (0, 1]")
+    if cfg.ransac_iters < 1:
+        raise ValueError("loop_closure_keypoint_ransac_iters must be >= 1")
+    if not cfg.inlier_dist > 0:
+        raise ValueError("loop_closure_keypoint_inlier_dist must be positive")
+    if cfg.min_inliers < 3:
+        raise ValueError("loop_closure_keypoint_min_inliers must be >= 3: three pairs define the pose")
+    return cfg
+
+
+def direction_table() -> np.ndarray:
+    """[32, 2] int32: rint(16384 (cos, sin)(2 pi k / 32))."""
+    a = 2.0 * np.pi * np.arange(BINS) / BINS
+    return np.rint(16384.0 * np.stack([np.cos(a), np.sin(a)], axis=1)).astype(np.int32)
+
+
+def rotated_patterns() -> np.ndarray:
+    """[32, 256, 4] int8: PATTERN turned into every bin, rint(R_k p) in float64."""
+    p = np.asarray(PATTERN, dtype=np.float64).reshape(256, 2, 2)
+    out = np.empty((BINS, 256, 4), dtype=np.int8)
+    for k in range(BINS):
+        c, s = np.cos(2.0 * np.pi * k / BINS), np.sin(2.0 * np.pi * k / BINS)
+        out[k, :, 0::2] = np.rint(c * p[..., 0] - s * p[..., 1])
+        out[k, :, 1::2] = np.rint(s * p[..., 0] + c * p[..., 1])
+    return out
+
+
+_tables: Dict = {}
+
+
+def _device_tables(dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dirs [32, 2] int32, tables [32, 256] int32 - the four int8 of a pair packed, lowest byte first) on `dev`, built once."""
+    key = (dev.type, dev.index)
+    if key not in _tables:
+        packed = np.ascontiguousarray(rotated_patterns()).view("<i4").reshape(BINS, 256)
+        _tables[key] = (torch.from_numpy(direction_table()).to(dev), torch.from_numpy(packed.astype(np.int32)).to(dev))
+    return _tables[key]
+
+
+def _check_image(color_chw, depth_chw):
+    if not (torch.is_tensor(color_chw) and color_chw.is_cuda and color_chw.dtype == torch.float32 and color_chw.dim() == 3
+            and color_chw.shape[0] == 3):
+        raise ValueError("keypoints: colour must be a float32 [3, H, W] tensor on the device")
+    H, W = int(color_chw.shape[1]), int(color_chw.shape[2])
+    if not (torch.is_tensor(depth_chw) and depth_chw.device == color_chw.device and depth_chw.dtype == torch.float32
+            and depth_chw.numel() == H * W):
+        raise ValueError("keypoints: depth must be a float32 [1, H, W] tensor on the colour's device")
+    return H, W
+
+
+def detect_and_describe(color_chw: torch.Tensor, depth_chw: torch.Tensor, K, cfg=None, keep_planes: bool = False) -> Dict:
+    """-> {"x", "y", "score", "bin": int32 numpy [N]; "desc": int32 [N, 8] on the device (the uint32 words' bits); "xyz": float64
+    numpy [N, 3], the pixels back-projected with the depth and K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]}, the keypoints in slot
+    order.  With keep_planes also "g8" (uint8 [H, W]), "box5" (int32 [H, W]), "slots" (int32 [cells, 4]) and "slot_desc" (int32
+    [cells, 8]) on the device, as the kernels left them.  Two launches and one small copy to the host (the slots)."""
+    cfg = config() if cfg is None else cfg
+    H, W = _check_image(color_chw, depth_chw)
+    dev = color_chw.device
+    c = int(cfg.cell)
+    n_slots = (-(-W // c)) * (-(-H // c))
+    color_chw, depth_chw = color_chw.contiguous(), depth_chw.contiguous()
+    g8 = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    box = torch.empty((H, W), dtype=torch.int32, device=dev)
+    slots = torch.empty((n_slots, 4), dtype=torch.int32, device=dev)
+    slot_desc = torch.empty((n_slots, 8), dtype=torch.int32, device=dev)
+    dirs, tables = _device_tables(dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_keypoint_detect(_lib.ptr(color_chw), _lib.ptr(depth_chw), H, W, c, int(cfg.threshold), _lib.ptr(g8), _lib.ptr(box),
+                                      _lib.ptr(slots), _lib.stream(dev))
+        _lib.check(rc, "rtgs_keypoint_detect")
+        rc = lib.rtgs_keypoint_describe(_lib.ptr(g8), _lib.ptr(box), H, W, n_slots, int(bool(cfg.oriented)), _lib.ptr(dirs),
+                                        _lib.ptr(tables), _lib.ptr(slots), _lib.ptr(slot_desc), _lib.stream(dev))
+        _lib.check(rc, "rtgs_keypoint_describe")
+    live = torch.nonzero(slots[:, 2] > 0).reshape(-1)
+    kp = slots[live]
+    z = depth_chw.reshape(H, W)[kp[:, 1].long(), kp[:, 0].long()]
+    host = torch.cat([kp.to(torch.float64), z.to(torch.float64)[:, None]], dim=1).cpu().numpy()      # the one copy
+    Kn = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
+    x, y, zz = host[:, 0], host[:, 1], host[:, 4]
+    out = {"x": host[:, 0].astype(np.int32), "y": host[:, 1].astype(np.int32), "score": host[:, 2].astype(np.int32),
+           "bin": host[:, 3].astype(np.int32), "desc": slot_desc[live].contiguous(),
+           "xyz": np.stack([(x - Kn[0, 2]) / Kn[0, 0] * zz, (y - Kn[1, 2]) / Kn[1, 1] * zz, zz], axis=1)}
+    if keep_planes:
+        out.update(g8=g8, box5=box, slots=slots, slot_desc=slot_desc)
+    return out
+
+
+def match_pairs(features, pairs: Sequence[Tuple]) -> List[np.ndarray]:
+    """features: keyframe key -> {"desc": int32 [N, 8] on the device} (a dict, or a list indexed by key); pairs: [(query key,
+    reference key)] -> per pair an int32 numpy [N_query, 3]: the reference's index, the distance, the second distance (-1, 257,
+    257 against an empty set).  One launch and one copy to the host for the whole batch."""
+    pairs = list(pairs)
+    if not pairs:
+        return []
+    keys = []
+    for q, r in pairs:
+        for k in (q, r):
+            if k not in keys:
+                keys.append(k)
+    descs = [features[k]["desc"] for k in keys]
+    for d in descs:
+        if not (torch.is_tensor(d) and d.is_cuda and d.dtype == torch.int32 and d.dim() == 2 and d.shape[1] == 8
+                and d.device == descs[0].device):
+            raise ValueError("match_pairs: every descriptor set must be an int32 [N, 8] tensor on one device")
+    dev = descs[0].device
+    begin, total = {}, 0
+    for k, d in zip(keys, descs):
+        begin[k] = total
+        total += int(d.shape[0])
+    table, n_out = [], 0
+    for q, r in pairs:
+        nq = int(features[q]["desc"].shape[0])
+        table.append((begin[q], nq, begin[r], int(features[r]["desc"].shape[0]), n_out))
+        n_out += nq
+    if n_out == 0:
+        return [np.empty((0, 3), dtype=np.int32) for _ in pairs]
+    if len(pairs) > 65535:
+        raise ValueError("match_pairs: at most 65535 pairs a launch")
+    all_desc = torch.cat(descs, dim=0).contiguous()
+    out = torch.empty((n_out, 3), dtype=torch.int32, device=dev)
+    tab = torch.tensor(table, dtype=torch.int32).to(dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_keypoint_match(_lib.ptr(all_desc), total, _lib.ptr(tab), len(pairs), max(t[1] for t in table), _lib.ptr(out), n_out,
+                                     _lib.stream(dev))
+    _lib.check(rc, "rtgs_keypoint_match")
+    host = out.cpu().numpy()
+    return [host[t[4]:t[4] + t[1]] for t in table]
+
+
+def filter_matches(m_ba, m_ab, max_hamming: int = 64, ratio: float = 0.8) -> List[Tuple[int, int, int]]:
+    """m_ba: b's keypoints matched against a's, m_ab the other way (rows of match_pairs) -> [(i in b, j in a, distance)] in
+    order of i: each the other's best, distance <= max_hamming and <= ratio x the second best on b's side."""
+    out = []
+    m_ab = np.asarray(m_ab)
+    for i, (j, d, second) in enumerate(np.asarray(m_ba).tolist()):
+        if j >= 0 and int(m_ab[j][0]) == i and d <= max_hamming and d <= float(ratio) * second:
+            out.append((i, int(j), int(d)))
+    return out
+
+
+def mix32(x: int) -> int:
+    """The counter-based generator of ransac_rigid: a 32-bit integer hash, no state."""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x
+
+
+def kabsch(pb, pa):
+    """R, t (float64) with pa ~ R pb + t in the least-squares sense."""
+    cb, ca = pb.mean(axis=0), pa.mean(axis=0)
+    U, _, Vt = np.linalg.svd((pa - ca).T @ (pb - cb))
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0])
+    R = U @ D @ Vt
+    return R, ca - R @ cb
+
+
+def _spread(p) -> bool:
+    e1, e2 = p[1] - p[0], p[2] - p[0]
+    n1, n2 = np.linalg.norm(e1), np.linalg.norm(e2)
+    return bool(n1 > 1e-9 and n2 > 1e-9 and np.linalg.norm(np.cross(e1, e2)) >= 0.1 * n1 * n2)
+
+
+def ransac_rigid(pa, pb, iters: int = 512, inlier_dist: float = 0.05, seed: int = 0):
+    """Matched 3-D points pa [n, 3] (in a's camera) and pb [n, 3] (in b's) -> (T 4 x 4 float64 with p_a = T p_b, that is
+    T_a^-1 T_b; the inliers' mask; the rms of their residuals) or None (fewer than 3 matches, no valid triplet).  Hypothesis h
+    draws the indices mix32(seed + 3 h + j) mod n, j = 0, 1, 2; a triplet with a repeated index, or whose angle at its first
+    point lies below 5.74 or above 174.26 degrees in either frame (|e1 x e2| < 0.1 |e1| |e2|), is skipped; the highest inlier
+    count wins, the earliest on a tie; then up to three rounds of refitting on the inliers, a round that loses inliers dropped."""
+    pa, pb = np.asarray(pa, dtype=np.float64).reshape(-1, 3), np.asarray(pb, dtype=np.float64).reshape(-1, 3)
+    n = pa.shape[0]
+    if n < 3 or pb.shape[0] != n:
+        return None
+    count = lambda R, t: np.linalg.norm(pb @ R.T + t - pa, axis=1) <= inlier_dist
+    best = None
+    for h in range(int(iters)):
+        idx = [mix32(int(seed) + 3 * h + j) % n for j in range(3)]
+        if len(set(idx)) < 3 or not _spread(pa[idx]) or not _spread(pb[idx]):
+            continue
+        R, t = kabsch(pb[idx], pa[idx])
+        mask = count(R, t)
+        if best is None or mask.sum() > best[2].sum():
+            best = (R, t, mask)
+    if best is None:
+        return None
+    R, t, mask = best
+    for _ in range(3):
+        if mask.sum() < 3:
+            break
+        R2, t2 = kabsch(pb[mask], pa[mask])
+        m2 = count(R2, t2)
+        if m2.sum() < mask.sum():
+            break
+        same = np.array_equal(m2, mask)
+        R, t, mask = R2, t2, m2
+        if same:
+            break
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    res = np.linalg.norm(pb[mask] @ R.T + t - pa[mask], axis=1)
+    return T, mask, float(np.sqrt(np.mean(res ** 2))) if mask.any() else 0.0
+
+
+def pose_from_matches(features_a: Dict, features_b: Dict, m_ba, m_ab, cfg) -> Dict:
+    """The host half of relative_pose, from the two match tables of match_pairs."""
+    out = {"T": None, "inliers": 0, "matches": 0, "rms": None, "keypoints_a": int(len(features_a["x"])),
+           "keypoints_b": int(len(features_b["x"])), "reason": None}
+    m = filter_matches(m_ba, m_ab, cfg.max_hamming, cfg.ratio)
+    out["matches"] = len(m)
+    fit = None
+    if len(m) >= 3:
+        fit = ransac_rigid(features_a["xyz"][[j for _, j, _ in m]], features_b["xyz"][[i for i, _, _ in m]], cfg.ransac_iters,
+                           cfg.inlier_dist)
+    if fit is not None:
+        out["inliers"], out["rms"] = int(fit[1].sum()), fit[2]
+    if out["inliers"] < cfg.min_inliers:                          # also: fewer than 3 matches, no valid triplet (0 inliers)
+        out["reason"] = f"{out['inliers']} inliers of {len(m)} matches, below {cfg.min_inliers}"
+        return out
+    out["T"] = fit[0]
+    return out
+
+
+def relative_pose(features_a: Dict, features_b: Dict, cfg=None) -> Dict:
+    """The two keyframes' features (detect_and_describe) -> {"T": T_a^-1 T_b in loop_closure.register_pair's convention (4 x 4
+    float64), "inliers", "matches", "rms" (metres), "keypoints_a", "keypoints_b", "reason": None} - or a refusal: "T" None and
+    "reason" "k inliers of n matches, below m" (k = 0 with fewer than 3 matches or without a valid triplet).  One match launch, both directions."""
+    cfg = config() if cfg is None else cfg
+    m_ba, m_ab = match_pairs({"a": features_a, "b": features_b}, [("b", "a"), ("a", "b")])
+    return pose_from_matches(features_a, features_b, m_ba, m_ab, cfg)

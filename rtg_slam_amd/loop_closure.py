@@ -2,6 +2,7 @@
 
     find_candidates     keyframe pairs far apart in time whose ESTIMATED poses lie close (host, deterministic)
     (place_recognition) keyframe pairs far apart in time that LOOK alike, whatever the poses say (loop_closure_candidates)
+    (keypoints)         a relative pose for an appearance pair from the two frames alone (loop_closure_appearance_init)
     register_pair       one candidate through rgbd_align.RgbdRefiner.refine from the estimated relative pose -> an edge or a refusal
     frame_corrections   the keyframes' corrections T'_k T_k^-1 spread over all frames along SE(3) geodesics
     deform_table        those corrections as the float32 table of rtgs_map_deform (include/rtgs_slam.h)
@@ -17,7 +18,13 @@ the same for both: max_correction_* then bounds the correction measured from the
 within 0.2 m and about 5 degrees plus the shift's yaw of the earlier view.  Two places that look and measure alike pass both
 witnesses; only those gates and loop_closure_huber stand against such an edge.  The defaults below are derived from the ICP's
 gates (icp_distance_threshold 0.1 m, icp_normal_threshold 20 degrees) and the drift the README quotes (5 cm over 2 000 frames),
-the appearance thresholds chosen on the synthetic box room; none has been measured on real data."""
+the appearance thresholds chosen on the synthetic box room; none has been measured on real data.
+
+loop_closure_appearance_init "keypoints" lifts that last limit: every appearance candidate's first guess becomes the relative pose
+keypoints.py computes from the two frames alone (corners, binary descriptors, a 3-D - 3-D RANSAC over their depth) when it has
+loop_closure_keypoint_min_inliers geometric witnesses, and the yaw guess otherwise; "keypoints_strict" refuses the candidate
+instead of falling back.  register_pair and its gates stay what they are - the correction gate then measures what it was meant
+to: how far the dense registration moved a guess that was already a measurement."""
 from __future__ import annotations
 
 import time
@@ -27,6 +34,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import keypoints as kp
 from . import pose_graph
 from .rgbd_align import se3_exp, se3_log
 
@@ -49,8 +57,16 @@ DEFAULTS = {
     "loop_closure_max_shift": 4,                   # columns searched to either side: 4 of 40 at a 90-degree view are about 11 degrees
     "loop_closure_min_score": 0.9,                 # ZNCC of the grey thumbnails at the best shift
     "loop_closure_max_depth_rel": 0.1,             # mean |depth difference| over the mean depth of the two thumbnails
+    # the first guess of an appearance candidate: "yaw" (place_recognition.appearance_init), "keypoints" (keypoints.relative_pose
+    # where it has min_inliers witnesses, the yaw guess otherwise) or "keypoints_strict" (no fallback: the candidate is refused)
+    "loop_closure_appearance_init": "yaw",
+    **{"loop_closure_keypoint_" + k: v for k, v in kp.DEFAULTS.items()},
 }
 CANDIDATE_SOURCES = ("pose", "appearance", "both")
+APPEARANCE_INITS = ("yaw", "keypoints", "keypoints_strict")
+# register_pair's figures, None in a candidate that keypoints_strict refused without registering it
+REGISTER_FIGURES = ("refine_reason", "iterations", "rank_min", "rms_geometric_before", "rms_geometric_after", "device_s", "inliers",
+                    "valid_source_pixels", "inlier_ratio", "correction_trans", "correction_rot_deg")
 
 
 def _angle_deg(R) -> float:
@@ -231,6 +247,14 @@ class LoopCloser:
             raise ValueError("loop_closure_min_score must lie in [-1, 1]")
         if not pl.max_depth_rel >= 0:
             raise ValueError("loop_closure_max_depth_rel must not be negative")
+        # kept apart as well: absent or "yaw", nothing of it reaches a report
+        self.keypoints = SimpleNamespace(init=str(get("loop_closure_appearance_init")),
+                                         cfg=kp.config(**{k: get("loop_closure_keypoint_" + k) for k in kp.DEFAULTS}))
+        if self.keypoints.init not in APPEARANCE_INITS:
+            raise ValueError(f"loop_closure_appearance_init must be one of {', '.join(APPEARANCE_INITS)}")
+        if self.keypoints.init != "yaw" and pl.candidates == "pose":
+            raise ValueError("loop_closure_appearance_init applies to appearance candidates: it needs loop_closure_candidates "
+                             "appearance or both")
         from .rgbd_align import RgbdRefiner
         exposure = bool(getattr(args, "rgbd_refine_exposure", False)) or bool(getattr(args, "map_exposure", False))
         ref_args = SimpleNamespace(**{k: v for k, v in vars(args).items() if k.startswith(("rgbd_refine_", "icp_"))})
@@ -277,7 +301,43 @@ class LoopCloser:
                              "pairs_scored": sum(max(0, b - cfg.min_gap + 1) for b in range(M)),
                              "candidates": len(found), "candidates_new": len(out)}
         rep["seconds"].update(describe=t1 - t0, scores=t2 - t1)
+        if self.keypoints.init != "yaw":
+            self._keypoint_inits(mapper, out, rep)
         return out
+
+    def _keypoint_inits(self, mapper, cands, rep):
+        """loop_closure_appearance_init "keypoints" / "keypoints_strict": the features of every keyframe in an appearance
+        candidate (once each, kept until this returns), ONE match launch for all pairs in both directions, the RANSAC per pair
+        on the host.  Each candidate's dict gains "init_source", "keypoints" and - under keypoints_strict below min_inliers -
+        "refused"; its "init" becomes the keypoint pose where that has its witnesses."""
+        kc, dev = self.keypoints.cfg, mapper.device
+        K = mapper.keyframe_list[0].K
+        t0 = time.perf_counter()
+        feats = {}
+        for a, b, *_ in cands:
+            for k in (a, b):
+                if k not in feats:
+                    km = mapper.keymap_list[k]
+                    feats[k] = kp.detect_and_describe(km["color_chw"], km["depth_chw"], K, kc)
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        tables = kp.match_pairs(feats, [pair for a, b, *_ in cands for pair in ((b, a), (a, b))])
+        t2 = time.perf_counter()
+        used = 0
+        for n, (a, b, _, _, seen) in enumerate(cands):
+            r = kp.pose_from_matches(feats[a], feats[b], tables[2 * n], tables[2 * n + 1], kc)
+            seen["keypoints"] = {"a": r["keypoints_a"], "b": r["keypoints_b"], "matches": r["matches"], "inliers": r["inliers"],
+                                 "rms_m": r["rms"]}
+            if r["T"] is not None:
+                seen["init"], seen["init_source"] = r["T"], "keypoints"
+                used += 1
+            else:
+                seen["init_source"] = "yaw"
+                if self.keypoints.init == "keypoints_strict":
+                    seen["refused"] = "keypoints: " + r["reason"]
+        rep["appearance"].update(init=self.keypoints.init, keypoint_inits=used,
+                                 **{"keypoint_" + k: v for k, v in vars(kc).items()})
+        rep["seconds"].update(keypoints_describe=t1 - t0, keypoints_match=t2 - t1, keypoints_ransac=time.perf_counter() - t2)
 
     def close(self, mapper, tracker) -> Dict:
         """-> the report (JSON-able).  Without an accepted edge nothing is changed: poses, keyframes and map stay bit-identical."""
@@ -308,14 +368,20 @@ class LoopCloser:
         cache, loop_edges = {}, []
         for a, b, dist, ang, seen in cands:
             init = pose_graph.inverse(old[a]) @ old[b] if seen is None else seen.pop("init")
-            r = register_pair(self.refiner, self._pyramids(mapper.keymap_list[b], K, cache, b),
-                              self._pyramids(mapper.keymap_list[a], K, cache, a), init, K, self.downscales, cfg)
+            refused = None if seen is None else seen.pop("refused", None)
+            if refused is not None:                                           # keypoints_strict: not registered at all
+                r = {"accepted": False, "reason": refused, "Z": None, **{k: None for k in REGISTER_FIGURES}}
+            else:
+                r = register_pair(self.refiner, self._pyramids(mapper.keymap_list[b], K, cache, b),
+                                  self._pyramids(mapper.keymap_list[a], K, cache, a), init, K, self.downscales, cfg)
             Z = r.pop("Z")
             r.update(a=a, b=b, frame_a=ids[a], frame_b=ids[b], distance_m=dist, angle_deg=ang)
             if mode != "pose":
                 r["source"] = "pose" if seen is None else "appearance"
                 r.update(seen or {})
-                r["Z"] = np.asarray(Z).tolist()                               # the measured T_a^-1 T_b, whatever became of it
+                r["Z"] = None if Z is None else np.asarray(Z).tolist()        # the measured T_a^-1 T_b, whatever became of it
+                if seen is not None and self.keypoints.init != "yaw":
+                    r["init"] = np.asarray(init).tolist()
             rep["candidates"].append(r)
             if r["accepted"]:
                 loop_edges.append((a, b, Z, cfg.loop_weights[0], cfg.loop_weights[1], True))

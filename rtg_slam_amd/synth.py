@@ -257,6 +257,30 @@ def box_room_color(cam: CameraSpec, c2w: torch.Tensor, depth: torch.Tensor) -> t
     return col.to(torch.float32).contiguous()
 
 
+def box_room_texture_color(cam: CameraSpec, c2w: torch.Tensor, depth: torch.Tensor, cell: float = 0.2,
+                           amplitude: float = 0.12) -> torch.Tensor:
+    """`box_room_color` plus a texture with corners in it: the world is cut into cubes of `cell` metres and every pixel gets, on
+    all three channels, the offset amplitude (2 u - 1) of the cube its WORLD point lies in, u in [0, 1] from an integer hash of
+    floor(world point / cell); clamped to [0, 1].  A function of the world point like the smooth part, so consistent across
+    views; the smooth part keeps thumbnails of nearby views alike, which a pure hash texture does not."""
+    H, W = cam.H, cam.W
+    device = depth.device
+    T = c2w.double().to(device)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64, device=device), torch.arange(W, dtype=torch.float64, device=device), indexing="ij")
+    z = depth.reshape(H, W).double()
+    pc = torch.stack([(xs - cam.cx) / cam.fx * z, (ys - cam.cy) / cam.fy * z, z], -1)
+    pw = pc @ T[:3, :3].t() + T[:3, 3]
+    q = torch.floor(pw / float(cell)).to(torch.int64)
+    m = 0xFFFFFFFF
+    h = ((q[..., 0] * 73856093) ^ (q[..., 1] * 19349663) ^ (q[..., 2] * 83492791)) & m
+    h = ((h ^ (h >> 16)) * 0x7FEB352D) & m
+    h = ((h ^ (h >> 15)) * 0x846CA68B) & m
+    h = h ^ (h >> 16)
+    u = (h & 0xFFFF).double() / 65535.0
+    col = box_room_color(cam, c2w, depth).double() + (float(amplitude) * (2.0 * u - 1.0))[None]
+    return col.clamp(0.0, 1.0).to(torch.float32).contiguous()
+
+
 def tum_noise(depth: torch.Tensor, seed: int = 0, hole_frac: float = 0.05, scale: float = 5000.0) -> torch.Tensor:
     """sigma_z = 0.0012 + 0.0019 (z-0.4)^2, 5 % holes, 1/5000 m quantisation."""
     g = torch.Generator().manual_seed(seed)

@@ -22,7 +22,20 @@
     sequence   the tour above once per loop_closure_candidates mode (pose, appearance, both; loop_closure_huber off): candidates
                by source, accepted edges, how far every measured appearance edge lies from the stream's true relative pose,
                ATE RMSE plain and aligned before and after, seconds per stage.
-    bench_ab   as above."""
+    bench_ab   as above.
+
+--keypoints measures the keypoint registration (rtg_slam_amd/keypoints.py, csrc/keypoints.hip) instead -> profiles/r28_keypoints.json:
+
+    kernels    rtgs_keypoint_detect + rtgs_keypoint_describe per keyframe at 320x240, 600x340 and 1200x680 of the textured room
+               (the two launches alone, and keypoints.detect_and_describe with its copy of the slots to the host), and
+               rtgs_keypoint_match for 1 and 64 candidate pairs (both directions each: 2 and 128 query sets) at about 300 and
+               about 3 000 keypoints a side: device events, a warm-up, 5 blocks; median and range per launch.
+    sequence   the tour above in the TEXTURED room (synth.box_room_texture_color), loop_closure_candidates appearance, once with
+               loop_closure_appearance_init yaw and once with keypoints: candidates, accepted edges, each edge's distance from
+               the stream's true relative pose, where every first guess came from, ATE RMSE plain and aligned before and after.
+    bench_ab   as above.
+
+--texture runs the sequence of any arm in the textured room."""
 import argparse
 import json
 import os
@@ -129,7 +142,76 @@ def time_place_kernels(dev):
     return out
 
 
-def sequence(dev, frames, mode=None):
+def time_keypoint_kernels(dev):
+    import numpy as np
+    import torch
+    from rtg_slam_amd import _lib, keypoints as kp, synth
+    lib = _lib.load()
+
+    def blocks(call, calls):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize(dev)
+        us = []
+        for _ in range(BLOCKS):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                call()
+            b.record()
+            b.synchronize()
+            us.append(1e3 * a.elapsed_time(b) / calls)
+        return {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
+
+    out = {"detect_describe": [], "match": []}
+    cfg = kp.config()
+    dirs, tables = kp._device_tables(dev)
+    pose = synth.trajectory(2, seed=21)[0]
+    for H, W in ((240, 320), (340, 600), (680, 1200)):
+        s = W / synth.REPLICA.W
+        cam = synth.CameraSpec(H, W, synth.REPLICA.fx * s, synth.REPLICA.fy * s, (W - 1) / 2.0, (H - 1) / 2.0)
+        d = synth.box_room_depth(cam, pose, device=dev)
+        c = synth.box_room_texture_color(cam, pose, d).contiguous()
+        d = d.reshape(1, H, W).contiguous()
+        K = np.array([[cam.fx, 0, cam.cx], [0, cam.fy, cam.cy], [0, 0, 1.0]])
+        f = kp.detect_and_describe(c, d, K, cfg, keep_planes=True)
+        n_slots = int(f["slots"].shape[0])
+        g8, box, slots, desc = f["g8"], f["box5"], f["slots"], f["slot_desc"]
+
+        def launches():
+            lib.rtgs_keypoint_detect(_lib.ptr(c), _lib.ptr(d), H, W, cfg.cell, cfg.threshold, _lib.ptr(g8), _lib.ptr(box), _lib.ptr(slots),
+                                     _lib.stream(dev))
+            lib.rtgs_keypoint_describe(_lib.ptr(g8), _lib.ptr(box), H, W, n_slots, 1, _lib.ptr(dirs), _lib.ptr(tables), _lib.ptr(slots),
+                                       _lib.ptr(desc), _lib.stream(dev))
+        row = {"H": H, "W": W, "cell": cfg.cell, "slots": n_slots, "keypoints": int(len(f["x"])), "calls_per_block": CALLS, "blocks": BLOCKS,
+               "us_per_keyframe_two_launches": blocks(launches, CALLS),
+               "us_per_keyframe_detect_and_describe": blocks(lambda: kp.detect_and_describe(c, d, K, cfg), CALLS),
+               "bytes": 21 * H * W, "note": "two launches = host enqueue included; detect_and_describe adds the compaction on the "
+                                            "device and the copy of the keypoints to the host, which waits for the device"}
+        row["GB_per_s_two_launches_at_median"] = round(row["bytes"] / row["us_per_keyframe_two_launches"]["median"] * 1e-3, 1)
+        out["detect_describe"].append(row)
+        print(row, flush=True)
+    for n, pairs, calls in ((300, 1, CALLS), (300, 64, CALLS), (3000, 1, CALLS), (3000, 64, 10)):
+        g = torch.Generator(device="cpu").manual_seed(n + pairs)
+        all_desc = torch.randint(-2 ** 31, 2 ** 31 - 1, (2 * pairs * n, 8), generator=g, dtype=torch.int64).to(torch.int32).to(dev)
+        table = []
+        for k in range(pairs):                                                    # sets 2 k and 2 k + 1, both directions
+            table.append((2 * k * n, n, (2 * k + 1) * n, n, 2 * k * n))
+            table.append(((2 * k + 1) * n, n, 2 * k * n, n, (2 * k + 1) * n))
+        tab = torch.tensor(table, dtype=torch.int32).to(dev)
+        res = torch.empty((2 * pairs * n, 3), dtype=torch.int32, device=dev)
+        call = lambda: lib.rtgs_keypoint_match(_lib.ptr(all_desc), 2 * pairs * n, _lib.ptr(tab), 2 * pairs, n, _lib.ptr(res), 2 * pairs * n,
+                                               _lib.stream(dev))
+        assert call() == 0
+        row = {"keypoints_a_side": n, "candidate_pairs": pairs, "query_sets": 2 * pairs, "distances": 2 * pairs * n * n,
+               "calls_per_block": calls, "blocks": BLOCKS, "us_per_launch": blocks(call, calls)}
+        row["distances_per_s_at_median"] = round(row["distances"] / row["us_per_launch"]["median"] * 1e6)
+        out["match"].append(row)
+        print(row, flush=True)
+    return out
+
+
+def sequence(dev, frames, mode=None, texture=False, init=None):
     import numpy as np
     import torch
     from rtg_slam_amd import mapping as mp, slam, synth
@@ -139,12 +221,13 @@ def sequence(dev, frames, mode=None):
     def stream(n):
         for c2w in poses[:n]:
             d = synth.box_room_depth(cam, c2w, device=dev)
-            c = synth.box_room_color(cam, c2w, d)
+            c = synth.box_room_texture_color(cam, c2w, d) if texture else synth.box_room_color(cam, c2w, d)
             torch.cuda.synchronize(dev)
             yield d.reshape(cam.H, cam.W), c, c2w.numpy()
 
     slam.run_sequence(cam, stream(30), mp.replica_args(seed=1), dev, capacity=800_000)         # warm-up, thrown away
-    args = mp.replica_args(seed=1, loop_closure=True, **({} if mode is None else {"loop_closure_candidates": mode}))
+    args = mp.replica_args(seed=1, loop_closure=True, **({} if mode is None else {"loop_closure_candidates": mode}),
+                           **({} if init is None else {"loop_closure_appearance_init": init}))
     mapper, tracker, rep = slam.run_sequence(cam, stream(frames), args, dev, capacity=800_000)
     lcr = rep["loop_closure"]
     reasons = {}
@@ -164,11 +247,13 @@ def sequence(dev, frames, mode=None):
         out["mode"], out["appearance"] = mode, lcr.get("appearance")
         ids = [int(i) for i in mapper.keyframe_ids]
         for row, c in zip(out["candidate_list"], lcr["candidates"]):
-            row.update({k: c[k] for k in ("source", "score", "shift", "depth_rel") if k in c})
+            row.update({k: c[k] for k in ("source", "score", "shift", "depth_rel", "init_source", "keypoints") if k in c})
             want = pg.inverse(np.asarray(tracker.pose_gt[ids[c["a"]]], dtype=np.float64)) @ np.asarray(tracker.pose_gt[ids[c["b"]]])
             row["true_angle_deg"] = float(np.rad2deg(np.arccos(min(1.0, max(-1.0, (np.trace(want[:3, :3]) - 1.0) / 2.0)))))
             row["true_distance_m"] = float(np.linalg.norm(want[:3, 3]))
-            row["z_error_m"] = float(np.linalg.norm(np.asarray(c["Z"])[:3, 3] - want[:3, 3])) if "Z" in c else None
+            row["z_error_m"] = float(np.linalg.norm(np.asarray(c["Z"])[:3, 3] - want[:3, 3])) if c.get("Z") is not None else None
+            if "init" in c:
+                row["init_error_m"] = float(np.linalg.norm(np.asarray(c["init"])[:3, 3] - want[:3, 3]))
         out["by_source"] = {s: {"candidates": sum(r.get("source", "pose") == s for r in out["candidate_list"]),
                                 "accepted": sum(r.get("source", "pose") == s and r["accepted"] for r in out["candidate_list"])}
                             for s in ("pose", "appearance")}
@@ -179,7 +264,9 @@ def sequence(dev, frames, mode=None):
                   "fps": rep["fps"], "wall_s": rep["wall_s"]}
     out["what"] = (f"slam.run_sequence, {frames} frames of synth.room_tour(seed=21) in the box room at {cam.W}x{cam.H}, "
                    "replica_args(seed=1, loop_closure=True) from an empty map, ICP tracking, every loop_closure_* value at its default"
-                   + ("" if mode is None else f" but loop_closure_candidates = {mode}"))
+                   + ("" if mode is None else f" but loop_closure_candidates = {mode}")
+                   + ("" if init is None else f" and loop_closure_appearance_init = {init}")
+                   + (", in the textured room (synth.box_room_texture_color)" if texture else ""))
     print({k: v for k, v in out.items() if k != "candidate_list"}, flush=True)
     return out
 
@@ -190,11 +277,14 @@ def main():
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--ab-runs", type=int, default=3)
     ap.add_argument("--appearance", action="store_true", help="measure the place recognition instead (r27_place_recognition.json)")
+    ap.add_argument("--keypoints", action="store_true", help="measure the keypoint registration instead (r28_keypoints.json)")
+    ap.add_argument("--texture", action="store_true", help="run the sequence in the textured room (always so with --keypoints)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--parts", default="kernels,sequence", help="what to measure now; an existing --out file keeps its other parts")
     opts = ap.parse_args()
     parts = set(opts.parts.split(","))
-    opts.out = opts.out or os.path.join(ROOT, "profiles", "r27_place_recognition.json" if opts.appearance else "r26_loop_closure.json")
+    opts.out = opts.out or os.path.join(ROOT, "profiles", "r28_keypoints.json" if opts.keypoints else
+                                        "r27_place_recognition.json" if opts.appearance else "r26_loop_closure.json")
     result = json.load(open(opts.out)) if os.path.exists(opts.out) else {}
     if opts.parent_tree:                                      # first: this process has not opened the GPU yet
         result["bench_ab"] = rac.bench_ab(os.path.abspath(opts.parent_tree), opts.ab_runs)
@@ -204,11 +294,14 @@ def main():
     dev = torch.device("cuda", 0)
     result["device"] = torch.cuda.get_device_name(dev)
     if "kernels" in parts:
-        result["kernels"] = time_place_kernels(dev) if opts.appearance else time_kernels(dev)
-    if "sequence" in parts and opts.appearance:
-        result["sequence"] = {mode: sequence(dev, opts.frames, mode) for mode in ("pose", "appearance", "both")}
+        result["kernels"] = (time_keypoint_kernels(dev) if opts.keypoints else time_place_kernels(dev) if opts.appearance
+                             else time_kernels(dev))
+    if "sequence" in parts and opts.keypoints:
+        result["sequence"] = {init: sequence(dev, opts.frames, "appearance", True, init) for init in ("yaw", "keypoints")}
+    elif "sequence" in parts and opts.appearance:
+        result["sequence"] = {mode: sequence(dev, opts.frames, mode, opts.texture) for mode in ("pose", "appearance", "both")}
     elif "sequence" in parts:
-        result["sequence"] = sequence(dev, opts.frames)
+        result["sequence"] = sequence(dev, opts.frames, texture=opts.texture)
     with open(opts.out, "w") as f:
         json.dump(result, f, indent=1, default=float)
         f.write("\n")
