@@ -867,6 +867,46 @@ int rtgs_keypoint_describe(const uint8_t* g8, const int32_t* box5, int32_t H, in
 int rtgs_keypoint_match(const uint32_t* desc, int64_t n_desc, const int32_t* pairs, int32_t n_pairs, int32_t max_queries,
                         int32_t* out, int64_t n_out, void* stream);
 
+/* ---- the match filter and the 3-D - 3-D rigid RANSAC of a batch of keyframe pairs on the device (csrc/rigid_ransac.hip; on the
+ * host it is keypoints.filter_matches and keypoints.ransac_rigid, 512 hypotheses a pair through LAPACK).
+ * tests/rigid_ransac_reference.py is the definition, in numpy float64: + - * / and sqrt in a stated order, every sum over matches
+ * in THE WAVE ORDER (above), a gated-out match counting as +0.0; the kernel matches it bit for bit.  It is a definition of its
+ * own: it fits by Horn's closed form where ransac_rigid uses an SVD, so the two agree to rounding, not in bits.
+ *
+ * rtgs_rigid_ransac.  matches [n_matches][3] int32 holds the tables rtgs_keypoint_match wrote (index, distance, second); xyz
+ *   [n_xyz][3] float64 the keypoints' back-projected points; pairs [n_pairs][6] int32 (device), for the pair (a, b): first row
+ *   and count nb of the table of b's keypoints against a's, first row and count na of the table of a's against b's, first row
+ *   of a's points and first row of b's points in xyz (na and nb of them).  A pair whose rows do not lie inside the buffers is
+ *   skipped: its record keeps what it held.
+ *     filter      row i of b's table survives when 0 <= j < na, a's row j names i, d <= max_hamming and (double)d <= ratio
+ *                 (double)second; the survivors in order of i, at most RTGS_RANSAC_MAX_MATCHES, are the n matches (a ballot and
+ *                 a prefix count, no atomics)
+ *     hypothesis  h = 0 .. iters - 1 draws mix32(seed + 3 h + j) mod n, j = 0, 1, 2 (uint32); skipped on a repeated index or
+ *                 when, in either frame, not |e1|^2 > 1e-18, not |e2|^2 > 1e-18 or not |e1 x e2|^2 >= 0.01 (|e1|^2 |e2|^2)
+ *     fit         of the triplet, and of the inliers in a refit: centroids, the 3 x 3 cross-covariance, Horn's symmetric 4 x 4
+ *                 matrix, its dominant eigenvector by 8 cyclic Jacobi sweeps (t = sign(theta) / (|theta| + sqrt(theta^2 + 1)),
+ *                 c = 1 / sqrt(t^2 + 1), s = t c, a zero off-diagonal skipped), the normalised quaternion to R, t = c_a - R c_b
+ *     count       a match is an inlier when (dx^2 + dy^2) + dz^2 <= inlier_dist^2, d = ((R b) + t) - a; the highest count wins,
+ *                 the earliest h on a tie
+ *     refit       up to three rounds on the inliers; a round that loses inliers is dropped and ends them, an unchanged set too
+ *   out [n_pairs][RTGS_RANSAC_HEAD + 3 max_matches] int32, 8-byte aligned, one record per pair: words 0 .. 33 hold 17 float64 -
+ *   T row by row (p_a = T p_b) and the rms of the inliers' residuals; word 34 n, 35 the inlier count, 36 the winning h (-1: no
+ *   valid hypothesis, or n < 3 - then T and rms are 0), 37 the survivors before the cap, 38 and 39 zero; then max_matches rows
+ *   (i, j, inlier flag), -1, -1, 0 beyond n.  max_matches must be even, at most RTGS_RANSAC_MAX_MATCHES, and at least the
+ *   smaller of that and the largest nb, or matches are dropped earlier than the definition drops them.
+ *   One block of 256 threads per pair: the n matches' points are staged once in LDS (48 KiB), one lane per hypothesis, the block's
+ *   best by shuffles, the refits by wave 0.
+ *   Returns 0 (also, without a launch, for n_pairs == 0), -1 without a launch (null or misaligned pointer, a negative count,
+ *   n_pairs > 65535, n_matches or n_xyz >= 2^31, iters < 1 or above RTGS_RANSAC_MAX_ITERS, max_matches negative, odd or above
+ *   RTGS_RANSAC_MAX_MATCHES, inlier_dist or ratio negative or NaN), -2 on a launch failure.
+ * No atomics, no host read, two runs are bit-equal. */
+#define RTGS_RANSAC_MAX_MATCHES 1024
+#define RTGS_RANSAC_MAX_ITERS 65535
+#define RTGS_RANSAC_HEAD 40
+int rtgs_rigid_ransac(const int32_t* matches, int64_t n_matches, const double* xyz, int64_t n_xyz, const int32_t* pairs,
+                      int32_t n_pairs, int32_t max_hamming, double ratio, int32_t iters, double inlier_dist, uint32_t seed,
+                      int32_t max_matches, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,9 @@ as a second witness), so that a loop whose drift exceeds --loop-closure-max-tran
 --loop-closure-max-shift, --loop-closure-min-score and --loop-closure-max-depth-rel set it up.  All five need --loop-closure,
 are written only when given, and the report's candidates gain `source` (and `score`, `shift`, `depth_rel`) and the report
 `appearance` only then.
+`--relocalise` (off by default; rtg_slam_amd.relocalisation) gives the loop a lost state: a frame the ICP tracker cannot hold is
+not mapped, and it and the frames after it are searched for among the keyframes until one is recovered; run_report.json gains
+`relocalisation` and `ate_rmse_tracked_m`.  `--loop-closure-keypoint-ransac device` runs the keypoint pose's RANSAC in one launch.
 `--loop-closure-appearance-init keypoints` (with candidates appearance or both) starts each appearance candidate's registration
 from a relative pose computed from the two keyframes alone (rtg_slam_amd.keypoints: FAST-9 corners, 256-bit descriptors, a
 brute-force Hamming match on the device, a 3-D - 3-D RANSAC over the matches' depth on the host) wherever that pose has
@@ -204,6 +207,10 @@ def _apply_loop_closure(args, opts) -> str | None:
         if name == "keypoint_oriented":
             value = value == "true"
         setattr(args, "loop_closure_" + name, list(value) if isinstance(value, (list, tuple)) else value)
+    if getattr(opts, "loop_closure_keypoint_ransac", None) is not None:      # not one of LOOP_CLOSURE_FLAGS: no key of DEFAULTS
+        if not getattr(args, "loop_closure", False):
+            return "--loop-closure-keypoint-ransac needs --loop-closure (or loop_closure: true in the config)"
+        args.loop_closure_keypoint_ransac = opts.loop_closure_keypoint_ransac
     if not getattr(args, "loop_closure", False):
         return None
     if getattr(args, "use_gt_pose", False):
@@ -211,6 +218,40 @@ def _apply_loop_closure(args, opts) -> str | None:
     try:
         from .loop_closure import LoopCloser
         LoopCloser(args)
+    except ValueError as e:
+        return str(e)
+    return None
+
+
+RELOCALISE_FLAGS = (("candidates", int, "N", "keyframes a lost frame is matched against, best thumbnail score first (default 3)"),
+                    ("min_score", float, "R", "ZNCC a keyframe's thumbnail needs against the lost frame's (default: loop closure's, 0.9)"),
+                    ("max_depth_rel", float, "R", "relative difference their depth thumbnails may have (default: loop closure's, 0.1)"),
+                    ("thumb_width", int, "N", "columns of a thumbnail (default: loop closure's, 40)"),
+                    ("max_shift", int, "N", "thumbnail columns searched to either side (default: loop closure's, 4)"),
+                    ("min_inliers", int, "N", "RANSAC inliers the keypoint pose needs (default: loop closure's, 8)"),
+                    ("min_inlier_ratio", float, "R", "registration gate (default: loop closure's, 0.3)"),
+                    ("max_rms", float, "M", "registration gate, metres (default: loop closure's, 0.02)"),
+                    ("max_correction_trans", float, "M", "registration gate, metres (default: loop closure's, 0.2)"),
+                    ("max_correction_rot_deg", float, "DEG", "registration gate, degrees (default: loop closure's, 5)"))
+
+
+def _apply_relocalise(args, opts) -> str | None:
+    """--relocalise and its --relocalise-* values set the config's `relocalise*` keys (absent from every preset), only when given;
+    -> what is wrong with them, or None."""
+    if getattr(opts, "relocalise", False):
+        args.relocalise = True
+    for name, *_ in RELOCALISE_FLAGS:
+        value = getattr(opts, "relocalise_" + name, None)
+        if value is None:
+            continue
+        if not getattr(args, "relocalise", False):
+            return f"--relocalise-{name.replace('_', '-')} needs --relocalise (or relocalise: true in the config)"
+        setattr(args, "relocalise_" + name, value)
+    if not getattr(args, "relocalise", False):
+        return None
+    try:
+        from .relocalisation import Relocaliser
+        Relocaliser(args)
     except ValueError as e:
         return str(e)
     return None
@@ -255,6 +296,10 @@ def cmd_slam(opts) -> int:
     if wrong is not None:
         log(wrong)
         return 2
+    wrong = _apply_relocalise(args, opts)
+    if wrong is not None:
+        log(wrong)
+        return 2
     save_path = args.save_path
     if os.path.isdir(save_path) and os.listdir(save_path):
         if not opts.overwrite:
@@ -278,6 +323,8 @@ def cmd_slam(opts) -> int:
             log(f"map exposure: channels {args.map_exposure_channels}")
     if getattr(args, "loop_closure", False):
         log("loop closure: on (once, after the last frame: keyframe pose graph, corrected trajectory, deformed map)")
+    if getattr(args, "relocalise", False):
+        log("relocalise: on (a frame ICP cannot hold is not mapped; lost frames are searched for among the keyframes)")
     if "device_list" in vars(args):
         log(f"device_list {args.device_list} ignored; running on {opts.device}")
     device = torch.device(opts.device)
@@ -318,6 +365,10 @@ def cmd_slam(opts) -> int:
             f"max {100 * lc.get('correction_max_m', 0.0):.2f} cm / mean {100 * lc.get('correction_mean_m', 0.0):.2f} cm, ATE "
             f"{100 * lc['ate_rmse_m_before']:.3f} -> {100 * lc['ate_rmse_m']:.3f} cm (aligned "
             f"{100 * lc['ate_rmse_aligned_m_before']:.3f} -> {100 * lc['ate_rmse_aligned_m']:.3f} cm) in {lc['seconds']['total']:.3f} s")
+    if "relocalisation" in report:
+        rl = report["relocalisation"]
+        log(f"relocalise: {len(rl['lost_frames'])} frames lost, {len(rl['events'])} recoveries in {rl['attempts']} attempts, "
+            f"refusals {rl['refusals']}")
     ates = prefix_ates(tracker.pose_es, tracker.pose_gt)
     with open(os.path.join(save_path, "save_traj", "ate.txt"), "w") as f:
         f.write("".join(f"{a!r}\n" for a in ates))
@@ -841,6 +892,15 @@ def build_parser() -> argparse.ArgumentParser:
             s.add_argument("--loop-closure-" + name.replace("_", "-"), choices=LOOP_CLOSURE_CHOICES[name], default=None, help=text)
         else:
             s.add_argument("--loop-closure-" + name.replace("_", "-"), type=typ, default=None, metavar=meta, help=text)
+    s.add_argument("--relocalise", action="store_true",
+                   help="a frame the ICP tracker cannot hold is not mapped; it and the frames after it are searched for among "
+                        "the keyframes (thumbnails, keypoints, a device RANSAC, a gated registration) until one is recovered "
+                        "(rtg_slam_amd.relocalisation)")
+    for name, typ, meta, text in RELOCALISE_FLAGS:
+        s.add_argument("--relocalise-" + name.replace("_", "-"), type=typ, default=None, metavar=meta, help=text)
+    s.add_argument("--loop-closure-keypoint-ransac", choices=("host", "device"), default=None,
+                   help="where the keypoint pose's match filter and RANSAC run: on the host per candidate (default), or in one "
+                        "rtgs_rigid_ransac launch for all candidates")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)

@@ -6,6 +6,8 @@ tests/keypoint_reference.py): what the reference gets from its ORB back end, in 
     filter_matches        mutual best, Hamming bound, ratio test (host)
     ransac_rigid          3-D - 3-D RANSAC over the matches' back-projected points (host, numpy float64, deterministic)
     relative_pose         the four together for one pair -> T = T_a^-1 T_b with its count of geometric witnesses, or a refusal
+    rigid_ransac_pairs    the filter and the RANSAC of a batch of pairs on the device, ONE launch behind the match launch, the match
+                          tables never leaving the device (rtgs_rigid_ransac; the definition is tests/rigid_ransac_reference.py)
 
 FAST-9 corners on the 8-bit grey image, one per cell of the image, oriented by the intensity centroid in 32 bins, described by
 256 comparisons of 5 x 5 box sums.  Single scale, pixel-centre localisation, no vocabulary.  After the grey value everything on
@@ -143,13 +145,9 @@ def detect_and_describe(color_chw: torch.Tensor, depth_chw: torch.Tensor, K, cfg
     return out
 
 
-def match_pairs(features, pairs: Sequence[Tuple]) -> List[np.ndarray]:
-    """features: keyframe key -> {"desc": int32 [N, 8] on the device} (a dict, or a list indexed by key); pairs: [(query key,
-    reference key)] -> per pair an int32 numpy [N_query, 3]: the reference's index, the distance, the second distance (-1, 257,
-    257 against an empty set).  One launch and one copy to the host for the whole batch."""
-    pairs = list(pairs)
-    if not pairs:
-        return []
+def _match_launch(features, pairs):
+    """The launch of match_pairs -> (out int32 [n_out, 3] on the device, or None when there is no query at all; table: per pair
+    (first query row, query count, first reference row, reference count, first row of out))."""
     keys = []
     for q, r in pairs:
         for k in (q, r):
@@ -171,7 +169,7 @@ def match_pairs(features, pairs: Sequence[Tuple]) -> List[np.ndarray]:
         table.append((begin[q], nq, begin[r], int(features[r]["desc"].shape[0]), n_out))
         n_out += nq
     if n_out == 0:
-        return [np.empty((0, 3), dtype=np.int32) for _ in pairs]
+        return None, table
     if len(pairs) > 65535:
         raise ValueError("match_pairs: at most 65535 pairs a launch")
     all_desc = torch.cat(descs, dim=0).contiguous()
@@ -182,8 +180,31 @@ def match_pairs(features, pairs: Sequence[Tuple]) -> List[np.ndarray]:
         rc = lib.rtgs_keypoint_match(_lib.ptr(all_desc), total, _lib.ptr(tab), len(pairs), max(t[1] for t in table), _lib.ptr(out), n_out,
                                      _lib.stream(dev))
     _lib.check(rc, "rtgs_keypoint_match")
+    return out, table
+
+
+def match_pairs(features, pairs: Sequence[Tuple]) -> List[np.ndarray]:
+    """features: keyframe key -> {"desc": int32 [N, 8] on the device} (a dict, or a list indexed by key); pairs: [(query key,
+    reference key)] -> per pair an int32 numpy [N_query, 3]: the reference's index, the distance, the second distance (-1, 257,
+    257 against an empty set).  One launch and one copy to the host for the whole batch."""
+    pairs = list(pairs)
+    if not pairs:
+        return []
+    out, table = _match_launch(features, pairs)
+    if out is None:
+        return [np.empty((0, 3), dtype=np.int32) for _ in pairs]
     host = out.cpu().numpy()
     return [host[t[4]:t[4] + t[1]] for t in table]
+
+
+def match_pairs_device(features, pairs: Sequence[Tuple]) -> Tuple:
+    """match_pairs with its table left on the device, for rigid_ransac_tables: -> (int32 [n_out, 3] device tensor, or None
+    when no pair has a query; [(first row, rows)] per pair).  One launch, no copy to the host."""
+    pairs = list(pairs)
+    if not pairs:
+        return None, []
+    out, table = _match_launch(features, pairs)
+    return out, [(t[4], t[1]) for t in table]
 
 
 def filter_matches(m_ba, m_ab, max_hamming: int = 64, ratio: float = 0.8) -> List[Tuple[int, int, int]]:
@@ -289,3 +310,102 @@ def relative_pose(features_a: Dict, features_b: Dict, cfg=None) -> Dict:
     cfg = config() if cfg is None else cfg
     m_ba, m_ab = match_pairs({"a": features_a, "b": features_b}, [("b", "a"), ("a", "b")])
     return pose_from_matches(features_a, features_b, m_ba, m_ab, cfg)
+
+
+RANSAC_CAP, RANSAC_HEAD = _lib.CONSTANTS["RTGS_RANSAC_MAX_MATCHES"], _lib.CONSTANTS["RTGS_RANSAC_HEAD"]
+RANSAC_MAX_ITERS = _lib.CONSTANTS["RTGS_RANSAC_MAX_ITERS"]
+
+
+def device_xyz(features: Dict, dev) -> torch.Tensor:
+    """The features' "xyz" on the device, float64 [N, 3]: the host's array uploaded once and kept under "xyz_dev", so both forms
+    hold the same bits."""
+    hit = features.get("xyz_dev")
+    if hit is None or hit.device != dev:
+        hit = features["xyz_dev"] = torch.from_numpy(np.ascontiguousarray(features["xyz"], dtype=np.float64).reshape(-1, 3)).to(dev)
+    return hit
+
+
+def rigid_ransac_tables(matches, xyz, table, dev, max_hamming: int = 64, ratio: float = 0.8, iters: int = 512, inlier_dist: float = 0.05,
+                        seed: int = 0) -> List[Dict]:
+    """rtgs_rigid_ransac (include/rtgs_slam.h; the definition is tests/rigid_ransac_reference.py) for a batch of pairs: matches
+    int32 [n, 3] and xyz float64 [m, 3] on the device `dev` (None for none), table [(first row and count nb of b's matches
+    against a, first row and count na of a's against b, first row of a's points, first row of b's)] on the host.  -> per pair
+    {"T" 4 x 4 float64, "n", "inliers", "rms", "h", "survivors", "ij" int32 [n, 2], "mask" bool [n]}; h = -1 (T and rms zero)
+    without a valid hypothesis.  One launch and one copy to the host for the whole batch."""
+    table = [tuple(int(v) for v in t) for t in table]
+    if not table:
+        return []
+    if len(table) > 65535:
+        raise ValueError("rigid_ransac_tables: at most 65535 pairs a launch")
+    if not 1 <= int(iters) <= RANSAC_MAX_ITERS:
+        raise ValueError(f"rigid_ransac_tables: iters must lie in 1 .. {RANSAC_MAX_ITERS}")
+    for t, dtype, name in ((matches, torch.int32, "matches"), (xyz, torch.float64, "xyz")):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == dtype and t.dim() == 2
+                                  and t.shape[1] == 3 and t.is_contiguous()):
+            raise ValueError(f"rigid_ransac_tables: {name} must be a contiguous {dtype} [N, 3] tensor on the device")
+    rows = min(RANSAC_CAP, max(0, max(t[1] for t in table)))
+    rows += rows & 1
+    out = torch.empty((len(table), RANSAC_HEAD + 3 * rows), dtype=torch.int32, device=dev)
+    tab = torch.tensor(table, dtype=torch.int32).reshape(-1, 6).to(dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_rigid_ransac(_lib.ptr0(matches), 0 if matches is None else int(matches.shape[0]), _lib.ptr0(xyz),
+                                   0 if xyz is None else int(xyz.shape[0]), _lib.ptr(tab), len(table), int(max_hamming), float(ratio),
+                                   int(iters), float(inlier_dist), int(seed) & 0xFFFFFFFF, rows, _lib.ptr(out), _lib.stream(dev))
+    _lib.check(rc, "rtgs_rigid_ransac")
+    host = out.cpu().numpy()                                                                      # the one copy
+    f64 = np.ascontiguousarray(host[:, :34]).view(np.float64)
+    res = []
+    for p in range(len(table)):
+        n = int(host[p, 34])
+        m = host[p, RANSAC_HEAD:RANSAC_HEAD + 3 * n].reshape(n, 3)
+        res.append({"T": f64[p, :16].reshape(4, 4).copy(), "n": n, "inliers": int(host[p, 35]), "rms": float(f64[p, 16]), "h": int(host[p, 36]),
+                    "survivors": int(host[p, 37]), "ij": m[:, :2].copy(), "mask": m[:, 2] != 0})
+    return res
+
+
+def rigid_ransac_pairs(features, pairs: Sequence[Tuple], cfg=None, seed: int = 0, seconds: Dict = None) -> List[Dict]:
+    """features: keyframe key -> detect_and_describe's dict; pairs: [(a, b)] -> per pair what pose_from_matches returns ("T" =
+    T_a^-1 T_b with at least cfg.min_inliers witnesses, or None and a "reason"), plus "h", "ij" and "mask" of
+    rigid_ransac_tables.  One match launch (both directions of every pair) and one rtgs_rigid_ransac launch for the whole batch,
+    the match tables never leaving the device; one copy to the host.  The filter and the RANSAC are the definition's
+    (tests/rigid_ransac_reference.py), which agrees with filter_matches and ransac_rigid in the matches and, to rounding, in
+    the pose of one inlier set - not bit for bit.  With `seconds` (a dict) the device is synchronised behind the match launch and
+    the dict gains "match" and "ransac", the seconds each took."""
+    import time
+    cfg = config() if cfg is None else cfg
+    pairs = list(pairs)
+    if not pairs:
+        return []
+    t0 = time.perf_counter()
+    matches, where = match_pairs_device(features, [q for a, b in pairs for q in ((b, a), (a, b))])
+    if seconds is not None:
+        torch.cuda.synchronize(features[pairs[0][0]]["desc"].device)
+        seconds["match"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+    keys = []
+    for a, b in pairs:
+        for k in (a, b):
+            if k not in keys:
+                keys.append(k)
+    dev = features[keys[0]]["desc"].device
+    begin, total = {}, 0
+    for k in keys:
+        begin[k] = total
+        total += int(features[k]["desc"].shape[0])
+    xyz = torch.cat([device_xyz(features[k], dev) for k in keys], dim=0).contiguous() if total else None
+    table = [(where[2 * n][0], where[2 * n][1], where[2 * n + 1][0], where[2 * n + 1][1], begin[a], begin[b]) for n, (a, b) in enumerate(pairs)]
+    fits = rigid_ransac_tables(matches, xyz, table, dev, cfg.max_hamming, cfg.ratio, cfg.ransac_iters, cfg.inlier_dist, seed)
+    if seconds is not None:
+        seconds["ransac"] = time.perf_counter() - t0
+    res = []
+    for (a, b), fit in zip(pairs, fits):
+        out = {"T": None, "inliers": fit["inliers"], "matches": fit["n"], "rms": fit["rms"] if fit["h"] >= 0 else None,
+               "keypoints_a": int(len(features[a]["x"])), "keypoints_b": int(len(features[b]["x"])), "reason": None,
+               "h": fit["h"], "ij": fit["ij"], "mask": fit["mask"]}
+        if out["inliers"] < cfg.min_inliers:
+            out["reason"] = f"{out['inliers']} inliers of {fit['n']} matches, below {cfg.min_inliers}"
+        else:
+            out["T"] = fit["T"]
+        res.append(out)
+    return res

@@ -64,6 +64,10 @@ DEFAULTS = {
 }
 CANDIDATE_SOURCES = ("pose", "appearance", "both")
 APPEARANCE_INITS = ("yaw", "keypoints", "keypoints_strict")
+# loop_closure_keypoint_ransac: where the match filter and the RANSAC of the keypoint pose run.  "host" (the default, also when
+# the key is absent) is keypoints.pose_from_matches per candidate; "device" is one rtgs_rigid_ransac launch for all candidates
+# (keypoints.rigid_ransac_pairs).  Kept out of DEFAULTS: absent or "host", no report and no launch knows of it
+KEYPOINT_RANSACS = ("host", "device")
 # register_pair's figures, None in a candidate that keypoints_strict refused without registering it
 REGISTER_FIGURES = ("refine_reason", "iterations", "rank_min", "rms_geometric_before", "rms_geometric_after", "device_s", "inliers",
                     "valid_source_pixels", "inlier_ratio", "correction_trans", "correction_rot_deg")
@@ -252,6 +256,14 @@ class LoopCloser:
                                          cfg=kp.config(**{k: get("loop_closure_keypoint_" + k) for k in kp.DEFAULTS}))
         if self.keypoints.init not in APPEARANCE_INITS:
             raise ValueError(f"loop_closure_appearance_init must be one of {', '.join(APPEARANCE_INITS)}")
+        self.keypoints.ransac = str(getattr(args, "loop_closure_keypoint_ransac", "host"))
+        if self.keypoints.ransac not in KEYPOINT_RANSACS:
+            raise ValueError(f"loop_closure_keypoint_ransac must be one of {', '.join(KEYPOINT_RANSACS)}")
+        if self.keypoints.ransac == "device" and self.keypoints.init == "yaw":
+            raise ValueError("loop_closure_keypoint_ransac applies to the keypoint pose: it needs loop_closure_appearance_init "
+                             "keypoints or keypoints_strict")
+        if self.keypoints.ransac == "device" and self.keypoints.cfg.ransac_iters > kp.RANSAC_MAX_ITERS:
+            raise ValueError(f"loop_closure_keypoint_ransac device: loop_closure_keypoint_ransac_iters must not exceed {kp.RANSAC_MAX_ITERS}")
         if self.keypoints.init != "yaw" and pl.candidates == "pose":
             raise ValueError("loop_closure_appearance_init applies to appearance candidates: it needs loop_closure_candidates "
                              "appearance or both")
@@ -308,7 +320,8 @@ class LoopCloser:
     def _keypoint_inits(self, mapper, cands, rep):
         """loop_closure_appearance_init "keypoints" / "keypoints_strict": the features of every keyframe in an appearance
         candidate (once each, kept until this returns), ONE match launch for all pairs in both directions, the RANSAC per pair
-        on the host.  Each candidate's dict gains "init_source", "keypoints" and - under keypoints_strict below min_inliers -
+        on the host - or, with loop_closure_keypoint_ransac "device", one rtgs_rigid_ransac launch for all pairs behind the
+        match launch, the match tables staying on the device.  Each candidate's dict gains "init_source", "keypoints" and - under keypoints_strict below min_inliers -
         "refused"; its "init" becomes the keypoint pose where that has its witnesses."""
         kc, dev = self.keypoints.cfg, mapper.device
         K = mapper.keyframe_list[0].K
@@ -321,11 +334,15 @@ class LoopCloser:
                     feats[k] = kp.detect_and_describe(km["color_chw"], km["depth_chw"], K, kc)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
-        tables = kp.match_pairs(feats, [pair for a, b, *_ in cands for pair in ((b, a), (a, b))])
+        on_device = self.keypoints.ransac == "device"
+        if on_device:
+            fits = kp.rigid_ransac_pairs(feats, [(a, b) for a, b, *_ in cands], kc)      # t2 - t1 below is both launches and the copy
+        else:
+            tables = kp.match_pairs(feats, [pair for a, b, *_ in cands for pair in ((b, a), (a, b))])
         t2 = time.perf_counter()
         used = 0
         for n, (a, b, _, _, seen) in enumerate(cands):
-            r = kp.pose_from_matches(feats[a], feats[b], tables[2 * n], tables[2 * n + 1], kc)
+            r = fits[n] if on_device else kp.pose_from_matches(feats[a], feats[b], tables[2 * n], tables[2 * n + 1], kc)
             seen["keypoints"] = {"a": r["keypoints_a"], "b": r["keypoints_b"], "matches": r["matches"], "inliers": r["inliers"],
                                  "rms_m": r["rms"]}
             if r["T"] is not None:
@@ -337,6 +354,8 @@ class LoopCloser:
                     seen["refused"] = "keypoints: " + r["reason"]
         rep["appearance"].update(init=self.keypoints.init, keypoint_inits=used,
                                  **{"keypoint_" + k: v for k, v in vars(kc).items()})
+        if on_device:
+            rep["appearance"]["keypoint_ransac"] = "device"
         rep["seconds"].update(keypoints_describe=t1 - t0, keypoints_match=t2 - t1, keypoints_ransac=time.perf_counter() - t2)
 
     def close(self, mapper, tracker) -> Dict:

@@ -37,6 +37,11 @@ class Tracker:
         self.rgbd_target = str(getattr(args, "rgbd_refine_target", "frame"))
         self.rgbd_exposure = (1.0, 0.0)                                       # of the frame last refined, into its target's
         self._color_t1 = None
+        # extension (off by default): `relocalise` - run_sequence sets the relocaliser; lost_frames are the frames that kept the
+        # last good pose and were not mapped
+        self.relocaliser = None
+        self.lost = False
+        self.lost_frames = []
         if self.rgbd_target not in ("frame", "model"):
             raise ValueError(f"rgbd_refine_target must be 'frame' or 'model', not {self.rgbd_target!r}")
         if not bool(getattr(args, "rgbd_refine", False)):
@@ -68,6 +73,15 @@ class Tracker:
         elif not self.initialized:
             self.initialized = True
             pose = np.eye(4) if init_pose is None else np.asarray(init_pose, dtype=np.float64)
+        elif self.relocaliser is not None:
+            pose, ok = self._track_or_relocalise(frame_map)
+            if self.lost:
+                # a lost frame: the last good pose, one row of pose_es all the same; the ICP state and the photometric target
+                # stay those of the last tracked frame, and nothing is prepared for the mapper
+                self.pose_es.append(pose)
+                self.lost_frames.append(int(self.curr_frame["frame_id"]))
+                frame.updatePose(pose)
+                return False
         else:
             rel, ok = self.icp_tracker.predict_pose(self.curr_frame)
             if self.rgbd_refiner is not None:
@@ -86,6 +100,31 @@ class Tracker:
         frame_map["normal_map_w"] = self.so.transform_map(frame_map["normal_map_c"], rot)
         # transform_map moves the zero vertices of invalid pixels too; they are never sampled (depth 0 / zero normal masks)
         return ok
+
+    def _track_or_relocalise(self, frame_map):
+        """`relocalise`: -> (pose, ok) and self.lost.  A frame is lost when predict_pose reports singular normal equations, a
+        non-finite pose or tracking_success False; while lost ICP is not tried and every frame goes to the relocaliser, whose
+        pose - the frame registered onto a keyframe - ends the lost state."""
+        if not self.lost:
+            try:
+                rel, ok = self.icp_tracker.predict_pose(self.curr_frame)
+            except RuntimeError as e:
+                if "singular normal equations" not in str(e):
+                    raise
+                rel, ok = None, False
+            if ok and not np.isfinite(rel).all():
+                ok = False
+            if ok:
+                if self.rgbd_refiner is not None:
+                    rel = self._rgbd_refine(rel, frame_map)
+                return self.pose_es[-1] @ rel.astype(np.float64), True
+            self.lost = True
+            self.relocaliser.lost_at = int(self.curr_frame["frame_id"])
+        pose = self.relocaliser.locate(self, frame_map, int(self.curr_frame["frame_id"]))
+        if pose is None:
+            return np.array(self.pose_es[-1], dtype=np.float64), False
+        self.lost = False
+        return pose, True
 
     def _intensity_pyramid(self, frame_map):
         """This frame's intensity pyramid, built once per frame (it is the source now and the target of the next frame)."""
@@ -173,7 +212,12 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
 
     args.loop_closure (absent = off): after the last frame and before the final global optimisation the loop closure runs once
     (loop_closure.LoopCloser.close): report["loop_closure"] is its report, the trajectory, the keyframes and the map are the
-    corrected ones, and tracker.pose_es_before_loop_closure keeps the trajectory as it was tracked."""
+    corrected ones, and tracker.pose_es_before_loop_closure keeps the trajectory as it was tracked.
+
+    args.relocalise (absent = off; rtg_slam_amd.relocalisation): a frame the ICP tracker cannot hold is LOST - it keeps the last
+    good pose, is listed in tracker.lost_frames and is not mapped (mapper.time still advances, so pose_es keeps one row per
+    frame) - and so is every frame after it until the relocaliser registers one onto a keyframe; that frame is mapped like any
+    other.  report["relocalisation"] and report["ate_rmse_tracked_m"] (the ATE over the frames not lost) exist only then."""
     from . import evaluation
     mapper = mapper if mapper is not None else Mapping(args, device, capacity=capacity, lr_scale=lr_scale)
     tracker = Tracker(args, device)
@@ -183,6 +227,11 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         if mapper.opt.world != 1:
             raise RuntimeError("loop_closure runs on one rank: the map deformation is not exchanged between ranks")
         closer = LoopCloser(args)                               # a bad option stops the run before its first frame
+    reloc = None
+    if bool(getattr(args, "relocalise", False)):
+        from .relocalisation import Relocaliser
+        reloc = tracker.relocaliser = Relocaliser(args, mapper.opt.world)      # the same: before the first frame
+        reloc.mapper = mapper
     t_track, t_map, per_frame = 0.0, 0.0, []
     evals, last_kf = [], None
     n = 0
@@ -194,6 +243,14 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         frame_map = tracker.map_preprocess(frame, depth, color, frame_id)
         tracker.tracking(frame, frame_map, pose_gt=gt_c2w, init_pose=gt_c2w if frame_id == 0 else None)
         t1 = time.perf_counter()                                # predict_pose returned a host pose: the tracker is done
+        if reloc is not None and tracker.lost:                  # a lost frame is not mapped; the map's clock still ticks
+            t_track += t1 - t0
+            per_frame.append((t1 - t0, 0.0, mapper.opt.N, mapper.opt.n_frozen))
+            if on_frame is not None:
+                on_frame(frame_id, frame, frame_map, mapper, tracker)
+            mapper.time += 1
+            n += 1
+            continue
         mapper.update_poses(tracker.get_new_poses())            # slam.py:76-77
         mapper.mapping(frame, frame_map, frame_id)
         mm = mapper.get_render_output(frame)
@@ -204,6 +261,8 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         else:
             tracker.update_last_status(frame, mm["render_depth"].clone(), frame_map["depth_map"],
                                        mm["render_normal"].contiguous(), frame_map["normal_map_w"])
+        if reloc is not None:
+            reloc.on_keyframes(mapper)                          # a new keyframe's thumbnail: one launch
         torch.cuda.synchronize(device)                          # the mapper's frame is over when its kernels are
         t2 = time.perf_counter()
         t_track += t1 - t0
@@ -252,6 +311,10 @@ def run_sequence(cam, stream: Iterable, args, device, mapper: Optional[Mapping] 
         report["eval"] = evals
     if closure is not None:
         report["loop_closure"] = closure
+    if reloc is not None:
+        report["relocalisation"] = reloc.report(tracker)
+        kept = [k for k in range(n) if k not in set(tracker.lost_frames)]
+        report["ate_rmse_tracked_m"] = ate_rmse([es[k] for k in kept], [gt[k] for k in kept]) if kept and len(gt) == n else None
     if tracker.rgbd_refiner is not None:
         reps = tracker.rgbd_reports
         k = max(len(reps), 1)
