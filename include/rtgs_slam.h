@@ -867,6 +867,51 @@ int rtgs_keypoint_describe(const uint8_t* g8, const int32_t* box5, int32_t H, in
 int rtgs_keypoint_match(const uint32_t* desc, int64_t n_desc, const int32_t* pairs, int32_t n_pairs, int32_t max_queries,
                         int32_t* out, int64_t n_out, void* stream);
 
+/* ---- the keypoints over an image pyramid, so that a revisit from another distance matches, and the votes by which revisits are
+ * found (csrc/keypoint_pyramid.hip).  tests/keypoint_pyramid_reference.py is the definition, in numpy; after the grey value
+ * everything is integer arithmetic and the four kernels match it bit for bit.
+ *
+ * THE LADDER.  Level l has the scale num / den = 1, 3/2, 2, 3, 4.  Level 1 is level 0 reduced 3:2, level 2 is level 0 reduced 2:1,
+ *   level 3 is level 1 reduced 2:1, level 4 is level 2 reduced 2:1.
+ *     2:1  size floor(W / 2) x floor(H / 2), value (a + b + c + d + 2) >> 2 of the 2 x 2 block; a trailing odd row or column is dropped
+ *     3:2  size 2 floor(W / 3) x 2 floor(H / 3); along each axis output 2k takes the inputs 3k, 3k + 1 with the weights 2, 1 and
+ *          output 2k + 1 the inputs 3k + 1, 3k + 2 with 1, 2; value (sum of the 2-D weight products times g8 + 4) / 9
+ *   Level 0's g8 is rtgs_keypoint_detect's.  A level's depth at (x, y) is level 0's at (floor((2x + 1) num / (2 den)),
+ *   floor((2y + 1) num / (2 den))): never an average.
+ *   levels [n_levels][5] int32 is a HOST array, 1 <= n_levels <= RTGS_KEYPOINT_MAX_LEVELS: first pixel of the level in the
+ *   buffers, H, W, num, den.  The caller chooses how many levels and where they lie; H, W, num and den must be the ladder's, every
+ *   level must lie inside the n_pixels of the buffers and no two may overlap.
+ *
+ * rtgs_keypoint_pyramid.  color_chw [3][H][W] and depth [H][W] float32 (H, W = level 0's) -> g8 [n_pixels] uint8 and depth_levels
+ *   [n_pixels] float32, the planes of all levels.  One block per 48 x 48 tile of level 0 makes that tile of every level.
+ * rtgs_keypoint_detect_levels.  g8, depth_levels -> box5 [n_pixels] int32 (per level, pixels outside the level counting as 0) and
+ *   slots [cells][4] int32: the slots of rtgs_keypoint_detect for every level in turn, level after level, x and y in the
+ *   level's pixels; cells = sum over the levels of ceil(H_l / cell) ceil(W_l / cell).  The rule per level is rtgs_keypoint_detect's,
+ *   the margin counted in the level's pixels.
+ * rtgs_keypoint_describe_levels.  rtgs_keypoint_describe over the same slots -> slots[.][3] and desc [cells][8] uint32.
+ *   All three return 0, -1 without a launch (null pointer, a table that is not the ladder's or leaves the buffers, n_pixels < 1 or
+ *   >= 2^31, cell or threshold outside rtgs_keypoint_detect's ranges), -2 on a launch failure.  With n_levels = 1 the three
+ *   together leave what rtgs_keypoint_detect and rtgs_keypoint_describe leave.
+ *
+ * rtgs_keypoint_votes.  matches [n_matches][3] int32 holds the tables rtgs_keypoint_match wrote; pairs [n_pairs][4] int32 (device),
+ *   for the pair (a, b): first row and count nb of the table of b's keypoints against a's, first row and count na of the table
+ *   of a's against b's.  votes[pair] = the number of rows i of b's table that survive rtgs_rigid_ransac's filter: 0 <= j < na,
+ *   a's row j names i, d <= max_hamming and (double)d <= ratio (double)second; not capped.  A pair whose rows do not lie inside
+ *   the buffer is skipped: votes keeps what it held.  One wave per pair, ballots and population counts.
+ *   Returns 0 (also, without a launch, for n_pairs == 0), -1 (null pointer, a negative count, n_matches >= 2^31, ratio negative or
+ *   NaN), -2.
+ * No atomics, no host read, two runs are bit-equal. */
+#define RTGS_KEYPOINT_MAX_LEVELS 5
+int rtgs_keypoint_pyramid(const float* color_chw, const float* depth, const int32_t* levels, int32_t n_levels, int64_t n_pixels,
+                          uint8_t* g8, float* depth_levels, void* stream);
+int rtgs_keypoint_detect_levels(const uint8_t* g8, const float* depth_levels, const int32_t* levels, int32_t n_levels, int64_t n_pixels,
+                                int32_t cell, int32_t threshold, int32_t* box5, int32_t* slots, void* stream);
+int rtgs_keypoint_describe_levels(const uint8_t* g8, const int32_t* box5, const int32_t* levels, int32_t n_levels, int64_t n_pixels,
+                                  int32_t cell, int32_t oriented, const int32_t* dirs, const uint32_t* tables, int32_t* slots,
+                                  uint32_t* desc, void* stream);
+int rtgs_keypoint_votes(const int32_t* matches, int64_t n_matches, const int32_t* pairs, int32_t n_pairs, int32_t max_hamming,
+                        double ratio, int32_t* votes, void* stream);
+
 /* ---- the match filter and the 3-D - 3-D rigid RANSAC of a batch of keyframe pairs on the device (csrc/rigid_ransac.hip; on the
  * host it is keypoints.filter_matches and keypoints.ransac_rigid, 512 hypotheses a pair through LAPACK).
  * tests/rigid_ransac_reference.py is the definition, in numpy float64: + - * / and sqrt in a stated order, every sum over matches

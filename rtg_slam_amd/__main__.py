@@ -68,7 +68,12 @@ brute-force Hamming match on the device, a 3-D - 3-D RANSAC over the matches' de
 --loop-closure-keypoint-min-inliers inliers, and from the thumbnail shift's yaw otherwise, so that a revisit from 0.5 m and 12
 degrees away registers; `keypoints_strict` refuses the candidate instead of falling back.  The --loop-closure-keypoint-* values
 set it up; the candidates then gain `init_source`, `init` and `keypoints`, the report's `seconds` the three keypoints_* stages.
-Single scale, pixel-centre corners, thresholds chosen on a synthetic room.
+Pixel-centre corners, thresholds chosen on a synthetic room; single scale unless `--loop-closure-keypoint-levels N` (2 .. 5)
+takes the keypoints from an image pyramid (scales 1, 3/2, 2, 3, 4), so that a revisit from another distance matches.
+`--loop-closure-candidates keypoints` finds the revisits by those keypoints alone - every keyframe pair is matched and its
+filtered matches counted on the device, the --loop-closure-keypoint-shortlist best per keyframe go through the device RANSAC and
+start from its pose - where the thumbnails refuse a view from further away; the report gains `keypoint_search`.
+`--relocalise-search keypoints` shortlists a lost frame's keyframes the same way, `--relocalise-keypoint-levels` sets its pyramid.
 `metric --exposure-aware` also scores every render in the frame's own exposure and white balance (an affine correction per
 channel, fitted on the device): eval_metric/exposure_frame_F_iter_I.csv and exposure_report.json, nothing else changes.
 
@@ -173,7 +178,8 @@ LOOP_CLOSURE_FLAGS = (("min_gap", int, "N", "keyframes between the two ends of a
                       ("odometry_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the odometry edges (default 1 1)"),
                       ("loop_weights", (float, float), ("W_ROT", "W_TRANS"), "weights of the loop edges (default 1 1)"),
                       ("candidates", str, None, "where the candidate pairs come from: the estimated poses (default), the "
-                                                "keyframes' thumbnails (rtg_slam_amd.place_recognition), or both"),
+                                                "keyframes' thumbnails (rtg_slam_amd.place_recognition), both, or the keyframes' "
+                                                "matched keypoints alone (every pair voted on, the best few through the RANSAC)"),
                       ("thumb_width", int, "N", "columns of a keyframe's thumbnail (default 40)"),
                       ("max_shift", int, "N", "thumbnail columns searched to either side, the yaw of the first guess (default 4)"),
                       ("min_score", float, "R", "ZNCC two thumbnails need at their best shift (default 0.9)"),
@@ -188,8 +194,12 @@ LOOP_CLOSURE_FLAGS = (("min_gap", int, "N", "keyframes between the two ends of a
                       ("keypoint_ratio", float, "R", "best distance <= R x second best (default 0.8)"),
                       ("keypoint_ransac_iters", int, "N", "triplets drawn (default 512)"),
                       ("keypoint_inlier_dist", float, "M", "metres a match may miss the hypothesis by (default 0.05)"),
-                      ("keypoint_min_inliers", int, "N", "inliers the keypoint pose needs to be used (default 8)"))
-LOOP_CLOSURE_CHOICES = {"candidates": ("pose", "appearance", "both"), "appearance_init": ("yaw", "keypoints", "keypoints_strict"),
+                      ("keypoint_min_inliers", int, "N", "inliers the keypoint pose needs to be used (default 8)"),
+                      ("keypoint_levels", int, "N", "levels of the image pyramid the keypoints are taken from, 1 .. 5: scales 1, 3/2, "
+                                                    "2, 3, 4 (default 1, single scale)"),
+                      ("keypoint_shortlist", int, "N", "with candidates keypoints: older keyframes per keyframe, most votes first, "
+                                                       "that go through the RANSAC (default 3)"))
+LOOP_CLOSURE_CHOICES = {"candidates": ("pose", "appearance", "both", "keypoints"), "appearance_init": ("yaw", "keypoints", "keypoints_strict"),
                         "keypoint_oriented": ("true", "false")}
 
 
@@ -232,7 +242,8 @@ RELOCALISE_FLAGS = (("candidates", int, "N", "keyframes a lost frame is matched 
                     ("min_inlier_ratio", float, "R", "registration gate (default: loop closure's, 0.3)"),
                     ("max_rms", float, "M", "registration gate, metres (default: loop closure's, 0.02)"),
                     ("max_correction_trans", float, "M", "registration gate, metres (default: loop closure's, 0.2)"),
-                    ("max_correction_rot_deg", float, "DEG", "registration gate, degrees (default: loop closure's, 5)"))
+                    ("max_correction_rot_deg", float, "DEG", "registration gate, degrees (default: loop closure's, 5)"),
+                    ("keypoint_levels", int, "N", "levels of the keypoints' image pyramid, 1 .. 5 (default: loop closure's, 1)"))
 
 
 def _apply_relocalise(args, opts) -> str | None:
@@ -247,6 +258,10 @@ def _apply_relocalise(args, opts) -> str | None:
         if not getattr(args, "relocalise", False):
             return f"--relocalise-{name.replace('_', '-')} needs --relocalise (or relocalise: true in the config)"
         setattr(args, "relocalise_" + name, value)
+    if getattr(opts, "relocalise_search", None) is not None:           # not one of RELOCALISE_FLAGS: no loop closure key behind it
+        if not getattr(args, "relocalise", False):
+            return "--relocalise-search needs --relocalise (or relocalise: true in the config)"
+        args.relocalise_search = opts.relocalise_search
     if not getattr(args, "relocalise", False):
         return None
     try:
@@ -898,6 +913,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "(rtg_slam_amd.relocalisation)")
     for name, typ, meta, text in RELOCALISE_FLAGS:
         s.add_argument("--relocalise-" + name.replace("_", "-"), type=typ, default=None, metavar=meta, help=text)
+    s.add_argument("--relocalise-search", choices=("thumbnails", "keypoints"), default=None,
+                   help="how a lost frame's keyframes are shortlisted: by thumbnail score (default) or by the votes of its keypoints "
+                        "against every keyframe's, for a return at another distance than any keyframe saw")
     s.add_argument("--loop-closure-keypoint-ransac", choices=("host", "device"), default=None,
                    help="where the keypoint pose's match filter and RANSAC run: on the host per candidate (default), or in one "
                         "rtgs_rigid_ransac launch for all candidates")

@@ -8,11 +8,16 @@ tests/keypoint_reference.py): what the reference gets from its ORB back end, in 
     relative_pose         the four together for one pair -> T = T_a^-1 T_b with its count of geometric witnesses, or a refusal
     rigid_ransac_pairs    the filter and the RANSAC of a batch of pairs on the device, ONE launch behind the match launch, the match
                           tables never leaving the device (rtgs_rigid_ransac; the definition is tests/rigid_ransac_reference.py)
+    vote_pairs            the number of filtered matches of a batch of pairs: ONE launch behind the match launch, only the counts
+                          leave the device (rtgs_keypoint_votes)
 
 FAST-9 corners on the 8-bit grey image, one per cell of the image, oriented by the intensity centroid in 32 bins, described by
-256 comparisons of 5 x 5 box sums.  Single scale, pixel-centre localisation, no vocabulary.  After the grey value everything on
-the device is integer arithmetic, so the kernels match the definition bit for bit.  There is no fallback: a CPU tensor or a
-missing kernel is an error."""
+256 comparisons of 5 x 5 box sums.  Pixel-centre localisation, no vocabulary.  Single scale by default; with the option `levels`
+(2 .. 5) the same rule runs on every level of an image pyramid of the scales 1, 3/2, 2, 3, 4 (csrc/keypoint_pyramid.hip; the
+definition is tests/keypoint_pyramid_reference.py), three launches a frame whatever the number of levels, and a keypoint of a
+coarser level is back-projected at the level-0 position of its pixel's centre with that pixel's own depth.  After the grey
+value everything on the device is integer arithmetic, so the kernels match the definition bit for bit.  There is no fallback: a
+CPU tensor or a missing kernel is an error."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -27,6 +32,8 @@ from .keypoint_pattern import PATTERN
 MARGIN = _lib.CONSTANTS["RTGS_KEYPOINT_MARGIN"]
 MIN_CELL, MAX_CELL = _lib.CONSTANTS["RTGS_KEYPOINT_MIN_CELL"], _lib.CONSTANTS["RTGS_KEYPOINT_MAX_CELL"]
 BINS = 32
+MAX_LEVELS = _lib.CONSTANTS["RTGS_KEYPOINT_MAX_LEVELS"]
+SCALES = ((1, 1), (3, 2), (2, 1), (3, 1), (4, 1))                  # num / den of level l; level 3 is level 1 halved, level 4 level 2
 # the loop closure's loop_closure_keypoint_* keys (loop_closure.DEFAULTS takes them from here); chosen on the synthetic textured
 # box room, none measured on real data
 DEFAULTS = {
@@ -43,7 +50,7 @@ DEFAULTS = {
 
 def config(**over) -> SimpleNamespace:
     """The keypoint options as a namespace, validated.  Raises ValueError."""
-    unknown = set(over) - set(DEFAULTS)
+    unknown = set(over) - set(DEFAULTS) - {"levels"}
     if unknown:
         raise ValueError(f"keypoints: unknown option {sorted(unknown)[0]}")
     v = dict(DEFAULTS, **over)
@@ -64,7 +71,28 @@ def config(**over) -> SimpleNamespace:
         raise ValueError("loop_closure_keypoint_inlier_dist must be positive")
     if cfg.min_inliers < 3:
         raise ValueError("loop_closure_keypoint_min_inliers must be >= 3: three pairs define the pose")
+    if "levels" in over:                                            # kept out of DEFAULTS: absent, no namespace and no report knows of it
+        if isinstance(over["levels"], bool) or int(over["levels"]) != over["levels"] or not 1 <= int(over["levels"]) <= MAX_LEVELS:
+            raise ValueError(f"loop_closure_keypoint_levels must be an integer in 1 .. {MAX_LEVELS}")
+        cfg.levels = int(over["levels"])
     return cfg
+
+
+def level_table(H: int, W: int, levels: int, cell: int) -> np.ndarray:
+    """The levels of an H x W frame's pyramid -> int32 [levels used, 5]: first pixel in the packed buffers, H_l, W_l, num, den.
+    Level 1 is level 0 reduced 3:2 (2 floor(n / 3)), levels 2, 3, 4 are levels 0, 1, 2 halved (floor(n / 2)).  Level 0 is always
+    there; a later level whose image cannot hold one cell inside the margin (a side below 2 MARGIN + cell) is dropped, and all
+    after it."""
+    sizes, rows, off = [(int(H), int(W))], [], 0
+    for l in range(1, int(levels)):
+        ph, pw = sizes[0 if l < 3 else l - 2]
+        sizes.append((2 * (ph // 3), 2 * (pw // 3)) if l == 1 else (ph // 2, pw // 2))
+    for l, (h, w) in enumerate(sizes):
+        if l > 0 and min(h, w) < 2 * MARGIN + int(cell):
+            break
+        rows.append((off, h, w) + SCALES[l])
+        off += h * w
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 5)
 
 
 def direction_table() -> np.ndarray:
@@ -111,9 +139,12 @@ def detect_and_describe(color_chw: torch.Tensor, depth_chw: torch.Tensor, K, cfg
     """-> {"x", "y", "score", "bin": int32 numpy [N]; "desc": int32 [N, 8] on the device (the uint32 words' bits); "xyz": float64
     numpy [N, 3], the pixels back-projected with the depth and K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]}, the keypoints in slot
     order.  With keep_planes also "g8" (uint8 [H, W]), "box5" (int32 [H, W]), "slots" (int32 [cells, 4]) and "slot_desc" (int32
-    [cells, 8]) on the device, as the kernels left them.  Two launches and one small copy to the host (the slots)."""
+    [cells, 8]) on the device, as the kernels left them.  Two launches and one small copy to the host (the slots).
+    With cfg.levels above 1 see _detect_and_describe_levels: three launches, and the dict gains "level", "x0", "y0", "levels_used"."""
     cfg = config() if cfg is None else cfg
     H, W = _check_image(color_chw, depth_chw)
+    if getattr(cfg, "levels", 1) > 1:
+        return _detect_and_describe_levels(color_chw, depth_chw, H, W, K, cfg, keep_planes)
     dev = color_chw.device
     c = int(cfg.cell)
     n_slots = (-(-W // c)) * (-(-H // c))
@@ -145,14 +176,73 @@ def detect_and_describe(color_chw: torch.Tensor, depth_chw: torch.Tensor, K, cfg
     return out
 
 
+_geometry: Dict = {}
+
+
+def _level_geometry(H, W, levels, cell, dev):
+    """What depends on the frame's size alone, built once per device: the level table (host), the pixel and slot totals and, on
+    the device, each slot's level, first pixel and row length."""
+    key = (H, W, levels, cell, dev.type, dev.index)
+    if key not in _geometry:
+        table = level_table(H, W, levels, cell)
+        cells = [(-(-int(h) // cell)) * (-(-int(w) // cell)) for _, h, w, _, _ in table]
+        lev = np.repeat(np.arange(len(table)), cells)
+        _geometry[key] = SimpleNamespace(table=np.ascontiguousarray(table), n_pixels=int(table[-1, 0] + table[-1, 1] * table[-1, 2]),
+                                         n_slots=int(sum(cells)), slot_level=torch.from_numpy(lev.astype(np.int64)).to(dev),
+                                         slot_off=torch.from_numpy(table[lev, 0].astype(np.int64)).to(dev),
+                                         slot_w=torch.from_numpy(table[lev, 2].astype(np.int64)).to(dev))
+    return _geometry[key]
+
+
+def _detect_and_describe_levels(color_chw, depth_chw, H, W, K, cfg, keep_planes) -> Dict:
+    """detect_and_describe over cfg.levels levels of the pyramid (level_table): rtgs_keypoint_pyramid, rtgs_keypoint_detect_levels
+    and rtgs_keypoint_describe_levels, three launches whatever the number of levels, and one small copy to the host.  The
+    keypoints are the non-empty slots of level 0 in slot order, then level 1's, and so on; "x", "y" are in the pixels of the
+    keypoint's "level", "x0" = (x + 0.5) s - 0.5 and "y0" (float64, s the level's scale) the position in level 0, at which "xyz" is
+    back-projected with the level depth of the keypoint's own pixel.  "levels_used" counts the levels that were not dropped.
+    With keep_planes the planes are the packed buffers of all levels and "table" the level table."""
+    dev = color_chw.device
+    c = int(cfg.cell)
+    geo = _level_geometry(H, W, int(cfg.levels), c, dev)
+    n, total = len(geo.table), geo.n_pixels
+    color_chw, depth_chw = color_chw.contiguous(), depth_chw.contiguous()
+    g8 = torch.empty((total,), dtype=torch.uint8, device=dev)
+    dl = torch.empty((total,), dtype=torch.float32, device=dev)
+    box = torch.empty((total,), dtype=torch.int32, device=dev)
+    slots = torch.empty((geo.n_slots, 4), dtype=torch.int32, device=dev)
+    slot_desc = torch.empty((geo.n_slots, 8), dtype=torch.int32, device=dev)
+    dirs, tables = _device_tables(dev)
+    lib = _lib.load()
+    levels = geo.table.ctypes.data                                   # a host array: the entry points read it before they launch
+    with torch.cuda.device(dev):
+        rc = lib.rtgs_keypoint_pyramid(_lib.ptr(color_chw), _lib.ptr(depth_chw), levels, n, total, _lib.ptr(g8), _lib.ptr(dl), _lib.stream(dev))
+        _lib.check(rc, "rtgs_keypoint_pyramid")
+        rc = lib.rtgs_keypoint_detect_levels(_lib.ptr(g8), _lib.ptr(dl), levels, n, total, c, int(cfg.threshold), _lib.ptr(box), _lib.ptr(slots),
+                                             _lib.stream(dev))
+        _lib.check(rc, "rtgs_keypoint_detect_levels")
+        rc = lib.rtgs_keypoint_describe_levels(_lib.ptr(g8), _lib.ptr(box), levels, n, total, c, int(bool(cfg.oriented)), _lib.ptr(dirs),
+                                               _lib.ptr(tables), _lib.ptr(slots), _lib.ptr(slot_desc), _lib.stream(dev))
+        _lib.check(rc, "rtgs_keypoint_describe_levels")
+    live = torch.nonzero(slots[:, 2] > 0).reshape(-1)
+    kp = slots[live]
+    z = dl[geo.slot_off[live] + kp[:, 1].long() * geo.slot_w[live] + kp[:, 0].long()]
+    host = torch.cat([kp.to(torch.float64), z.to(torch.float64)[:, None], geo.slot_level[live].to(torch.float64)[:, None]], dim=1).cpu().numpy()
+    Kn = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
+    level = host[:, 5].astype(np.int32)
+    scale = np.array([num / den for num, den in SCALES], dtype=np.float64)[level]
+    x0, y0, zz = (host[:, 0] + 0.5) * scale - 0.5, (host[:, 1] + 0.5) * scale - 0.5, host[:, 4]
+    out = {"x": host[:, 0].astype(np.int32), "y": host[:, 1].astype(np.int32), "score": host[:, 2].astype(np.int32),
+           "bin": host[:, 3].astype(np.int32), "desc": slot_desc[live].contiguous(), "level": level, "x0": x0, "y0": y0,
+           "levels_used": n, "xyz": np.stack([(x0 - Kn[0, 2]) / Kn[0, 0] * zz, (y0 - Kn[1, 2]) / Kn[1, 1] * zz, zz], axis=1)}
+    if keep_planes:
+        out.update(g8=g8, depth_levels=dl, box5=box, slots=slots, slot_desc=slot_desc, table=geo.table.copy())
+    return out
+
+
 def _match_launch(features, pairs):
     """The launch of match_pairs -> (out int32 [n_out, 3] on the device, or None when there is no query at all; table: per pair
     (first query row, query count, first reference row, reference count, first row of out))."""
-    keys = []
-    for q, r in pairs:
-        for k in (q, r):
-            if k not in keys:
-                keys.append(k)
+    keys = list(dict.fromkeys(k for pair in pairs for k in pair))   # in order of first appearance
     descs = [features[k]["desc"] for k in keys]
     for d in descs:
         if not (torch.is_tensor(d) and d.is_cuda and d.dtype == torch.int32 and d.dim() == 2 and d.shape[1] == 8
@@ -383,11 +473,7 @@ def rigid_ransac_pairs(features, pairs: Sequence[Tuple], cfg=None, seed: int = 0
         torch.cuda.synchronize(features[pairs[0][0]]["desc"].device)
         seconds["match"] = time.perf_counter() - t0
         t0 = time.perf_counter()
-    keys = []
-    for a, b in pairs:
-        for k in (a, b):
-            if k not in keys:
-                keys.append(k)
+    keys = list(dict.fromkeys(k for pair in pairs for k in pair))   # in order of first appearance
     dev = features[keys[0]]["desc"].device
     begin, total = {}, 0
     for k in keys:
@@ -409,3 +495,49 @@ def rigid_ransac_pairs(features, pairs: Sequence[Tuple], cfg=None, seed: int = 0
             out["T"] = fit["T"]
         res.append(out)
     return res
+
+
+def keypoint_votes(matches, table, dev, max_hamming: int = 64, ratio: float = 0.8) -> torch.Tensor:
+    """rtgs_keypoint_votes (include/rtgs_slam.h; the definition is tests/keypoint_pyramid_reference.votes): matches int32 [n, 3] on
+    the device `dev` (None for none), table [(first row and count nb of b's matches against a, first row and count na of a's
+    against b)] on the host -> int32 [pairs] on the device: per pair the rows that survive rigid_ransac_tables' filter, not
+    capped.  One launch, nothing read."""
+    table = np.asarray(table, dtype=np.int32).reshape(-1, 4)
+    if matches is not None and not (torch.is_tensor(matches) and matches.is_cuda and matches.device == dev and matches.dtype == torch.int32
+                                    and matches.dim() == 2 and matches.shape[1] == 3 and matches.is_contiguous()):
+        raise ValueError("keypoint_votes: matches must be a contiguous int32 [N, 3] tensor on the device")
+    votes = torch.zeros((len(table),), dtype=torch.int32, device=dev)
+    if len(table) == 0:
+        return votes
+    tab = torch.from_numpy(table).to(dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().rtgs_keypoint_votes(_lib.ptr0(matches), 0 if matches is None else int(matches.shape[0]), _lib.ptr(tab), len(table),
+                                             int(max_hamming), float(ratio), _lib.ptr(votes), _lib.stream(dev))
+    _lib.check(rc, "rtgs_keypoint_votes")
+    return votes
+
+
+MAX_VOTE_PAIRS = 65535 // 2                                          # a match launch takes 65535 tables, a pair needs two
+
+
+def vote_pairs(features, pairs: Sequence[Tuple], cfg=None) -> np.ndarray:
+    """features: keyframe key -> detect_and_describe's dict; pairs: [(a, b)], at most MAX_VOTE_PAIRS -> int32 numpy [pairs]: how
+    many matches of each pair survive the filter (mutual best, Hamming bound, ratio test).  One match launch (both directions of
+    every pair) and one rtgs_keypoint_votes launch; the match tables stay on the device, only the counts are read."""
+    cfg = config() if cfg is None else cfg
+    pairs = list(pairs)
+    if not pairs:
+        return np.zeros((0,), dtype=np.int32)
+    if len(pairs) > MAX_VOTE_PAIRS:
+        raise ValueError(f"vote_pairs: at most {MAX_VOTE_PAIRS} pairs a launch")
+    matches, where = match_pairs_device(features, [q for a, b in pairs for q in ((b, a), (a, b))])
+    dev = features[pairs[0][0]]["desc"].device
+    table = [(where[2 * n][0], where[2 * n][1], where[2 * n + 1][0], where[2 * n + 1][1]) for n in range(len(pairs))]
+    return keypoint_votes(matches, table, dev, cfg.max_hamming, cfg.ratio).cpu().numpy()
+
+
+def shortlist(votes, k: int, floor: int) -> List[int]:
+    """votes[a] of one keyframe's partners a = 0 .. -> the up to k partners of the most votes that reach `floor`, a tie going to
+    the lower index; in order of descending votes."""
+    order = sorted((a for a, v in enumerate(votes) if v >= floor), key=lambda a: (-int(votes[a]), a))
+    return order[:int(k)]

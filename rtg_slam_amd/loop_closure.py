@@ -24,7 +24,13 @@ loop_closure_appearance_init "keypoints" lifts that last limit: every appearance
 keypoints.py computes from the two frames alone (corners, binary descriptors, a 3-D - 3-D RANSAC over their depth) when it has
 loop_closure_keypoint_min_inliers geometric witnesses, and the yaw guess otherwise; "keypoints_strict" refuses the candidate
 instead of falling back.  register_pair and its gates stay what they are - the correction gate then measures what it was meant
-to: how far the dense registration moved a guess that was already a measurement."""
+to: how far the dense registration moved a guess that was already a measurement.
+
+Thumbnails and single-scale keypoints both miss a revisit seen from another distance (the thumbnails' depth witness refuses a
+view more than about 10 % further away by construction).  loop_closure_keypoint_levels takes the keypoints from an image pyramid
+instead, and loop_closure_candidates "keypoints" finds the revisits by those keypoints alone (LoopCloser._keypoint_search): the
+count of filtered matches ranks the older keyframes, the device RANSAC judges the best few, register_pair and its gates stay
+what they are.  Every pair of keyframes is matched, so the search costs O(keyframes^2) match work; there is no vocabulary."""
 from __future__ import annotations
 
 import time
@@ -62,8 +68,17 @@ DEFAULTS = {
     "loop_closure_appearance_init": "yaw",
     **{"loop_closure_keypoint_" + k: v for k, v in kp.DEFAULTS.items()},
 }
-CANDIDATE_SOURCES = ("pose", "appearance", "both")
+CANDIDATE_SOURCES = ("pose", "appearance", "both", "keypoints")
 APPEARANCE_INITS = ("yaw", "keypoints", "keypoints_strict")
+# loop_closure_keypoint_levels (1 .. 5, absent = 1): the levels of the image pyramid the keypoints are taken from (keypoints.py).
+# loop_closure_candidates "keypoints": the revisits are found by the keyframes' keypoints alone - every pair min_gap apart is
+# matched and its filtered matches counted on the device (the votes), the loop_closure_keypoint_shortlist older keyframes with
+# the most votes per keyframe go through the device RANSAC, and those with min_inliers witnesses become candidates that start
+# from the RANSAC pose.  It implies appearance_init keypoints_strict and keypoint_ransac device.  Both keys are kept out of
+# DEFAULTS: absent, no report and no launch knows of them
+KEYPOINT_SHORTLIST = 3
+# the match tables of one chunk of the keypoint search (12 bytes a row, both directions of every pair) stay below this
+KEYPOINT_SEARCH_TABLE_BYTES = 64 << 20
 # loop_closure_keypoint_ransac: where the match filter and the RANSAC of the keypoint pose run.  "host" (the default, also when
 # the key is absent) is keypoints.pose_from_matches per candidate; "device" is one rtgs_rigid_ransac launch for all candidates
 # (keypoints.rigid_ransac_pairs).  Kept out of DEFAULTS: absent or "host", no report and no launch knows of it
@@ -252,13 +267,27 @@ class LoopCloser:
         if not pl.max_depth_rel >= 0:
             raise ValueError("loop_closure_max_depth_rel must not be negative")
         # kept apart as well: absent or "yaw", nothing of it reaches a report
+        levels = {"levels": args.loop_closure_keypoint_levels} if hasattr(args, "loop_closure_keypoint_levels") else {}
         self.keypoints = SimpleNamespace(init=str(get("loop_closure_appearance_init")),
-                                         cfg=kp.config(**{k: get("loop_closure_keypoint_" + k) for k in kp.DEFAULTS}))
+                                         cfg=kp.config(**{k: get("loop_closure_keypoint_" + k) for k in kp.DEFAULTS}, **levels))
         if self.keypoints.init not in APPEARANCE_INITS:
             raise ValueError(f"loop_closure_appearance_init must be one of {', '.join(APPEARANCE_INITS)}")
         self.keypoints.ransac = str(getattr(args, "loop_closure_keypoint_ransac", "host"))
         if self.keypoints.ransac not in KEYPOINT_RANSACS:
             raise ValueError(f"loop_closure_keypoint_ransac must be one of {', '.join(KEYPOINT_RANSACS)}")
+        if pl.candidates == "keypoints":
+            if hasattr(args, "loop_closure_appearance_init") and self.keypoints.init != "keypoints_strict":
+                raise ValueError("loop_closure_candidates keypoints starts every candidate from its keypoint pose: "
+                                 "loop_closure_appearance_init can only be keypoints_strict with it")
+            if hasattr(args, "loop_closure_keypoint_ransac") and self.keypoints.ransac != "device":
+                raise ValueError("loop_closure_candidates keypoints runs the RANSAC on the device: loop_closure_keypoint_ransac "
+                                 "can only be device with it")
+            self.keypoints.init, self.keypoints.ransac = "keypoints_strict", "device"
+            self.keypoints.shortlist = int(getattr(args, "loop_closure_keypoint_shortlist", KEYPOINT_SHORTLIST))
+            if self.keypoints.shortlist < 1:
+                raise ValueError("loop_closure_keypoint_shortlist must be >= 1")
+        elif hasattr(args, "loop_closure_keypoint_shortlist"):
+            raise ValueError("loop_closure_keypoint_shortlist applies to the keypoint search: it needs loop_closure_candidates keypoints")
         if self.keypoints.ransac == "device" and self.keypoints.init == "yaw":
             raise ValueError("loop_closure_keypoint_ransac applies to the keypoint pose: it needs loop_closure_appearance_init "
                              "keypoints or keypoints_strict")
@@ -358,6 +387,71 @@ class LoopCloser:
             rep["appearance"]["keypoint_ransac"] = "device"
         rep["seconds"].update(keypoints_describe=t1 - t0, keypoints_match=t2 - t1, keypoints_ransac=time.perf_counter() - t2)
 
+    def _keypoint_search(self, mapper, old, rep) -> List[Tuple]:
+        """loop_closure_candidates "keypoints": the revisits found by the keyframes' keypoints alone, as (a, b, metres, degrees
+        between the ESTIMATED poses, {"init", "init_source", "votes", "keypoints"}).
+          1. the features of every keyframe (three launches each above one level, two at one)
+          2. every pair a <= b - min_gap matched in both directions and voted on, in chunks of whole rows of b: a chunk holds at
+             most keypoints.MAX_VOTE_PAIRS pairs and KEYPOINT_SEARCH_TABLE_BYTES of match tables; one match launch and one vote
+             launch a chunk, only the votes read
+          3. per keyframe b the `shortlist` older keyframes of the most votes, at least min_inliers of them (a pair with fewer
+             filtered matches cannot have min_inliers inliers) and ties to the older keyframe, all in ONE rigid_ransac_pairs
+          4. per b the max_per_keyframe of the most inliers that reach min_inliers, ties to the older keyframe
+        Fills rep["keypoint_search"]."""
+        cfg, kc, dev = self.cfg, self.keypoints.cfg, mapper.device
+        K = mapper.keyframe_list[0].K
+        M = len(mapper.keymap_list)
+        clock = lambda: (torch.cuda.synchronize(dev), time.perf_counter())[1]
+        t0 = clock()
+        feats = [kp.detect_and_describe(km["color_chw"], km["depth_chw"], K, kc) for km in mapper.keymap_list]
+        t1 = clock()
+        counts = [int(f["desc"].shape[0]) for f in feats]
+        votes = {}                                                       # b -> int32 [b - min_gap + 1]
+        chunk, rows, chunks, voted = [], 0, 0, 0
+
+        def flush():
+            nonlocal chunk, rows, chunks, voted
+            if chunk:
+                got = kp.vote_pairs(feats, chunk, kc)
+                at = 0
+                for b in sorted({b for _, b in chunk}):
+                    n = b - cfg.min_gap + 1
+                    votes[b] = got[at:at + n]
+                    at += n
+                chunks, voted = chunks + 1, voted + len(chunk)
+            chunk, rows = [], 0
+
+        for b in range(cfg.min_gap, M):
+            n = b - cfg.min_gap + 1
+            if n > kp.MAX_VOTE_PAIRS:
+                raise RuntimeError(f"loop_closure_candidates keypoints: more than {kp.MAX_VOTE_PAIRS + cfg.min_gap - 1} keyframes")
+            need = n * counts[b] + sum(counts[:n])                       # rows of the two tables of b's pairs
+            if chunk and (len(chunk) + n > kp.MAX_VOTE_PAIRS or 12 * (rows + need) > KEYPOINT_SEARCH_TABLE_BYTES):
+                flush()
+            chunk += [(a, b) for a in range(n)]
+            rows += need
+        flush()
+        t2 = clock()
+        short = [(a, b) for b in sorted(votes) for a in kp.shortlist(votes[b], self.keypoints.shortlist, kc.min_inliers)]
+        fits = []
+        for at in range(0, len(short), kp.MAX_VOTE_PAIRS):               # one launch unless there are more than 32 767 pairs
+            fits += kp.rigid_ransac_pairs(feats, short[at:at + kp.MAX_VOTE_PAIRS], kc)
+        t3 = clock()
+        out = []
+        for b in sorted(votes):
+            mine = sorted((-fit["inliers"], a, fit) for (a, bb), fit in zip(short, fits) if bb == b and fit["T"] is not None)
+            for _, a, fit in mine[:cfg.max_per_keyframe]:
+                rel_pose = pose_graph.inverse(old[a]) @ old[b]
+                out.append((a, b, float(np.linalg.norm(old[a][:3, 3] - old[b][:3, 3])), _angle_deg(rel_pose[:3, :3]),
+                            {"init": fit["T"], "init_source": "keypoints", "source": "keypoints", "votes": int(votes[b][a]),
+                             "keypoints": {"a": fit["keypoints_a"], "b": fit["keypoints_b"], "matches": fit["matches"],
+                                           "inliers": fit["inliers"], "rms_m": fit["rms"]}}))
+        rep["keypoint_search"] = {"pairs_voted": voted, "shortlisted": len(short), "candidates": len(out), "levels": int(getattr(kc, "levels", 1)),
+                                  "levels_used": max((int(f.get("levels_used", 1)) for f in feats), default=1), "chunks": chunks,
+                                  "shortlist": self.keypoints.shortlist, **{"keypoint_" + k: v for k, v in vars(kc).items()},
+                                  "seconds": {"features": t1 - t0, "votes": t2 - t1, "ransac": t3 - t2}}
+        return out
+
     def close(self, mapper, tracker) -> Dict:
         """-> the report (JSON-able).  Without an accepted edge nothing is changed: poses, keyframes and map stay bit-identical."""
         from . import slam_ops
@@ -377,10 +471,12 @@ class LoopCloser:
         gt = tracker.pose_gt if len(tracker.pose_gt) == n else None
         old = [np.array(tracker.pose_es[i], dtype=np.float64) for i in ids]
         mode = self.place.candidates
-        cands = [] if mode == "appearance" else [
+        cands = [] if mode in ("appearance", "keypoints") else [
             (a, b, dist, ang, None) for a, b, dist, ang in
             find_candidates(old, ids, cfg.min_gap, cfg.max_trans, cfg.max_rot_deg, cfg.max_per_keyframe)]
-        if mode != "pose":
+        if mode == "keypoints":
+            cands += self._keypoint_search(mapper, old, rep)
+        elif mode != "pose":
             cands += self._appearance_candidates(mapper, old, {(a, b) for a, b, *_ in cands}, rep)
         t1 = time.perf_counter()
         K = mapper.keyframe_list[0].K
@@ -396,7 +492,7 @@ class LoopCloser:
             Z = r.pop("Z")
             r.update(a=a, b=b, frame_a=ids[a], frame_b=ids[b], distance_m=dist, angle_deg=ang)
             if mode != "pose":
-                r["source"] = "pose" if seen is None else "appearance"
+                r["source"] = "pose" if seen is None else seen.pop("source", "appearance")
                 r.update(seen or {})
                 r["Z"] = None if Z is None else np.asarray(Z).tolist()        # the measured T_a^-1 T_b, whatever became of it
                 if seen is not None and self.keypoints.init != "yaw":

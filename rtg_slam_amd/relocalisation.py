@@ -22,7 +22,15 @@ The keys, read with getattr, default to the run's loop_closure_* values and thos
 registration's gates relocalise_min_inlier_ratio, relocalise_max_rms, relocalise_max_correction_trans,
 relocalise_max_correction_rot_deg.  The keypoint options other than min_inliers are the run's loop_closure_keypoint_*.  One rank
 only; not with use_gt_pose; not built for rtg_slam_amd.pipeline.  Not built either: relocalising against the map's render
-instead of the keyframes, a motion model for the frames while lost, several ranks."""
+instead of the keyframes, a motion model for the frames while lost, several ranks.
+
+relocalise_search "keypoints" (absent: "thumbnails") replaces steps 1 and 2, for a camera that comes back at another distance
+than any keyframe saw the place from - the thumbnails' depth witness refuses such a view by construction.  Every keyframe's
+keypoints are computed when it is made (on_keyframes); a lost frame's are matched against ALL keyframes in one match launch, one
+rtgs_keypoint_votes launch counts each keyframe's filtered matches, and the relocalise_candidates keyframes of the most votes, at
+least relocalise_min_inliers of them, go to step 3's RANSAC.  No thumbnail is made.  relocalise_keypoint_levels (default: the
+run's loop_closure_keypoint_levels, else 1) takes the keypoints from an image pyramid, which is what lets views from different
+distances match at all (keypoints.py)."""
 from __future__ import annotations
 
 import re
@@ -43,8 +51,11 @@ KEYS = {"relocalise_min_score": "loop_closure_min_score", "relocalise_max_depth_
         "relocalise_thumb_width": "loop_closure_thumb_width", "relocalise_max_shift": "loop_closure_max_shift",
         "relocalise_min_inliers": "loop_closure_keypoint_min_inliers", "relocalise_min_inlier_ratio": "loop_closure_min_inlier_ratio",
         "relocalise_max_rms": "loop_closure_max_rms", "relocalise_max_correction_trans": "loop_closure_max_correction_trans",
-        "relocalise_max_correction_rot_deg": "loop_closure_max_correction_rot_deg"}
+        "relocalise_max_correction_rot_deg": "loop_closure_max_correction_rot_deg",
+        "relocalise_keypoint_levels": "loop_closure_keypoint_levels"}
 STAGES = ("describe", "scores", "keypoints", "match", "ransac", "registration")
+SEARCHES = ("thumbnails", "keypoints")
+KEYPOINT_STAGES = ("keypoints", "votes", "match", "ransac", "registration")       # of relocalise_search keypoints
 FIRST_ROWS = 256
 
 
@@ -69,6 +80,8 @@ class Relocaliser:
                 setattr(mine, theirs, getattr(args, key))
         mine.loop_closure_candidates, mine.loop_closure_appearance_init = "appearance", "keypoints_strict"
         mine.loop_closure_keypoint_ransac = "device"
+        if hasattr(mine, "loop_closure_keypoint_shortlist"):            # the run's keypoint search has its own shortlist
+            del mine.loop_closure_keypoint_shortlist
         try:
             closer = LoopCloser(mine)
         except ValueError as e:
@@ -80,6 +93,10 @@ class Relocaliser:
         self.candidates = int(getattr(args, "relocalise_candidates", DEFAULT_CANDIDATES))
         if self.candidates < 1:
             raise ValueError("relocalise_candidates must be >= 1")
+        self.search = str(getattr(args, "relocalise_search", "thumbnails"))
+        if self.search not in SEARCHES:
+            raise ValueError(f"relocalise_search must be one of {', '.join(SEARCHES)}")
+        self.search_given = hasattr(args, "relocalise_search")
         self.closer, self.cfg, self.place, self.kc = closer, closer.cfg, closer.place, closer.keypoints.cfg
         self.mapper = None
         self.desc: Optional[Dict] = None
@@ -89,9 +106,13 @@ class Relocaliser:
         self.lost_at: Optional[int] = None
         self.attempts = 0
         self.events, self.refusals, self.last_refusal = [], {}, None
-        self.seconds = {k: 0.0 for k in STAGES}
+        self.seconds = {k: 0.0 for k in (KEYPOINT_STAGES if self.search == "keypoints" else STAGES)}
 
     def options(self) -> Dict:
+        return {**self._options(), **({"search": self.search} if self.search_given else {}),
+                **({"keypoint_levels": self.kc.levels} if hasattr(self.kc, "levels") else {})}
+
+    def _options(self) -> Dict:
         return {"candidates": self.candidates, "min_score": self.place.min_score, "max_depth_rel": self.place.max_depth_rel,
                 "thumb_width": self.place.thumb_width, "max_shift": self.place.max_shift, "min_inliers": self.kc.min_inliers,
                 "min_inlier_ratio": self.cfg.min_inlier_ratio, "max_rms": self.cfg.max_rms,
@@ -118,8 +139,16 @@ class Relocaliser:
                 self.desc[k] = new
 
     def on_keyframes(self, mapper) -> None:
-        """After a frame was mapped: one rtgs_place_describe per keyframe not described yet."""
+        """After a frame was mapped: one rtgs_place_describe per keyframe not described yet - or, with relocalise_search
+        keypoints, its keypoints."""
         t0 = time.perf_counter()
+        while self.search == "keypoints" and self.M < len(mapper.keymap_list):
+            km = mapper.keymap_list[self.M]
+            self.features[self.M] = kp.detect_and_describe(km["color_chw"], km["depth_chw"], mapper.keyframe_list[0].K, self.kc)
+            self.M += 1
+        if self.search == "keypoints":
+            self.seconds["keypoints"] += time.perf_counter() - t0
+            return
         while self.M < len(mapper.keymap_list):
             km = mapper.keymap_list[self.M]
             self._rows(km, self.M + 2)                               # the keyframes and the row of a lost frame
@@ -141,6 +170,8 @@ class Relocaliser:
         if M == 0:
             return self._refuse("no keyframe")
         clock = lambda: (torch.cuda.synchronize(dev), time.perf_counter())[1]
+        if self.search == "keypoints":
+            return self._locate_by_votes(tracker, frame_map, frame_id, clock)
         t0 = clock()
         self._rows(frame_map, M + 1)
         pr.describe(frame_map["color_chw"], frame_map["depth_chw"], self.place.thumb_width, out=self.desc, row=M)
@@ -168,12 +199,38 @@ class Relocaliser:
         sec["keypoints"] += t3 - t2
         if len(feats["frame"]["x"]) == 0 or all(len(feats[a]["x"]) == 0 for _, _, a in hits):
             return self._refuse("no keypoints")
+        found = {a: {"score": -msc, "shift": int(row[1, a]), "depth_rel": dr} for msc, dr, a in hits}
+        return self._fit_and_register(tracker, frame_map, frame_id, feats, [a for _, _, a in hits], found, clock)
+
+    def _locate_by_votes(self, tracker, frame_map, frame_id, clock):
+        """relocalise_search keypoints: the shortlist from the votes of ALL keyframes - one match launch, one vote launch, the
+        votes read - then what `locate` does from its RANSAC on."""
+        mapper, sec, M = self.mapper, self.seconds, self.M
+        t0 = clock()
+        feats = dict(self.features)
+        feats["frame"] = kp.detect_and_describe(frame_map["color_chw"], frame_map["depth_chw"], mapper.keyframe_list[0].K, self.kc)
+        t1 = clock()
+        sec["keypoints"] += t1 - t0
+        if len(feats["frame"]["x"]) == 0 or all(len(feats[a]["x"]) == 0 for a in range(M)):
+            return self._refuse("no keypoints")
+        votes = np.concatenate([kp.vote_pairs(feats, [(a, "frame") for a in range(at, min(M, at + kp.MAX_VOTE_PAIRS))], self.kc)
+                                for at in range(0, M, kp.MAX_VOTE_PAIRS)])      # one launch pair below 32 768 keyframes
+        sec["votes"] += time.perf_counter() - t1
+        hits = kp.shortlist(votes, self.candidates, self.kc.min_inliers)
+        if not hits:
+            return self._refuse("no keyframe above the votes", f"no keyframe above the votes: the best of {M} has {int(votes.max())}, below {self.kc.min_inliers}")
+        return self._fit_and_register(tracker, frame_map, frame_id, feats, hits, {a: {"votes": int(votes[a])} for a in hits}, clock)
+
+    def _fit_and_register(self, tracker, frame_map, frame_id, feats, hits, found, clock):
+        """Steps 3 to 6 of `locate` for the shortlisted keyframes `hits`, best first; found[a] is what the search knows of a."""
+        mapper, sec = self.mapper, self.seconds
+        K = mapper.keyframe_list[0].K
         stage = {}
-        fits = kp.rigid_ransac_pairs(feats, [(a, "frame") for _, _, a in hits], self.kc, seconds=stage)
+        fits = kp.rigid_ransac_pairs(feats, [(a, "frame") for a in hits], self.kc, seconds=stage)
         sec["match"] += stage["match"]
         sec["ransac"] += stage["ransac"]
         best = max(range(len(hits)), key=lambda k: (fits[k]["inliers"], -k))
-        fit, (msc, dr, a) = fits[best], hits[best]
+        fit, a = fits[best], hits[best]
         if fit["T"] is None:
             return self._refuse("too few inliers", fit["reason"])
         t4 = time.perf_counter()
@@ -185,7 +242,7 @@ class Relocaliser:
             return self._refuse("registration: " + re.sub(r"-?\d+(\.\d+)?", "#", r["reason"]), "registration: " + r["reason"])
         T_kf = np.asarray(tracker.pose_es[int(mapper.keyframe_ids[a])], dtype=np.float64)
         self.events.append({"lost_at": self.lost_at, "recovered_at": int(frame_id), "keyframe": int(a), "keyframe_frame": int(mapper.keyframe_ids[a]),
-                            "score": -msc, "shift": int(row[1, a]), "depth_rel": dr, "matches": fit["matches"], "inliers": fit["inliers"],
+                            **found[a], "matches": fit["matches"], "inliers": fit["inliers"],
                             "rms_m": fit["rms"], "correction_trans": r["correction_trans"], "correction_rot_deg": r["correction_rot_deg"],
                             "inlier_ratio": r["inlier_ratio"], "rms_geometric_after": r["rms_geometric_after"],
                             "Z": np.asarray(r["Z"]).tolist()})

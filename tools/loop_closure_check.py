@@ -211,7 +211,7 @@ def time_keypoint_kernels(dev):
     return out
 
 
-def sequence(dev, frames, mode=None, texture=False, init=None):
+def sequence(dev, frames, mode=None, texture=False, init=None, levels=None):
     import numpy as np
     import torch
     from rtg_slam_amd import mapping as mp, slam, synth
@@ -227,7 +227,8 @@ def sequence(dev, frames, mode=None, texture=False, init=None):
 
     slam.run_sequence(cam, stream(30), mp.replica_args(seed=1), dev, capacity=800_000)         # warm-up, thrown away
     args = mp.replica_args(seed=1, loop_closure=True, **({} if mode is None else {"loop_closure_candidates": mode}),
-                           **({} if init is None else {"loop_closure_appearance_init": init}))
+                           **({} if init is None else {"loop_closure_appearance_init": init}),
+                           **({} if levels is None else {"loop_closure_keypoint_levels": levels}))
     mapper, tracker, rep = slam.run_sequence(cam, stream(frames), args, dev, capacity=800_000)
     lcr = rep["loop_closure"]
     reasons = {}
@@ -245,9 +246,11 @@ def sequence(dev, frames, mode=None, texture=False, init=None):
     if mode is not None:
         from rtg_slam_amd import pose_graph as pg
         out["mode"], out["appearance"] = mode, lcr.get("appearance")
+        if "keypoint_search" in lcr:                              # candidates keypoints: pairs voted, shortlisted, seconds per stage
+            out["keypoint_search"] = lcr["keypoint_search"]
         ids = [int(i) for i in mapper.keyframe_ids]
         for row, c in zip(out["candidate_list"], lcr["candidates"]):
-            row.update({k: c[k] for k in ("source", "score", "shift", "depth_rel", "init_source", "keypoints") if k in c})
+            row.update({k: c[k] for k in ("source", "score", "shift", "depth_rel", "init_source", "keypoints", "votes") if k in c})
             want = pg.inverse(np.asarray(tracker.pose_gt[ids[c["a"]]], dtype=np.float64)) @ np.asarray(tracker.pose_gt[ids[c["b"]]])
             row["true_angle_deg"] = float(np.rad2deg(np.arccos(min(1.0, max(-1.0, (np.trace(want[:3, :3]) - 1.0) / 2.0)))))
             row["true_distance_m"] = float(np.linalg.norm(want[:3, 3]))
@@ -256,7 +259,8 @@ def sequence(dev, frames, mode=None, texture=False, init=None):
                 row["init_error_m"] = float(np.linalg.norm(np.asarray(c["init"])[:3, 3] - want[:3, 3]))
         out["by_source"] = {s: {"candidates": sum(r.get("source", "pose") == s for r in out["candidate_list"]),
                                 "accepted": sum(r.get("source", "pose") == s and r["accepted"] for r in out["candidate_list"])}
-                            for s in ("pose", "appearance")}
+                            for s in ("pose", "appearance", "keypoints")}
+        out["wrong_edges"] = [(r["a"], r["b"]) for r in out["candidate_list"] if r["accepted"] and r["z_error_m"] is not None and r["z_error_m"] > 0.05]
     if "graph" in lcr:
         g = lcr["graph"]
         out["graph"] = {k: g[k] for k in ("cost_before", "cost_after", "iterations", "accepted", "last_update", "reason")}
@@ -266,6 +270,7 @@ def sequence(dev, frames, mode=None, texture=False, init=None):
                    "replica_args(seed=1, loop_closure=True) from an empty map, ICP tracking, every loop_closure_* value at its default"
                    + ("" if mode is None else f" but loop_closure_candidates = {mode}")
                    + ("" if init is None else f" and loop_closure_appearance_init = {init}")
+                   + ("" if levels is None else f" and loop_closure_keypoint_levels = {levels}")
                    + (", in the textured room (synth.box_room_texture_color)" if texture else ""))
     print({k: v for k, v in out.items() if k != "candidate_list"}, flush=True)
     return out
@@ -278,12 +283,15 @@ def main():
     ap.add_argument("--ab-runs", type=int, default=3)
     ap.add_argument("--appearance", action="store_true", help="measure the place recognition instead (r27_place_recognition.json)")
     ap.add_argument("--keypoints", action="store_true", help="measure the keypoint registration instead (r28_keypoints.json)")
+    ap.add_argument("--keypoint-search", action="store_true",
+                    help="run the textured sequence with loop_closure_candidates keypoints at --levels levels (r30_keypoint_pyramid_tour.json)")
+    ap.add_argument("--levels", type=int, default=3)
     ap.add_argument("--texture", action="store_true", help="run the sequence in the textured room (always so with --keypoints)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--parts", default="kernels,sequence", help="what to measure now; an existing --out file keeps its other parts")
     opts = ap.parse_args()
     parts = set(opts.parts.split(","))
-    opts.out = opts.out or os.path.join(ROOT, "profiles", "r28_keypoints.json" if opts.keypoints else
+    opts.out = opts.out or os.path.join(ROOT, "profiles", "r30_keypoint_pyramid_tour.json" if opts.keypoint_search else "r28_keypoints.json" if opts.keypoints else
                                         "r27_place_recognition.json" if opts.appearance else "r26_loop_closure.json")
     result = json.load(open(opts.out)) if os.path.exists(opts.out) else {}
     if opts.parent_tree:                                      # first: this process has not opened the GPU yet
@@ -293,6 +301,9 @@ def main():
         raise SystemExit("loop_closure_check.py needs a GPU; nothing was measured")
     dev = torch.device("cuda", 0)
     result["device"] = torch.cuda.get_device_name(dev)
+    if opts.keypoint_search:                                  # its kernels are timed by tools/keypoint_pyramid_check.py
+        result["sequence"] = sequence(dev, opts.frames, "keypoints", True, levels=opts.levels)
+        parts = set()
     if "kernels" in parts:
         result["kernels"] = (time_keypoint_kernels(dev) if opts.keypoints else time_place_kernels(dev) if opts.appearance
                              else time_kernels(dev))

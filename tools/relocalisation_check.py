@@ -99,7 +99,7 @@ def time_kernels(dev):
     return rows
 
 
-def time_locate(dev):
+def time_locate(dev, search=None, levels=None):
     import numpy as np
     import torch
     from types import SimpleNamespace
@@ -115,7 +115,8 @@ def time_locate(dev):
             keymaps.append({"color_chw": synth.box_room_texture_color(cam, c2w, d).contiguous(), "depth_chw": d.reshape(1, cam.H, cam.W).contiguous()})
         mapper = SimpleNamespace(keymap_list=keymaps, keyframe_list=[mp.Frame(cam, poses[0].numpy(), dev)], keyframe_ids=list(range(M)))
         tracker = SimpleNamespace(pose_es=[p.numpy().astype(np.float64) for p in poses])
-        r = rl.Relocaliser(mp.replica_args(seed=1, relocalise=True))
+        r = rl.Relocaliser(mp.replica_args(seed=1, relocalise=True, **({} if search is None else {"relocalise_search": search}),
+                                            **({} if levels is None else {"relocalise_keypoint_levels": levels})))
         r.mapper = mapper
         r.on_keyframes(mapper)
         a = M // 2
@@ -130,11 +131,11 @@ def time_locate(dev):
             pose = r.locate(tracker, fm, M + k)
             torch.cuda.synchronize(dev)
             total = time.perf_counter() - t0
-            calls.append(dict({s: 1e3 * (r.seconds[s] - before[s]) for s in rl.STAGES}, total=1e3 * total))
+            calls.append(dict({s: 1e3 * (r.seconds[s] - before[s]) for s in r.seconds}, total=1e3 * total))
         ev = r.events[-1] if r.events else None
         row = {"keyframes": M, "image": [cam.W, cam.H], "recovered": pose is not None, "refusals": dict(r.refusals),
                "error_mm": None if pose is None else 1e3 * float(np.linalg.norm(pose[:3, 3] - truth[:3, 3])),
-               "event": None if ev is None else {k: ev[k] for k in ("keyframe", "score", "matches", "inliers", "correction_trans")},
+               "event": None if ev is None else {k: ev[k] for k in ("keyframe", "score", "votes", "matches", "inliers", "correction_trans") if k in ev},
                "first_call_ms": {k: round(v, 3) for k, v in calls[0].items()},
                "later_calls_ms_median": {k: round(statistics.median(c[k] for c in calls[1:]), 3) for k in calls[0]},
                "later_calls_ms_max": {k: round(max(c[k] for c in calls[1:]), 3) for k in calls[0]},
@@ -192,6 +193,8 @@ def main():
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--ab-runs", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r29_relocalisation.json"))
+    ap.add_argument("--search", choices=("thumbnails", "keypoints"), default=None, help="relocalise_search of the locate part")
+    ap.add_argument("--levels", type=int, default=None, help="relocalise_keypoint_levels of the locate part")
     ap.add_argument("--parts", default="kernels,locate,tour", help="what to measure now; an existing --out file keeps its other parts")
     opts = ap.parse_args()
     parts = set(opts.parts.split(","))
@@ -206,7 +209,8 @@ def main():
     if "kernels" in parts:
         result["kernels"] = time_kernels(dev)
     if "locate" in parts:
-        result["locate"] = time_locate(dev)
+        key = "locate" if opts.search is None and opts.levels is None else f"locate_{opts.search or 'thumbnails'}_levels_{opts.levels or 1}"
+        result[key] = time_locate(dev, opts.search, opts.levels)
     if "tour" in parts:
         result["tour"] = tour(dev, opts.frames)
     with open(opts.out, "w") as f:
