@@ -778,12 +778,29 @@ int rtgs_white_balance_apply(const float* color_chw, int32_t H, int32_t W, const
  *          w' = fmaf(-az, bz, fmaf(-ay, by, fmaf(-ax, bx, aw bw)))     x' = fmaf(-az, by, fmaf(ay, bz, fmaf(ax, bw, aw bx)))
  *          y' = fmaf(az, bx, fmaf(ay, bw, fmaf(-ax, bz, aw by)))       z' = fmaf(az, bw, fmaf(-ay, bx, fmaf(ax, by, aw bz)))
  *        not normalised: the raw quaternion keeps its norm up to the rounding of a unit q_D
- *   Opacity, scales and the SH block are not touched (the higher SH bands are NOT rotated).  No atomics, no host read, two runs
+ *   Opacity, scales and the SH block are not touched (the higher SH bands are NOT rotated unless loop_closure_rotate_sh: then
+ *   rtgs_map_deform_sh below turns them behind this call).  No atomics, no host read, two runs
  *   are bit-equal.  Returns 0 (also, without a launch, for N == 0), -1 on a null or misaligned pointer, N < 0 or above
  *   RTGS_MAP_DEFORM_MAX_ROWS, n_frames < 1 or an unknown tick_kind, -2 on a launch failure. */
 #define RTGS_MAP_DEFORM_MAX_ROWS 2147483647LL
 int rtgs_map_deform(float* xyz, float* raw8, const void* tick, int32_t tick_kind, int64_t N, const float* table,
                     int32_t n_frames, void* stream);
+
+/* rtgs_map_deform_sh (csrc/map_deform_sh.hip).  The higher SH bands of the same rows turn with the correction's rotation.
+ *   shs [N][16][3] float32 (coefficient-major, channel-minor), 16-B aligned, updated IN PLACE; tick, tick_kind and the clamp of f
+ *   as above; sh_table [n_frames][84] float32, 16-B aligned (336 B a row): per frame the matrices M1 [3][3], M2 [5][5], M3 [7][7]
+ *   with Y_l(R d) = M_l Y_l(d) for the basis functions of the rasterizer (rtg_slam_amd/sh_rotation.py, built on the host in
+ *   float64 and rounded), row-major, 9 + 25 + 49 values, then one flag.  Per row, float32:
+ *     1  f = tick clamped to [0, n_frames - 1]
+ *     2  if the flag sh_table[f][83] compares equal to 0 the row is NOT written: it stays bit-identical, -0.0 included
+ *     3  coefficient 0 is not touched; for each band (coefficients 1..3, 4..8, 9..15: n = 3, 5, 7), each output i and each channel,
+ *        with x the band's n coefficients of that channel:
+ *          acc = M[i][n-1] * x[n-1];   for j = n-2 .. 0:  acc = fmaf(M[i][j], x[j], acc);   coefficient (first + i) = acc
+ *   tests/map_deform_sh_reference.py restates it in numpy float32; the kernel matches it bit for bit.  No atomics, no host read,
+ *   two runs are bit-equal.  Returns 0 (also, without a launch, for N == 0), -1 on a null or misaligned pointer, N < 0 or above
+ *   RTGS_MAP_DEFORM_MAX_ROWS, n_frames < 1 or an unknown tick_kind, -2 on a launch failure. */
+int rtgs_map_deform_sh(float* shs, const void* tick, int32_t tick_kind, int64_t N, const float* sh_table, int32_t n_frames,
+                       void* stream);
 
 /* ---- loop closure: place recognition by appearance (no counterpart in the reference, whose ORB back end recognises places by a
  * trained vocabulary; csrc/place.hip).  tests/place_reference.py is the definition, in numpy; both kernels match it bit for bit.

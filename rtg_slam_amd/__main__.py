@@ -53,6 +53,9 @@ optimisation (rtg_slam_amd.loop_closure): keyframe pairs whose estimated poses l
 the accepted ones join a keyframe pose graph, and the trajectory, the keyframes and the map's Gaussians move with the optimum.
 save_traj/pose_es.npy is then the corrected trajectory, save_traj/pose_es_before_loop_closure.npy the tracked one, and
 run_report.json gains `loop_closure`; the keys go into config.yaml only when given.  Not with use_gt_pose.
+The Gaussians' centres and rotations move; their higher SH bands keep pointing where they did unless `--loop-closure-rotate-sh`
+(config key loop_closure_rotate_sh; needs --loop-closure, written only when given) turns them with each frame's correction as
+well (rtg_slam_amd.sh_rotation, rtgs_map_deform_sh); the report then gains `sh_rotated` and its `seconds` the stage `sh_table`.
 `--loop-closure-candidates appearance` (or `both`) finds the pairs by what the keyframes look like instead of (or besides) where
 the trajectory puts them (rtg_slam_amd.place_recognition: thumbnails compared by ZNCC over a horizontal shift, depth thumbnails
 as a second witness), so that a loop whose drift exceeds --loop-closure-max-trans is still found; --loop-closure-thumb-width,
@@ -221,6 +224,10 @@ def _apply_loop_closure(args, opts) -> str | None:
         if not getattr(args, "loop_closure", False):
             return "--loop-closure-keypoint-ransac needs --loop-closure (or loop_closure: true in the config)"
         args.loop_closure_keypoint_ransac = opts.loop_closure_keypoint_ransac
+    if getattr(opts, "loop_closure_rotate_sh", False):                       # a store_true flag, no key of DEFAULTS either
+        if not getattr(args, "loop_closure", False):
+            return "--loop-closure-rotate-sh needs --loop-closure (or loop_closure: true in the config)"
+        args.loop_closure_rotate_sh = True
     if not getattr(args, "loop_closure", False):
         return None
     if getattr(args, "use_gt_pose", False):
@@ -337,7 +344,8 @@ def cmd_slam(opts) -> int:
         if hasattr(args, "map_exposure_channels"):
             log(f"map exposure: channels {args.map_exposure_channels}")
     if getattr(args, "loop_closure", False):
-        log("loop closure: on (once, after the last frame: keyframe pose graph, corrected trajectory, deformed map)")
+        log("loop closure: on (once, after the last frame: keyframe pose graph, corrected trajectory, deformed map"
+            + (", higher SH bands turned with it)" if getattr(args, "loop_closure_rotate_sh", False) else ")"))
     if getattr(args, "relocalise", False):
         log("relocalise: on (a frame ICP cannot hold is not mapped; lost frames are searched for among the keyframes)")
     if "device_list" in vars(args):
@@ -919,6 +927,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--loop-closure-keypoint-ransac", choices=("host", "device"), default=None,
                    help="where the keypoint pose's match filter and RANSAC run: on the host per candidate (default), or in one "
                         "rtgs_rigid_ransac launch for all candidates")
+    s.add_argument("--loop-closure-rotate-sh", action="store_true",
+                   help="the deformed map's higher SH bands turn with each frame's correction as well (rtgs_map_deform_sh); "
+                        "without it they keep pointing where they did (default)")
     m = sub.add_parser("metric", help="evaluate a saved model (metric.py)")
     m.add_argument("--config", required=True)
     m.add_argument("--load-frame", type=int, default=-1)

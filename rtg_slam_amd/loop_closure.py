@@ -7,6 +7,7 @@
     frame_corrections   the keyframes' corrections T'_k T_k^-1 spread over all frames along SE(3) geodesics
     deform_table        those corrections as the float32 table of rtgs_map_deform (include/rtgs_slam.h)
     LoopCloser.close    candidates -> edges -> pose_graph.optimize -> trajectory, keyframes and map moved
+    (sh_rotation)       with loop_closure_rotate_sh, the map's higher SH bands turned by each frame's correction as well
 
 The option (`loop_closure: True`) is off by default and runs once, after the last frame and before the final global optimisation
 (slam.run_sequence).  By default (loop_closure_candidates "pose") candidates come from the estimated poses alone, so a loop whose
@@ -83,6 +84,8 @@ KEYPOINT_SEARCH_TABLE_BYTES = 64 << 20
 # the key is absent) is keypoints.pose_from_matches per candidate; "device" is one rtgs_rigid_ransac launch for all candidates
 # (keypoints.rigid_ransac_pairs).  Kept out of DEFAULTS: absent or "host", no report and no launch knows of it
 KEYPOINT_RANSACS = ("host", "device")
+# loop_closure_rotate_sh (a bool, absent = False): the higher SH bands of the deformed map turn with each frame's correction
+# (sh_rotation.sh_rotation_table, rtgs_map_deform_sh).  Kept out of DEFAULTS: absent or False, no report and no launch knows of it
 # register_pair's figures, None in a candidate that keypoints_strict refused without registering it
 REGISTER_FIGURES = ("refine_reason", "iterations", "rank_min", "rms_geometric_before", "rms_geometric_after", "device_s", "inliers",
                     "valid_source_pixels", "inlier_ratio", "correction_trans", "correction_rot_deg")
@@ -296,6 +299,9 @@ class LoopCloser:
         if self.keypoints.init != "yaw" and pl.candidates == "pose":
             raise ValueError("loop_closure_appearance_init applies to appearance candidates: it needs loop_closure_candidates "
                              "appearance or both")
+        self.rotate_sh = getattr(args, "loop_closure_rotate_sh", False)
+        if not isinstance(self.rotate_sh, bool):
+            raise ValueError("loop_closure_rotate_sh must be true or false")
         from .rgbd_align import RgbdRefiner
         exposure = bool(getattr(args, "rgbd_refine_exposure", False)) or bool(getattr(args, "map_exposure", False))
         ref_args = SimpleNamespace(**{k: v for k, v in vars(args).items() if k.startswith(("rgbd_refine_", "icp_"))})
@@ -529,7 +535,15 @@ class LoopCloser:
                 rot[:3, :3] = D[ids[k]][:3, :3]
                 km["normal_map_w"] = slam_ops.transform_map(km["normal_map_w"], torch.from_numpy(rot))
         table = torch.from_numpy(deform_table(D)).to(dev)
-        mapper.opt.deform_rows(table)
+        if self.rotate_sh:
+            from .sh_rotation import sh_rotation_table
+            ts = time.perf_counter()
+            sh_table = torch.from_numpy(sh_rotation_table(D)).to(dev)
+            rep["seconds"]["sh_table"] = time.perf_counter() - ts
+            rep["sh_rotated"] = True
+            mapper.opt.deform_rows(table, sh_table=sh_table)
+        else:
+            mapper.opt.deform_rows(table)
         torch.cuda.synchronize(dev)
         t4 = time.perf_counter()
         rep["changed"] = True

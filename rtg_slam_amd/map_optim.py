@@ -744,7 +744,7 @@ class ShardedMapOptimizer:
         _lib.check(rc, "rtgs_history_merge")
         self._act_valid = False            # scaling and rotation moved outside the step's tail
 
-    def deform_rows(self, table: torch.Tensor, tick: Optional[torch.Tensor] = None):
+    def deform_rows(self, table: torch.Tensor, tick: Optional[torch.Tensor] = None, sh_table: Optional[torch.Tensor] = None):
         """Move every row - frozen and trainable - by the rigid correction of the frame that added it (rtgs_map_deform,
         include/rtgs_slam.h): `table` float32 [n_frames, 16] on the device (loop_closure.deform_table), `tick` int32 or int64
         [>= N] or [>= N, 1], default aux["add_tick"].  A row a release moved back to the unstable cloud carries the tick of its
@@ -752,7 +752,11 @@ class ShardedMapOptimizer:
         optimisations: it raises inside a global optimisation and on several ranks, and a local optimisation that was still
         open loses its snapshots, so that its history_merge() refuses instead of blending the old positions back in.
         Everything derived from the old rows is dropped: the activated copies, the attach and history snapshots, and - through
-        `version`, `_frozen_version` and the map epoch - the renders, neighbour structures and per-row cull results others keep."""
+        `version`, `_frozen_version` and the map epoch - the renders, neighbour structures and per-row cull results others keep.
+        `sh_table` float32 [n_frames, 84] on the device (sh_rotation.sh_rotation_table, the same n_frames as `table`): behind
+        rtgs_map_deform, on the same stream and with the same tick, rtgs_map_deform_sh turns the higher SH bands of the rows whose
+        correction rotates; None (the default) leaves the SH block alone and never calls it.  The Adam moments of the SH block
+        are left as they are, as those of xyz and the rotation are: they describe gradients in the old frame and decay."""
         from . import _lib
         if self._scope != "local" or self.world != 1:
             raise RuntimeError("deform_rows(): one rank, local scope (not inside a global optimisation)")
@@ -762,6 +766,12 @@ class ShardedMapOptimizer:
         if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2
                 and table.shape[1] == 16 and table.shape[0] >= 1 and table.is_contiguous() and table.device == self.device):
             raise ValueError("deform_rows(): table must be a contiguous float32 [n_frames, 16] on the map's device")
+        if sh_table is not None and not (
+                torch.is_tensor(sh_table) and sh_table.is_cuda and sh_table.dtype == torch.float32 and sh_table.dim() == 2
+                and sh_table.shape[1] == 84 and sh_table.shape[0] == table.shape[0] and sh_table.is_contiguous()
+                and sh_table.device == self.device):
+            raise ValueError("deform_rows(): sh_table must be a contiguous float32 [n_frames, 84] on the map's device, n_frames "
+                             "that of table")
         if tick.dtype not in (torch.int32, torch.int64) or tick.device != self.device or not tick.is_contiguous():
             raise ValueError("deform_rows(): tick must be a contiguous int32 or int64 array on the map's device")
         if tick.numel() != tick.shape[0] or tick.shape[0] < self.N:
@@ -779,7 +789,11 @@ class ShardedMapOptimizer:
             rc = lib.rtgs_map_deform(_lib.ptr(st["xyz"]["p"]), _lib.ptr(st["raw8"]["p"]), _lib.ptr(tick),
                                      0 if tick.dtype == torch.int32 else 1, int(self.N), _lib.ptr(table), int(table.shape[0]),
                                      _lib.stream(dev))
-        _lib.check(rc, "rtgs_map_deform")
+            _lib.check(rc, "rtgs_map_deform")
+            if sh_table is not None:
+                rc = lib.rtgs_map_deform_sh(_lib.ptr(st["shs"]["p"]), _lib.ptr(tick), 0 if tick.dtype == torch.int32 else 1,
+                                            int(self.N), _lib.ptr(sh_table), int(sh_table.shape[0]), _lib.stream(dev))
+                _lib.check(rc, "rtgs_map_deform_sh")
         self._act_valid = False             # rotations and the normals derived from them moved
         self.attach_init = None             # snapshots of the old positions: the next begin_local_optimization() retakes them
         self._history = None

@@ -35,6 +35,18 @@
                the stream's true relative pose, where every first guess came from, ATE RMSE plain and aligned before and after.
     bench_ab   as above.
 
+--sh measures the rotation of the SH bands (rtg_slam_amd/sh_rotation.py, csrc/map_deform_sh.hip) instead
+-> profiles/r31_sh_rotation.json:
+
+    kernels    rtgs_map_deform_sh at 300 000 and 1 200 000 rows over a 2 000-frame table with every row flagged, int32 ticks
+               in ascending runs (a real map: the waves share one frame) and drawn at random (the worst case: every lane gathers
+               its own matrix): device events, a warm-up, 5 blocks of CALLS launches; median and range per launch and the
+               counted bytes per second (360 B a moved row: 45 floats in and out).  Beside it, in the same process and with the
+               same ticks, rtgs_map_deform (60 B a row) and the plain torch form the kernel replaces - the [N,7,7], [N,5,5] and
+               [N,3,3] matrices gathered by tick and three batched products.  And the host time of sh_rotation_table for the
+               2 000 frames.
+    bench_ab   as above.
+
 --texture runs the sequence of any arm in the textured room."""
 import argparse
 import json
@@ -92,6 +104,84 @@ def time_kernels(dev):
         rows.append(row)
         print(row, flush=True)
     return rows
+
+
+def time_sh_kernels(dev):
+    import time
+    import numpy as np
+    import torch
+    from rtg_slam_amd import _lib, loop_closure as lc, sh_rotation as shr
+    from rtg_slam_amd.rgbd_align import se3_exp
+    lib = _lib.load()
+    step = se3_exp([0.0, np.deg2rad(1.0) / TABLE_FRAMES, 0.0, 0.05 / TABLE_FRAMES, 0.0, 0.0])
+    D, cur = [], np.eye(4)
+    for _ in range(TABLE_FRAMES):                                             # the drift of time_kernels: to 1 degree and 5 cm
+        cur = cur @ step
+        D.append(cur.copy())
+    D = np.stack(D)
+    host = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        sh_np = shr.sh_rotation_table(D)
+        host.append(time.perf_counter() - t0)
+    assert sh_np[:, 83].all()
+    sh_table = torch.from_numpy(sh_np).to(dev)
+    table = torch.from_numpy(lc.deform_table(D)).to(dev)
+    M = [sh_table[:, at:at + n * n].reshape(-1, n, n).contiguous() for n, at in ((3, 0), (5, 9), (7, 34))]
+
+    def blocks(call):
+        for _ in range(20):
+            call()
+        torch.cuda.synchronize(dev)
+        us = []
+        for _ in range(BLOCKS):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(CALLS):
+                call()
+            b.record()
+            b.synchronize()
+            us.append(1e3 * a.elapsed_time(b) / CALLS)
+        return {"median": round(statistics.median(us), 2), "min": round(min(us), 2), "max": round(max(us), 2)}
+
+    out = {"sh_rotation_table_host_ms": {"frames": TABLE_FRAMES, "median": round(1e3 * statistics.median(host), 2),
+                                         "min": round(1e3 * min(host), 2), "max": round(1e3 * max(host), 2)}, "rows": [],
+           "what": "launch-to-launch times of back-to-back launches on the same rows: 58 MB of SH rows at 300 k and 230 MB at 1.2 M "
+                   "stay in or near the 256 MiB Infinity Cache between launches, so the counted TB/s are not HBM rates"}
+    for N in (300_000, 1_200_000):
+        g = torch.Generator(device="cpu").manual_seed(1)
+        shs = (torch.randn(N, 16, 3, generator=g) * 0.05).to(dev)
+        xyz = (torch.rand(N, 3, generator=g) * 4 - 2).to(dev)
+        raw8 = torch.randn(N, 8, generator=g).to(dev)
+        ticks = {"runs": ((torch.arange(N, dtype=torch.int64) * TABLE_FRAMES) // N).to(torch.int32),
+                 "random": torch.randint(0, TABLE_FRAMES, (N,), generator=g, dtype=torch.int32)}
+        for name, tick in ticks.items():
+            tick = tick.to(dev)
+            long_tick = tick.long()
+
+            def kernel():
+                assert lib.rtgs_map_deform_sh(_lib.ptr(shs), _lib.ptr(tick), 0, N, _lib.ptr(sh_table), TABLE_FRAMES, _lib.stream(dev)) == 0
+
+            def rigid():
+                assert lib.rtgs_map_deform(_lib.ptr(xyz), _lib.ptr(raw8), _lib.ptr(tick), 0, N, _lib.ptr(table), TABLE_FRAMES,
+                                           _lib.stream(dev)) == 0
+
+            def torch_form():
+                for (first, n), m in zip(((1, 3), (4, 5), (9, 7)), M):
+                    shs[:, first:first + n] = torch.bmm(m[long_tick], shs[:, first:first + n])
+            row = {"rows": N, "ticks": name, "table_frames": TABLE_FRAMES, "calls_per_block": CALLS, "blocks": BLOCKS,
+                   "us_per_launch": {"rtgs_map_deform_sh": blocks(kernel), "rtgs_map_deform": blocks(rigid), "torch_form": blocks(torch_form)},
+                   "note": "per launch = host enqueue included; every row is moved; the rows are turned in place again and again by "
+                           "orthogonal matrices, so they keep their size"}
+            us = row["us_per_launch"]
+            row["counted_TB_per_s_at_median"] = {"rtgs_map_deform_sh (360 B a row)": round(360 * N / us["rtgs_map_deform_sh"]["median"] * 1e-6, 3),
+                                                 "rtgs_map_deform (60 B a row)": round(60 * N / us["rtgs_map_deform"]["median"] * 1e-6, 3),
+                                                 "torch_form (360 B a row)": round(360 * N / us["torch_form"]["median"] * 1e-6, 3)}
+            row["kernel_beats_torch_form"] = bool(us["rtgs_map_deform_sh"]["median"] < us["torch_form"]["median"])
+            row["finite"] = bool(torch.isfinite(shs).all())
+            out["rows"].append(row)
+            print(row, flush=True)
+    return out
 
 
 def time_place_kernels(dev):
@@ -286,12 +376,13 @@ def main():
     ap.add_argument("--keypoint-search", action="store_true",
                     help="run the textured sequence with loop_closure_candidates keypoints at --levels levels (r30_keypoint_pyramid_tour.json)")
     ap.add_argument("--levels", type=int, default=3)
+    ap.add_argument("--sh", action="store_true", help="measure the rotation of the SH bands instead (r31_sh_rotation.json)")
     ap.add_argument("--texture", action="store_true", help="run the sequence in the textured room (always so with --keypoints)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--parts", default="kernels,sequence", help="what to measure now; an existing --out file keeps its other parts")
     opts = ap.parse_args()
     parts = set(opts.parts.split(","))
-    opts.out = opts.out or os.path.join(ROOT, "profiles", "r30_keypoint_pyramid_tour.json" if opts.keypoint_search else "r28_keypoints.json" if opts.keypoints else
+    opts.out = opts.out or os.path.join(ROOT, "profiles", "r31_sh_rotation.json" if opts.sh else "r30_keypoint_pyramid_tour.json" if opts.keypoint_search else "r28_keypoints.json" if opts.keypoints else
                                         "r27_place_recognition.json" if opts.appearance else "r26_loop_closure.json")
     result = json.load(open(opts.out)) if os.path.exists(opts.out) else {}
     if opts.parent_tree:                                      # first: this process has not opened the GPU yet
@@ -301,6 +392,10 @@ def main():
         raise SystemExit("loop_closure_check.py needs a GPU; nothing was measured")
     dev = torch.device("cuda", 0)
     result["device"] = torch.cuda.get_device_name(dev)
+    if opts.sh:                                               # no sequence of its own: the tour's closure is r26's
+        if "kernels" in parts:
+            result["kernels"] = time_sh_kernels(dev)
+        parts = set()
     if opts.keypoint_search:                                  # its kernels are timed by tools/keypoint_pyramid_check.py
         result["sequence"] = sequence(dev, opts.frames, "keypoints", True, levels=opts.levels)
         parts = set()
